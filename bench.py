@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — ANI pairs/sec, many-to-many NxN ~5 Mbp genomes (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config many-to-many|one-to-many|c4|c5]
+    python bench.py --gpus 1 --steps K --warmup W [--config many-to-many|one-to-many|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...        (no launcher around it: bench.py starts its N ranks itself, see self_launch)
 
@@ -16,7 +16,7 @@ Workloads (config.workload):
               fixed, every GPU maps its own 1000 query genomes (rank r maps variant r of the clustered set; variant 0 is the
               reference set itself), each rank sketches 1/N of the references, the 12-byte minimizer records are all-gathered
               once over RCCL/xGMI while the rank sketches its queries' fragments, and every rank builds the full index.
-              value = N x 10^6 pairs / step.  The STRONG-scaling figure is measured beside it (strong_scaling_leg; --scaling strong
+              value = N x 10^6 pairs / step.  With --full the STRONG-scaling figure is measured beside it (strong_scaling_leg; --scaling strong
               makes it the timed region and the weak job the leg): the SAME 1000 x 1000 job on N GPUs, reference-sharded — rank r
               hashes genomes [r*1000/N, (r+1)*1000/N) once for both roles, indexes that shard only, and the ranks' packed fragment
               sketches are all-gathered (one collective, under the mapping of the rank's own set): nothing is replicated.  The
@@ -24,7 +24,7 @@ Workloads (config.workload):
       --simulate-world W (one GPU): the compute of ONE rank of the W-GPU strong job, without communication — the measured
               per-rank time behind the predicted W-GPU figure.
   one-to-many = configs[1]: 1 query genome (cluster 0, member 1) against the 1000-genome set; a step still sketches and
-      indexes the references (the reference does too); the map-only latency is reported beside it.
+      indexes the references (the reference does too); with --full the map-only latency is reported beside it.
   c5 = configs[4]'s reference side: a reference set that does not stay resident (default 30 000 x 5 Mbp, --genomes 90000 for the
       full count; generated and sketched slice by slice; only the 12-byte minimizer records of one BLOCK of references stay
       (--ref-block, default: a third of the device memory), the block's index is streamed chunk by chunk, every query is mapped
@@ -37,10 +37,16 @@ Workloads (config.workload):
               the ranks' query fragment sketches go round a ring (isend/irecv over RCCL, overlapped with the mapping) and every rank
               maps every query against its shard.  No replicated index build, 1/N of the index memory per GPU.
 
-Prints ONE JSON line on rank 0 (see the driver contract): value = whole-job pairs/sec, plus
+Prints ONE JSON line on rank 0 (see the driver contract): value = whole-job pairs/sec, ms_per_step = one timed step, plus
   roofline     — the dominant kernel (L2 sliding MinHash), algorithmic bytes (12*m_c + 4*s per candidate)
                  over its HIP-event time on the launch stream, against the 8 TB/s HBM peak; .stage = the L2 stage as a
-                 whole on the same bytes; .int_ops = the two hashing kernels against the VALU integer ceiling;
+                 whole on the same bytes; .int_ops = the two hashing kernels against the VALU integer ceiling
+                 (from the library's counters of the timed steps: no run of its own).
+--dump-outputs DIR writes the CGI rows of the last timed step (bench.py: dump_outputs).  Only with --full (a plain run sets up, warms
+up, times --steps steps and prints the line):
+  rows_identical_across_steps, rows_multiset — the timed steps' rows checksummed against each other, and over all ranks against the
+                 stored value of the standard job;
+  weak_scaling_leg / strong_scaling_leg (N > 1), map_only (one-to-many) — measurements of their own beside the timed region;
   parity_timed_rows — the rows of the LAST TIMED STEP compared with the untouched reference binary (every reference x
                  the CPU-baseline queries) and with the C oracle on >= 200 random pairs;
   cpu_baseline — oracle/_ref/fastANI_ref (the untouched reference, built by oracle/Makefile) timed on this box's host cores
@@ -95,6 +101,13 @@ def parse():
     ap.add_argument("--dry-collectives", action="store_true", help="N > 1: run ONLY the collectives of the multi-rank step — the one-word all-reduce, the in-place all-gather with the "
                     "real slot size of the workload, the barrier — 10 times, print per-rank seconds and GB/s as one JSON line and leave (tells a hang from a slow link in ~30 s)")
     ap.add_argument("--dump-rows", default="", help="write the rows of the last timed step to <path>[.rank<r>].npy (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the CGI rows of the last timed step to DIR/<field>.npy, one float array per field, rows in (query, reference) "
+                         "order (N > 1: DIR/<field>_rank<r>.npy); above 64 MB a fixed, seeded sample of the (query, reference) pairs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baseline, the command line end to end, the row checks against the reference binary and the "
+                         "oracle, the determinism and multiset checks of the rows, the other scaling leg (N > 1) and the map-only latency (one-to-many).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
     ap.add_argument("--slice-genomes", type=int, default=1000, help="c5: genomes generated and sketched per slice")
     ap.add_argument("--query-slice", type=int, default=2000, help="c5: query genomes per kept fragment set")
     ap.add_argument("--query-block", type=int, default=0, help="c5: query genomes whose fragment sets are resident together (0 = all of --queries).  With it the queries, too, are generated "
@@ -1037,6 +1050,34 @@ def rows_multiset(R, rows, with_rank0=False):
     return (n, h, n0, h0) if with_rank0 else (n, h)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_FIELDS = (("qryGenomeId", "<f8"), ("refGenomeId", "<f8"), ("countSeq", "<f8"), ("totalQueryFragments", "<f8"), ("identity", "<f4"))
+
+
+def dump_outputs(R, rows, outdir):
+    """--dump-outputs: the CGI rows of the last timed step as one float array per field (ids and counts as float64, exact; identity
+    as the float32 it is), in (query, reference) order, so that two builds can be compared array by array.  Beyond 64 MB the rows of
+    a fixed, seeded sample of the (query, reference) pairs are kept: a pair is in or out by a hash of its ids alone, the same pairs
+    whatever else a build finds (the share 2^-k changes only with the size of the output)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    row_bytes = sum(np.dtype(dt).itemsize for _, dt in DUMP_FIELDS)
+    if len(rows) * row_bytes > DUMP_LIMIT_BYTES:
+        with np.errstate(over="ignore"):
+            h = (rows["qryGenomeId"].astype(np.uint64) << np.uint64(32)) | rows["refGenomeId"].astype(np.uint32).astype(np.uint64)
+            h = (h + np.uint64(R.args.seed)) * np.uint64(0x9E3779B97F4A7C15)
+            h ^= h >> np.uint64(31)
+            h *= np.uint64(0xBF58476D1CE4E5B9)
+            h ^= h >> np.uint64(29)
+        # one pair in 2^k, k as small as keeps the expected size 5 % under the limit: k moves only when the row count doubles
+        k = int(np.ceil(np.log2(len(rows) * row_bytes / (0.95 * DUMP_LIMIT_BYTES))))
+        rows = rows[(h >> np.uint64(64 - k)) == 0]
+    rows = rows[np.lexsort((rows["refGenomeId"], rows["qryGenomeId"]))]
+    suffix = "_rank%d" % R.rank if R.world > 1 else ""
+    for name, dt in DUMP_FIELDS:
+        np.save(os.path.join(outdir, name + suffix + ".npy"), rows[name].astype(dt))
+
+
 def sync(R):
     dev_sync(R)
     if R.dist is not None:
@@ -1072,8 +1113,9 @@ def settle(R, budget_s=5.0, need=5):
             "what": "before the warm-up steps: 1 GiB read-modify-write probes until %d in a row run within 1.5 x the fastest (a device still busy with an earlier process's leftovers would disturb the first steps)" % need}
 
 
-def timed_loop(R, step, steps, warmup):
-    """W untimed warm-up steps, then exactly K steps bracketed by barrier + device synchronisation; the job's time is the MAX over ranks"""
+def timed_loop(R, step, steps, warmup, check=True):
+    """W untimed warm-up steps, then exactly K steps bracketed by barrier + device synchronisation; the job's time is the MAX over ranks.
+    check = False: only the last step's rows are kept past the timed region and no checksums are taken (rows_crc = None)"""
     import zlib
     import numpy as np
     for _ in range(warmup):
@@ -1100,13 +1142,15 @@ def timed_loop(R, step, steps, warmup):
     dt_local = time.perf_counter() - t0
     # a step may hand its rows back as the arrays of its mapping calls: one array from here on (outside the timed region)
     from fastani_amd.multi_gpu import join_rows
+    if not check:
+        rows_all = rows_all[-1:]
     rows_all = [join_rows(r) if isinstance(r, list) else r for r in rows_all]
     rows = rows_all[-1] if rows_all else rows
     # outside the timed region: every step must have produced the same rows (run-to-run determinism)
-    crc = [zlib.crc32(np.ascontiguousarray(r).view(np.uint8)) & 0xffffffff for r in rows_all]          # (a view: no copy of the rows)
+    crc = [zlib.crc32(np.ascontiguousarray(r).view(np.uint8)) & 0xffffffff for r in rows_all] if check else None     # (a view: no copy of the rows)
     del rows_all
     if dropped:                                              # --drop-rows: the steps' own counts and running checksums stand for the rows
-        crc = [c for _, c in dropped]
+        crc = [c for _, c in dropped] if check else None
         R.rows_last_step = dropped[-1][0]
     dt = dt_local
     if R.dist is not None:
@@ -1187,20 +1231,24 @@ def main():
     if mode == "simulate":
         prepare_simulation(R)
     R.settle = settle(R)
-    res = timed_loop(R, STEPS[mode], args.steps, args.warmup)
+    res = timed_loop(R, STEPS[mode], args.steps, args.warmup, check=args.full)
     rows, dt = res["rows"], res["dt"]
     rank_info = gather_rank_info(R, res, args.steps, mode) if R.dist is not None else None
-    # the rows of the last timed step over all ranks as (count, multiset hash); --drop-rows jobs keep no rows and carry their own checksums
-    R.rows_multiset = rows_multiset(R, rows, with_rank0=True) if not getattr(R, "drop_rows", False) and mode != "simulate" else None
+    # --full: the rows of the last timed step over all ranks as (count, multiset hash); --drop-rows jobs keep no rows and carry their own checksums
+    R.rows_multiset = rows_multiset(R, rows, with_rank0=True) if args.full and not getattr(R, "drop_rows", False) and mode != "simulate" else None
     c = e.counters()
     host_timeline = {k: round(v / args.steps, 2) for k, v in R.timers.items() if v}
     if args.dump_rows:
         np.save(args.dump_rows + (".rank%d" % rank if R.multi else "") + ".npy", rows)
+    if args.dump_outputs:
+        dump_outputs(R, rows, args.dump_outputs)
+
+    # everything below up to the report is --full only: the extra scaling legs, the map-only latency, and (in report) the CPU legs and row checks
 
     # N > 1, headline set: the timed region above is the STRONG-scaling job (fixed 1000 x 1000); the weak-scaling figure of the same
     # kernels (fixed database, 1000 queries per GPU) is measured beside it, outside the contract's timed region
     weak_leg = None
-    if mode == "ring" and cfg == "many-to-many" and not args.no_weak_leg:
+    if args.full and mode == "ring" and cfg == "many-to-many" and not args.no_weak_leg:
         # (the contract's figure is already in hand: whatever happens in this extra leg must not cost the line — a failure here is
         # reported inside it.  The state the report reads is put back afterwards.)
         keep = (R.nq_local, R.first_query_id)
@@ -1224,7 +1272,7 @@ def main():
     # same kernels — the fixed NR x NR job, references sharded — is measured beside it; its rows over all ranks are the standard job's
     # rows, so its rows_multiset is held against the stored value: the row check of a multi-rank hardware run.
     strong_leg = None
-    if mode == "gather" and cfg == "many-to-many" and not args.no_strong_leg and not args.queries:
+    if args.full and mode == "gather" and cfg == "many-to-many" and not args.no_strong_leg and not args.queries:
         keep = (R.nq_local, R.first_query_id, R.qrys, R.n_queries_total, R.mode)
         try:
             R.nq_local, R.qrys, R.first_query_id, R.n_queries_total, R.mode = R.hi - R.lo, R.my_refs, R.lo, NR, "ring"
@@ -1246,7 +1294,7 @@ def main():
 
     # one-to-many: the latency-shaped number — map the one query against a resident index
     map_only = None
-    if cfg == "one-to-many" and rank == 0:
+    if args.full and cfg == "one-to-many" and rank == 0:
         from fastani_amd.api import Sketch
         sk = Sketch(e, p, R.refs)
         sk.map_cgi_batch(R.qrys, R.first_query_id)
@@ -1389,12 +1437,14 @@ def report(R, args, res, c, rank_info, host_timeline, weak_leg, map_only, strong
                       "name": cfg, "ref_genomes": NR, "query_genomes": n_queries_total, "genome_len": L, "inputs": "2-bit packed, resident in HBM" if cfg != "c5" else "2-bit packed, generated in HBM slice by slice inside the step",
                       "all_vs_all_single_hash_pass": bool(fused), "mode": mode,
                       "index_chunks": int(c["indexChunks"] // max(1, args.steps))},
-           "rows_last_step": int(getattr(R, "rows_last_step", len(rows))), "rows_identical_across_steps": len(set(res["rows_crc"])) == 1, "step_ms_rank0": res["step_ms"],
+           "rows_last_step": int(getattr(R, "rows_last_step", len(rows))), "step_ms_rank0": res["step_ms"],
            "stage_ms_per_step_rank0": stages, "host_timeline_ms_per_step_rank0": host_timeline, "l1_big_path": {"fragments_per_step": int(c["l1BigFragments"] // args.steps), "ms_per_step": round(c["msL1Big"] / args.steps, 3)},
            "counters_per_step_rank0": {k: int(c[k] // args.steps) for k in ("refMinimizers", "queryFragments", "seedHits", "l1Candidates",
                                                                           "l2WindowEntries", "l2Steps", "l2FastCandidates", "l2SlowCandidates",
                                                                           "l2SlowLimit", "l2SlowDup", "l2SlowOverflow", "cgiRows", "indexChunkBuilds", "l1Probes", "l1MidFragments", "l1TinyFragments")},
            "roofline": roof}
+    if res["rows_crc"] is not None:                          # --full
+        out["rows_identical_across_steps"] = len(set(res["rows_crc"])) == 1
     if sim:
         out["simulated"] = {"world": R.W, "rank": R.r, "what": "value = %d x %d pairs / the time ONE rank of a %d-GPU strong-scaling job computes (sketch + index of its %d genomes, %d mapping calls: its own set, the others merged); "
                                                               "the all-gather of the packed fragment sets (%d bytes per rank) runs under the mapping of the rank's own set and is not in it"
@@ -1432,11 +1482,11 @@ def report(R, args, res, c, rank_info, host_timeline, weak_leg, map_only, strong
         out["strong_scaling_leg"] = strong_leg
     if map_only:
         out["map_only"] = map_only
-    if world == 1 and mode == "single" and not R.multi and not (args.no_cpu_baseline and args.no_e2e and args.no_verify):
+    if args.full and world == 1 and mode == "single" and not R.multi and not (args.no_cpu_baseline and args.no_e2e and args.no_verify):
         qids = [int(q) for q in R.sample_queries] if getattr(R, "drop_rows", False) else list(range(R.first_query_id, R.first_query_id + nq_local))
         legs = cpu_legs(args, e, p, rows, NR, qids, L)
         out.update(legs)
-    elif (mode == "simulate" or R.multi) and world == 1 and not args.no_verify and not R.emu:
+    elif args.full and (mode == "simulate" or R.multi) and world == 1 and not args.no_verify and not R.emu:
         # the rows of a one-rank ring / gather / simulated-rank run against the oracle, pair by pair
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import orc

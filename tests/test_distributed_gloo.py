@@ -166,7 +166,7 @@ def test_bench_orchestration_two_ranks(config, scaling, launcher, emu_engine, tm
     outer = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher else [sys.executable]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(outer + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", config, "--scaling", scaling, "--genomes", "6",
-                                "--genome-len", "24000", "--dump-rows", dump],
+                                "--genome-len", "24000", "--dump-rows", dump, "--full"],
                        capture_output=True, env=dict(env, ANI_BENCH_BACKEND="emu"), timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1]
@@ -271,7 +271,7 @@ def test_bench_c5_reference_blocks(emu_engine, tmp_path):
     dump = os.path.join(str(tmp_path), "rows_dropped")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--config", "c5", "--genomes", str(n), "--queries", str(nq),
                         "--genome-len", str(L), "--ref-block", "3", "--slice-genomes", "2", "--query-slice", "1", "--query-block", "2", "--drop-rows", "--sample-queries", "1",
-                        "--dump-rows", dump], capture_output=True, env=dict(os.environ, ANI_BENCH_BACKEND="emu"), timeout=1200)
+                        "--dump-rows", dump, "--full"], capture_output=True, env=dict(os.environ, ANI_BENCH_BACKEND="emu"), timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
     assert out["rows_last_step"] == len(single) and out["rows_identical_across_steps"]
@@ -279,3 +279,64 @@ def test_bench_c5_reference_blocks(emu_engine, tmp_path):
     got = np.load(dump + ".npy")
     got = got[np.lexsort((got["refGenomeId"], got["qryGenomeId"]))]
     assert len(kept_q) == 1 and np.array_equal(got, single[single["qryGenomeId"] == kept_q[0]])
+
+
+def test_bench_plain_run_dump_outputs(emu_engine, tmp_path):
+    """a plain run (no --full) times --steps steps and prints the line without the checks of --full; --dump-outputs writes the rows of
+    the last timed step as one float array per field, in (query, reference) order, the same arrays from run to run; beyond the size
+    limit a seeded sample of the pairs, the same pairs whatever else is in the rows"""
+    import argparse
+    import json
+    import subprocess
+    from fastani_amd.api import DeviceGenomes, Sketch
+    L, n = 24000, 6
+    words = (L + 15) // 16
+    buf = np.zeros(n * words + 64, dtype=np.uint32)
+    emu_engine.synth_packed(20260925, 0, n, L, buf.ctypes.data)
+    dg = DeviceGenomes(buf.ctypes.data, n, L)
+    single = Sketch(emu_engine, emu_engine.params(), dg).map_cgi_batch(dg, 0)
+    single = single[np.lexsort((single["refGenomeId"], single["qryGenomeId"]))]
+    fields = ("qryGenomeId", "refGenomeId", "countSeq", "totalQueryFragments", "identity")
+    dumps = []
+    for run in range(2):
+        d = os.path.join(str(tmp_path), "out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--genomes", str(n),
+                            "--genome-len", str(L), "--dump-outputs", d], capture_output=True, env=dict(os.environ, ANI_BENCH_BACKEND="emu"), timeout=1200)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 3 and len(out["step_ms_rank0"]) == 3 and out["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in out, k
+        for k in ("rows_identical_across_steps", "rows_multiset", "parity_timed_rows", "end_to_end"):
+            assert k not in out, k
+        got = {f: np.load(os.path.join(d, f + ".npy")) for f in fields}
+        assert sorted(os.listdir(d)) == sorted(f + ".npy" for f in fields)
+        for f in fields:
+            assert got[f].dtype == (np.float32 if f == "identity" else np.float64)
+            assert np.array_equal(got[f], single[f].astype(got[f].dtype)), f
+        dumps.append(got)
+    # the sample of a larger output: rows of whole pairs, in order, under the limit, chosen by the pair alone
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Run:
+        pass
+    R = Run()
+    R.rank, R.world = 0, 1
+    R.args = argparse.Namespace(seed=20260925)
+    many = np.concatenate([single] * 40)
+    many["qryGenomeId"] += np.repeat(np.arange(40, dtype=np.int32) * n, len(single))
+    limit = bench.DUMP_LIMIT_BYTES
+    try:
+        bench.DUMP_LIMIT_BYTES = 36 * len(many) // 2
+        d = os.path.join(str(tmp_path), "sample")
+        bench.dump_outputs(R, many[::-1].copy(), d)
+        q, g = np.load(os.path.join(d, "qryGenomeId.npy")), np.load(os.path.join(d, "refGenomeId.npy"))
+        assert 0 < len(q) and 36 * len(q) <= bench.DUMP_LIMIT_BYTES
+        keys = set(zip(many["qryGenomeId"].tolist(), many["refGenomeId"].tolist()))
+        assert all((int(a), int(b)) in keys for a, b in zip(q, g)) and np.all(np.diff(q * 1000 + g) > 0)
+        bench.dump_outputs(R, many[len(single):], d + "2")            # fewer rows: the pairs kept are the same pairs
+        q2, g2 = np.load(os.path.join(d + "2", "qryGenomeId.npy")), np.load(os.path.join(d + "2", "refGenomeId.npy"))
+        assert set(zip(q2.tolist(), g2.tolist())) == {(a, b) for a, b in zip(q.tolist(), g.tolist()) if a >= n}
+    finally:
+        bench.DUMP_LIMIT_BYTES = limit

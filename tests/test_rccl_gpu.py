@@ -34,7 +34,7 @@ def _single_rows(gpu_engine):
 
 def _bench(args, env=None, launcher=True, port=29650):
     cmd = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher else [sys.executable])
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--genomes", str(N), "--genome-len", str(L), "--no-cpu-baseline", "--no-e2e"] + args
+    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--genomes", str(N), "--genome-len", str(L), "--no-cpu-baseline", "--no-e2e", "--full"] + args
     r = subprocess.run(cmd, capture_output=True, env=dict(os.environ, **(env or {})), timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     return json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])

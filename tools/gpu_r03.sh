@@ -15,7 +15,7 @@ if has tests; then
 fi
 if has bench; then
   echo "== bench" | tee "$OUT/bench.log"
-  timeout 900 python bench.py --steps 10 --warmup 2 2> "$OUT/bench.err" | tee "$OUT/bench.json.log" | cut -c1-600
+  timeout 900 python bench.py --full --steps 10 --warmup 2 2> "$OUT/bench.err" | tee "$OUT/bench.json.log" | cut -c1-600
   tail -3 "$OUT/bench.err"
 fi
 if has prof; then
@@ -28,7 +28,7 @@ fi
 if has cluster; then
   for cs in 100 500; do
     echo "== bench --cluster-size $cs"
-    timeout 900 python bench.py --steps 1 --warmup 1 --cluster-size $cs --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_cs$cs.err" | tee "$OUT/bench_cs$cs.json.log" | cut -c1-400
+    timeout 900 python bench.py --full --steps 1 --warmup 1 --cluster-size $cs --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_cs$cs.err" | tee "$OUT/bench_cs$cs.json.log" | cut -c1-400
     tail -2 "$OUT/bench_cs$cs.err"
   done
 fi
@@ -41,7 +41,7 @@ if has c4big; then
 fi
 if has o2m; then
   echo "== one-to-many"
-  timeout 600 python bench.py --config one-to-many --steps 5 --warmup 1 --no-e2e 2> "$OUT/bench_o2m.err" | tee "$OUT/bench_o2m.json.log" | cut -c1-400
+  timeout 600 python bench.py --full --config one-to-many --steps 5 --warmup 1 --no-e2e 2> "$OUT/bench_o2m.err" | tee "$OUT/bench_o2m.json.log" | cut -c1-400
 fi
 if has pmc; then
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do

@@ -60,7 +60,7 @@ if has pair; then
 fi
 if has bench; then
   echo "== bench" | tee "$OUT/bench.log"
-  timeout 900 python bench.py --steps 10 --warmup 2 2> "$OUT/bench.err" | tee "$OUT/bench.json.log" | cut -c1-900
+  timeout 900 python bench.py --full --steps 10 --warmup 2 2> "$OUT/bench.err" | tee "$OUT/bench.json.log" | cut -c1-900
   tail -3 "$OUT/bench.err"
 fi
 if has prof; then
@@ -79,7 +79,7 @@ fi
 if has sim8; then
   for w in 8; do
     echo "== simulated rank 0 of $w (strong scaling of the 1000 x 1000 set)"
-    timeout 600 python bench.py --steps 5 --warmup 2 --simulate-world $w --oracle-pairs 60 2> "$OUT/sim$w.err" | tee "$OUT/bench_sim$w.json.log" | cut -c1-700
+    timeout 600 python bench.py --full --steps 5 --warmup 2 --simulate-world $w --oracle-pairs 60 2> "$OUT/sim$w.err" | tee "$OUT/bench_sim$w.json.log" | cut -c1-700
     tail -2 "$OUT/sim$w.err"
   done
 fi
@@ -92,14 +92,14 @@ fi
 if has rccl; then
   for cfg in "many-to-many" "c4 --genomes 2000"; do
     echo "== one rank over RCCL: $cfg"
-    ANI_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 3 --warmup 1 --config $cfg --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/rccl.err" | tee "$OUT/rccl_one_rank_$(echo $cfg | cut -d' ' -f1).json.log" | cut -c1-600
+    ANI_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --steps 3 --warmup 1 --config $cfg --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/rccl.err" | tee "$OUT/rccl_one_rank_$(echo $cfg | cut -d' ' -f1).json.log" | cut -c1-600
     tail -2 "$OUT/rccl.err"
   done
 fi
 if has cluster; then
   for cs in 100 500; do
     echo "== bench --cluster-size $cs"
-    timeout 900 python bench.py --steps 1 --warmup 1 --cluster-size $cs --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_cs$cs.err" | tee "$OUT/bench_cs$cs.json.log" | cut -c1-400
+    timeout 900 python bench.py --full --steps 1 --warmup 1 --cluster-size $cs --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_cs$cs.err" | tee "$OUT/bench_cs$cs.json.log" | cut -c1-400
     tail -2 "$OUT/bench_cs$cs.err"
   done
 fi
@@ -109,12 +109,12 @@ if has c4; then
 fi
 if has c5; then
   echo "== c5: ${C5_GENOMES:-30000} references (streamed index) x 300 queries"
-  timeout 1500 python bench.py --config c5 --genomes ${C5_GENOMES:-30000} --queries 300 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_c5.err" | tee "$OUT/bench_c5.json.log" | cut -c1-900
+  timeout 1500 python bench.py --full --config c5 --genomes ${C5_GENOMES:-30000} --queries 300 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/bench_c5.err" | tee "$OUT/bench_c5.json.log" | cut -c1-900
   tail -3 "$OUT/bench_c5.err"
 fi
 if has o2m; then
   echo "== one-to-many"
-  timeout 600 python bench.py --config one-to-many --steps 5 --warmup 1 --no-e2e 2> "$OUT/bench_o2m.err" | tee "$OUT/bench_o2m.json.log" | cut -c1-400
+  timeout 600 python bench.py --full --config one-to-many --steps 5 --warmup 1 --no-e2e 2> "$OUT/bench_o2m.err" | tee "$OUT/bench_o2m.json.log" | cut -c1-400
 fi
 if has pmc; then
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do

@@ -17,7 +17,7 @@ d = json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith
 k = d.get('roofline', {}).get('all_kernels_ms_per_step', {})
 print('$1', d.get('value'), d.get('ms_per_step'), d.get('stage_ms_per_step_rank0'), {x: k[x] for x in ('ani::k_l2_sim', 'ani::k_l2_codes', 'ani::k_l1_probe', 'ani::k_l1') if x in k}, 'l2Steps', d.get('counters_per_step_rank0', {}).get('l2Steps'), 'rows_ok', d.get('rows_identical_across_steps'))
 "; }
-QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify"
+QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify --full"
 
 if has disk; then
   { echo "== disk"; df -h "$REPO" /tmp /dev/shm 2>&1; nproc; free -g | head -2
@@ -42,7 +42,7 @@ if has bench3; then
   for i in 1 2 3; do
     echo "== bench run $i"
     extra=""; [ $i -gt 1 ] && extra="--no-e2e"          # (the command-line leg once)
-    timeout 900 python bench.py --workdir /tmp/ani_bench_wd $extra 2> "$OUT/bench$i.err" > "$OUT/bench$i.json.log"
+    timeout 900 python bench.py --full --workdir "$TMPDIR/ani_bench_wd" $extra 2> "$OUT/bench$i.err" > "$OUT/bench$i.json.log"
     python - "$OUT/bench$i.json.log" <<'EOF' | tee -a "$OUT/bench3_summary.txt"
 import sys, json
 d = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith('{')][-1])
@@ -114,12 +114,12 @@ EOF3
 fi
 if has c4sim8; then
   echo "== configs[3] in its multi-rank form: rank 0 of 8 at 10 000 x 10 000 (1250-genome shard, own set + merged 8750-genome foreign set)"
-  timeout 1500 python bench.py --config c4 --simulate-world 8 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4sim8.err" | tee "$OUT/c4sim8.json.log" | cut -c1-1500
+  timeout 1500 python bench.py --full --config c4 --simulate-world 8 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4sim8.err" | tee "$OUT/c4sim8.json.log" | cut -c1-1500
   tail -3 "$OUT/c4sim8.err"
 fi
 if has c4one; then
   echo "== configs[3] on one GPU, warm (for the ratio)"
-  timeout 1500 python bench.py --config c4 --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4one.err" | tee "$OUT/c4one.json.log" | cut -c1-1500
+  timeout 1500 python bench.py --full --config c4 --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4one.err" | tee "$OUT/c4one.json.log" | cut -c1-1500
   tail -3 "$OUT/c4one.err"
 fi
 if has sim8; then
@@ -134,7 +134,7 @@ if has sim8; then
 fi
 if has c5warm; then
   echo "== configs[4] reference side, warm: 90 000 x 5 Mbp references x 1000 queries, --steps 2 --warmup 1"
-  ANI_POOL_TRACE=1 timeout 1500 python bench.py --config c5 --genomes 90000 --queries 1000 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c5warm.err" | tee "$OUT/c5warm.json.log" | cut -c1-1500
+  ANI_POOL_TRACE=1 timeout 1500 python bench.py --full --config c5 --genomes 90000 --queries 1000 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c5warm.err" | tee "$OUT/c5warm.json.log" | cut -c1-1500
   grep -c "hipMalloc" "$OUT/c5warm.err"; grep "hipMalloc" "$OUT/c5warm.err" | awk '{mb+=$4; ms+=$6} END {print "fresh device memory:", mb/1024, "GB,", ms/1000, "s inside hipMalloc"}' | tee "$OUT/c5warm_pool.txt"
   grep -n "timed step" "$OUT/c5warm.err" | head; grep "hipMalloc" "$OUT/c5warm.err" | sort -k6 -n -r | head -12 >> "$OUT/c5warm_pool.txt"
   gzip -f "$OUT/c5warm.err"
@@ -144,11 +144,11 @@ if has c5big; then
   # The queries' fragment sketches stay resident (1.6 GB per 1000 genomes), the references stream block by block, chunk by chunk.
   if [ -z "${C5_SKIP_SMALL:-}" ]; then
   echo "== configs[4]: 90 000 references x 1000 queries (the known-safe size, new query-set path), one cold step"
-  timeout 600 python bench.py --config c5 --genomes 90000 --queries 1000 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 20 2> "$OUT/c5_1000.err" | tee "$OUT/c5_1000.json.log" | cut -c1-1200
+  timeout 600 python bench.py --full --config c5 --genomes 90000 --queries 1000 --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 20 2> "$OUT/c5_1000.err" | tee "$OUT/c5_1000.json.log" | cut -c1-1200
   tail -2 "$OUT/c5_1000.err"; free -g | head -2
   fi
   echo "== configs[4]: 90 000 references x ${C5_QUERIES:-10000} queries, one cold step"
-  timeout 900 python bench.py --config c5 --genomes 90000 --queries ${C5_QUERIES:-10000} --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 20 2> "$OUT/c5_big.err" | tee "$OUT/c5_big.json.log" | cut -c1-1500
+  timeout 900 python bench.py --full --config c5 --genomes 90000 --queries ${C5_QUERIES:-10000} --steps 1 --warmup 0 --no-cpu-baseline --no-e2e --oracle-pairs 20 2> "$OUT/c5_big.err" | tee "$OUT/c5_big.json.log" | cut -c1-1500
   tail -3 "$OUT/c5_big.err"; free -g | head -2
 fi
 if has ubench; then

@@ -17,7 +17,7 @@ d = json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith
 k = d.get('roofline', {}).get('all_kernels_ms_per_step', {})
 print('$1', d.get('value'), d.get('ms_per_step'), d.get('stage_ms_per_step_rank0'), {x: k[x] for x in ('ani::k_l2_sim', 'ani::k_l2_codes', 'ani::k_l1_probe', 'ani::k_l1<0,2048>') if x in k}, 'rows_ok', d.get('rows_identical_across_steps'))
 "; }
-QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify"
+QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify --full"
 if has alloc; then
   { echo "== fresh device memory on this box"; timeout 300 tools/ubench/alloc; } 2>&1 | tee "$OUT/ubench_alloc.txt"
 fi
@@ -57,7 +57,7 @@ if has bench3; then
   for i in 1 2 3; do
     echo "== bench run $i"
     extra=""; [ $i -gt 1 ] && extra="--no-e2e"
-    timeout 900 python bench.py --workdir /tmp/ani_bench_wd $extra 2> "$OUT/bench$i.err" > "$OUT/bench$i.json.log"
+    timeout 900 python bench.py --full --workdir "$TMPDIR/ani_bench_wd" $extra 2> "$OUT/bench$i.err" > "$OUT/bench$i.json.log"
     python - "$OUT/bench$i.json.log" <<'PYEOF' | tee -a "$OUT/bench3_summary.txt"
 import sys, json
 d = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith('{')][-1])
@@ -69,18 +69,18 @@ PYEOF
 fi
 if has c4one; then
   echo "== configs[3] on one GPU, warm"
-  ANI_POOL_TRACE=1 timeout 1500 python bench.py --config c4 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4one.err" | tee "$OUT/c4one.json.log" | cut -c1-1500
+  ANI_POOL_TRACE=1 timeout 1500 python bench.py --full --config c4 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4one.err" | tee "$OUT/c4one.json.log" | cut -c1-1500
   grep "hipMalloc\|reserved" "$OUT/c4one.err" | awk '{mb+=$4; ms+=$6} END {print "c4 fresh device memory:", mb/1024, "GB,", ms/1000, "s inside hipMalloc"}' | tee "$OUT/c4one_pool.txt"
   grep -n "timed step" "$OUT/c4one.err" | head -3; grep -v "ani pool" "$OUT/c4one.err" | tail -3; gzip -f "$OUT/c4one.err"
 fi
 if has c4sim8; then
   echo "== configs[3]: rank 0 of 8 at 10 000 x 10 000"
-  timeout 1500 python bench.py --config c4 --simulate-world 8 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4sim8.err" | tee "$OUT/c4sim8.json.log" | cut -c1-1500
+  timeout 1500 python bench.py --full --config c4 --simulate-world 8 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c4sim8.err" | tee "$OUT/c4sim8.json.log" | cut -c1-1500
   tail -3 "$OUT/c4sim8.err"
 fi
 if has c5warm; then
   echo "== configs[4] reference side, warm: 90 000 x 5 Mbp references x 1000 queries, --steps 2 --warmup 1"
-  ANI_POOL_TRACE=1 timeout 1500 python bench.py --config c5 --genomes 90000 --queries 1000 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c5warm.err" | tee "$OUT/c5warm.json.log" | cut -c1-1500
+  ANI_POOL_TRACE=1 timeout 1500 python bench.py --full --config c5 --genomes 90000 --queries 1000 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --oracle-pairs 60 2> "$OUT/c5warm.err" | tee "$OUT/c5warm.json.log" | cut -c1-1500
   grep "hipMalloc\|reserved" "$OUT/c5warm.err" | awk '{mb+=$4; ms+=$6} END {print "c5 fresh device memory:", mb/1024, "GB,", ms/1000, "s inside hipMalloc"}' | tee "$OUT/c5warm_pool.txt"
   grep -n "timed step" "$OUT/c5warm.err" | head -3; grep -v "ani pool" "$OUT/c5warm.err" | tail -3; gzip -f "$OUT/c5warm.err"
 fi
@@ -97,7 +97,7 @@ if has c5full; then
   # configs[4] as stated: all-vs-all over 90 000 x 5 Mbp genomes = 8.1 x 10^9 pairs on ONE GPU — queries generated inside the step and taken in
   # blocks of 30 000 (48 GB of fragment sets), the references streamed block by block once per query block; rows counted + checksummed, 24 queries kept
   echo "== configs[4]: ${C5_GENOMES:-90000} x ${C5_QUERIES:-90000}, one cold step"
-  timeout 2400 python bench.py --config c5 --genomes ${C5_GENOMES:-90000} --queries ${C5_QUERIES:-90000} --query-block ${C5_QBLOCK:-30000} --drop-rows --steps 1 --warmup 0 \
+  timeout 2400 python bench.py --full --config c5 --genomes ${C5_GENOMES:-90000} --queries ${C5_QUERIES:-90000} --query-block ${C5_QBLOCK:-30000} --drop-rows --steps 1 --warmup 0 \
       --no-cpu-baseline --no-e2e --oracle-pairs 48 2> "$OUT/c5full.err" | tee "$OUT/c5full.json.log" | cut -c1-1800
   tail -3 "$OUT/c5full.err"; free -g | head -2
 fi

@@ -10,7 +10,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 has() { [[ " $STAGES " == *" $1 "* ]]; }
-QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify"
+QUICK="--steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-verify --full"
 ms() { python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')][-1])
@@ -40,7 +40,7 @@ fi
 if has bench1; then
   echo "== the default line"
   mkdir -p /tmp/ani_bench_wd
-  timeout 900 python bench.py --workdir /tmp/ani_bench_wd 2> "$OUT/bench.err" > "$OUT/bench.json.log"
+  timeout 900 python bench.py --full --workdir "$TMPDIR/ani_bench_wd" 2> "$OUT/bench.err" > "$OUT/bench.json.log"
   ms bench < "$OUT/bench.json.log"; tail -3 "$OUT/bench.err"
   rm -rf /tmp/ani_bench_wd
 fi
