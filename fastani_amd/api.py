@@ -4,6 +4,7 @@
     Sketch.map_query(genome)               ≙ skch::Map::Map + callback     (src/map/include/computeMap.hpp:93)
     Sketch.compute_cgi(maps, total, qid)   ≙ cgi::computeCGI               (src/cgi/include/computeCoreIdentity.hpp:166)
     Sketch.map_cgi_batch(genomes, first)   ≙ the query loop of src/cgi/core_genome_identity.cpp:81-106
+    Engine.cluster_greedy(rows, n, t)      greedy species clustering of the rows at an ANI threshold (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -114,6 +115,7 @@ def _bind(lib):
         "ani_map_cgi_batch": (C.c_int, [vp, vp, C.POINTER(SeqBatch), C.c_int32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+        "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -367,6 +369,18 @@ class Engine:
 
     def device_copy(self, dst, src, nbytes):
         self._chk(self.lib.ani_device_copy(self.h, dst, src, nbytes))
+
+    def cluster_greedy(self, rows, n_genomes, min_identity):
+        """greedy clustering of the pair graph w(i, j) >= min_identity (ani_cluster_greedy): `rows` a CGI_DT array whose qryGenomeId /
+        refGenomeId are ids in one numbering [0, n_genomes); the rows of a pair are folded in the order given, self rows ignored.
+        -> (representative int32[n_genomes], identity float32[n_genomes]); a representative is its own, with identity 0."""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        n_genomes = int(n_genomes)
+        rep = np.empty(max(n_genomes, 0), dtype=np.int32)
+        ident = np.empty(max(n_genomes, 0), dtype=np.float32)
+        self._chk(self.lib.ani_cluster_greedy(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(min_identity),
+                                              rep.ctypes.data if n_genomes > 0 else None, ident.ctypes.data if n_genomes > 0 else None))
+        return rep, ident
 
 
 class FragmentSet:

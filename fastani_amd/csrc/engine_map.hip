@@ -1,12 +1,14 @@
 // engine_map.hip — mapping and reduction: L1 seed lookup + candidate regions, L2 sliding MinHash, identity filter
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
-// src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets.
+// src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
+// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
 #include "kernels/l1.hpp"
 #include "kernels/l2.hpp"
 #include "kernels/reduce.hpp"
+#include "kernels/cluster.hpp"
 
 namespace anih {
 using namespace ani;
@@ -579,6 +581,107 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   }
   return ANI_OK;
 }
+// ---- greedy clustering of the pair graph (ani_cluster_greedy) ----
+// Device memory per row: 20 (rows) + 2 x 12 (keys and positions) + 12 (the sort's ping-pong) bytes at the peak, the 12-byte edge list
+// after the sort's inputs are gone; per edge end 8 (CSR); per genome 40.  Every buffer is the pool's and goes back to it on return.
+int cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float minIdentity, int32_t *representative, float *identityToRep)
+{
+  for (int32_t i = 0; i < nG; i++) { representative[i] = i; identityToRep[i] = 0.0f; }
+  if (n == 0) return ANI_OK;
+  // every buffer goes back to the pool on return (the launches below take plain pointers, never the holder)
+  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, E_LO, E_HI, E_W, LOW, HIGH, DEG, FILL, OFF, NBR, NBR_W, STATE, REP, REP_W, FLAGS, SORT, NBUF };
+  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
+  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
+  hipStream_t st = ctx->stream;
+  int b = 1;
+  while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
+  const size_t V = (size_t)nG;
+  ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB, *flags, *off, *state; int32_t *lowDeg, *highDeg, *deg, *fill, *rep; float *repW;
+  TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
+  TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB)); TRY(buf(FLAGS, 64, (void **)&flags));
+  TRY(buf(LOW, V * 4, (void **)&lowDeg)); TRY(buf(HIGH, V * 4, (void **)&highDeg)); TRY(buf(DEG, V * 4, (void **)&deg));
+  TRY(buf(FILL, V * 8, (void **)&fill)); TRY(buf(OFF, V * 4 + 4, (void **)&off)); TRY(buf(STATE, V * 4, (void **)&state));
+  TRY(buf(REP, V * 4, (void **)&rep)); TRY(buf(REP_W, V * 4, (void **)&repW));
+  // flags: [0] a bad id, [1] the edge count, [2..3] the undecided counters of the rounds
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+
+  // one upload; keys; the stable sort puts the rows of a pair next to each other in the order given
+  HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
+  HIP_TRY(hipMemsetAsync(lowDeg, 0, V * 4, st)); HIP_TRY(hipMemsetAsync(highDeg, 0, V * 4, st));
+  hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0]) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
+  size_t tb = 0;
+  int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
+  void *sortTmp = nullptr;
+  if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
+  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
+  B.b[SORT].release(); B.b[KEYS_A].release(); B.b[VALS_A].release();
+
+  // fold + threshold -> edge list (at most one edge per sorted row) and the degrees
+  int32_t *eLo, *eHi; float *eW;
+  TRY(buf(E_LO, n * 4, (void **)&eLo)); TRY(buf(E_HI, n * 4, (void **)&eHi)); TRY(buf(E_W, n * 4, (void **)&eW));
+  hipLaunchKernelGGL(k_cluster_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                     (uint64_t)n, b, minIdentity, flags + 1, eLo, eHi, eW, lowDeg, highDeg);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, flags + 1, 4, hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(k_cluster_degrees, dim3(grid_for(V)), dim3(256), 0, st, nG, (const int32_t *)lowDeg, (const int32_t *)highDeg, deg, fill);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t nE = host[0];
+  if (nE == 0) return ANI_OK;                          // no edge: every genome is its own representative
+  B.b[ROWS].release(); B.b[KEYS_B].release(); B.b[VALS_B].release();
+
+  // CSR over both directions: offsets = prefix sum of the degrees (device_scan: ANI_ERR_LIMIT beyond 2^32 - 16 entries)
+  uint64_t total = 0;
+  TRY(device_scan(ctx, deg, off, (uint32_t)V, &total));
+  const uint32_t tot32 = (uint32_t)total;
+  HIP_TRY(hipMemcpyAsync(off + V, &tot32, 4, hipMemcpyHostToDevice, st));
+  int32_t *nbr; float *nbrW;
+  TRY(buf(NBR, (size_t)total * 4, (void **)&nbr)); TRY(buf(NBR_W, (size_t)total * 4, (void **)&nbrW));
+  hipLaunchKernelGGL(k_cluster_scatter, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)eLo, (const int32_t *)eHi, (const float *)eW,
+                     (const uint32_t *)off, (const int32_t *)lowDeg, fill, nbr, nbrW);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(state, 0, V * 4, st));
+
+  // greedy rounds: batches of kRounds launches; the last launch of a batch counts the undecided vertices, the count is copied back
+  // asynchronously and read while the next batch runs (a batch after the last one with work only finds decided vertices)
+  constexpr int kRounds = 8;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+  if (hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(ANI_ERR_DEVICE, "hipEventCreate failed"); }
+  struct EvGuard { hipEvent_t *e; ~EvGuard() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } evGuard{ev};
+  const unsigned grid = grid_for(V, kTPB);
+  // every launch decides at least the lowest undecided vertex (its lower neighbours were all decided before the launch started)
+  const uint64_t maxBatches = V / kRounds + 3;
+  bool done = false;
+  for (uint64_t batch = 0; !done; batch++) {
+    if (batch > maxBatches) return fail(ANI_ERR_INTERNAL, "greedy rounds did not converge after %llu launches", (unsigned long long)(batch * kRounds));
+    const int slot = (int)(batch & 1);
+    uint32_t *und = flags + 2 + slot;
+    HIP_TRY(hipMemsetAsync(und, 0, 4, st));
+    for (int r = 0; r < kRounds; r++) {
+      uint32_t *count = r == kRounds - 1 ? und : nullptr;
+      hipLaunchKernelGGL(k_cluster_round, dim3(grid), dim3(kTPB), 0, st, nG, (const uint32_t *)off, (const int32_t *)lowDeg, (const int32_t *)nbr, state, count);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host + 2 + slot, und, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev[slot], st));
+    if (batch > 0) { HIP_TRY(hipEventSynchronize(ev[slot ^ 1])); done = host[2 + (slot ^ 1)] == 0; }
+  }
+  hipLaunchKernelGGL(k_cluster_assign, dim3(grid), dim3(kTPB), 0, st, nG, (const uint32_t *)off, (const int32_t *)nbr, (const float *)nbrW,
+                     (const uint32_t *)state, rep, repW);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(representative, rep, V * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(identityToRep, repW, V * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -780,5 +883,15 @@ int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *skc, const ani_seq_batch_t
   return ANI_OK;
 }
 
+
+int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float minIdentity, int32_t *representative, float *identityToRep)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 0 && (!representative || !identityToRep))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (!(minIdentity > 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside (0, 100]", (double)minIdentity);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  HIP_TRY(hipSetDevice(ctx->device));
+  return cluster_greedy(ctx, rows, n, nGenomes, minIdentity, representative, identityToRep);
+}
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // Mirrors the reference driver core_genome_identity() (src/cgi/core_genome_identity.cpp:27-167): same flags and
 // defaults (src/map/include/parseCmdArgs.hpp:114-234), same output files and formats (cgi::outputCGI
 // src/cgi/include/computeCoreIdentity.hpp:307-344, cgi::outputPhylip :353-448, cgi::outputVisualizationFile :103-153,
-// cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  Sketch / Map / computeCGI run on the GPU(s)
+// cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
+// (greedy species clusters over the .matrix cells, ani_cluster_greedy).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -59,6 +60,7 @@ struct Options {
   int kmerSize = 16, fragLen = 3000, threads = 1;
   float minFraction = 0.2f, maxRatioDiff = 100.0f;     // parseCmdArgs.hpp:121,:128 (the help text says 10.0; the code sets 100.0)
   bool visualize = false, matrix = false, sanityCheck = false;
+  float cluster = 0.0f;                                // --cluster T: greedy clustering at w >= T (0 = off)
   std::vector<std::string> refs, queries;
   std::vector<int> devices{0};
   std::string out, saveSketch, refSketch;
@@ -73,7 +75,7 @@ struct Options {
     "Example usage:\n$ fastANI -q genome1.fa -r genome2.fa -o output.txt\n$ fastANI -q genome1.fa --rl genome_list.txt -o output.txt\n\n"
     "SYNOPSIS\n"
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
-    "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix]\n"
+    "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -88,6 +90,8 @@ struct Options {
     "     --maxRatioDiff <value>  maximum difference between (Total Ref. Length/Total Occ. Hashes) and (Total Ref. Length/Total No. Hashes). [default : 10.0]\n"
     "     --visualize  output mappings for visualization [disabled by default] (small-input mode: whole sets in host memory, one GPU)\n"
     "     --matrix    also output ANI values as lower triangular matrix (.matrix) [disabled by default]\n"
+    "     --cluster <value>  also output greedy species clusters at this ANI threshold (0 < value <= 100), in input order (.clusters:\n"
+    "                 genome, representative, ANI to it or NA for a representative) [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -138,6 +142,8 @@ Options parse(int argc, char **argv)
     else if (a == "--maxRatioDiff") o.maxRatioDiff = (float)atof(need(i));
     else if (a == "--visualize") o.visualize = true;
     else if (a == "--matrix") o.matrix = true;
+    else if (a == "--cluster") { o.cluster = (float)atof(need(i));
+      if (!(o.cluster > 0.0f && o.cluster <= 100.0f)) { std::cerr << "ERROR, --cluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -408,6 +414,7 @@ void trace(const char *what) { static const bool on = getenv("ANI_CLI_TRACE") !=
 void die(const char *what) { std::cerr << "ERROR, " << what << ": " << ani_last_error() << std::endl; exit(1); }
 
 struct VisRow { std::string q, r; float id; int64_t qs, qe, rs, re; };
+struct Cell { int32_t row, col; float id; };         // a .matrix cell: row > col (the .matrix numbering)
 
 // files -> slices of about `sliceBytes` (by file size)
 std::vector<std::pair<size_t, size_t>> make_slices(const FilePipeline &fp, size_t a, size_t b, uint64_t sliceBytes)
@@ -1090,20 +1097,18 @@ int main(int argc, char **argv)
       if (trusted(e))
         out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << e.identity << "\t" << e.countSeq << "\t" << e.totalQueryFragments << "\n";
   }
-  // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
-  // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
-  // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
-  // row by row.  Memory is O(results).
-  if (o.matrix) {
-    std::unordered_map<std::string, int> g2i; std::vector<std::string> names;
+  // The cells of the .matrix, shared by the .clusters writer so that the two files never disagree: genomes numbered queries first, then
+  // references not seen yet (first occurrence wins, :353-380); every trusted row that is not a self row becomes a (row > column, identity)
+  // cell, in result order.
+  std::vector<std::string> names;
+  std::vector<Cell> cells;
+  if (o.matrix || o.cluster > 0.0f) {
+    std::unordered_map<std::string, int> g2i;
     for (auto &e : o.queries) if (!g2i.count(e)) { g2i[e] = (int)names.size(); names.push_back(e); }
     for (auto &e : o.refs) if (!g2i.count(e)) { g2i[e] = (int)names.size(); names.push_back(e); }
     std::vector<int> qIdx((size_t)nQry), rIdx((size_t)nRef);
     for (int i = 0; i < nQry; i++) qIdx[i] = g2i[o.queries[i]];
     for (int i = 0; i < nRef; i++) rIdx[i] = g2i[o.refs[i]];
-    const int n = (int)names.size();
-    struct Cell { int32_t row, col; float id; };
-    std::vector<Cell> cells;
     for (auto &e : finalResults)
       if (trusted(e)) {
         int a = qIdx[e.qryGenomeId], b = rIdx[e.refGenomeId];
@@ -1111,6 +1116,32 @@ int main(int argc, char **argv)
         if (a < b) std::swap(a, b);
         cells.push_back(Cell{a, b, e.identity});
       }
+  }
+  // ---- .clusters: greedy clustering at --cluster T over the cells (ani_cluster_greedy on the first device: the cells of a pair are folded in
+  // result order as the .matrix writer folds them), one line per genome in .matrix order: genome, representative, w or NA
+  if (o.cluster > 0.0f) {
+    const int n = (int)names.size();
+    std::vector<ani_cgi_t> rows(cells.size());
+    for (size_t i = 0; i < cells.size(); i++) rows[i] = ani_cgi_t{cells[i].col, cells[i].row, 0, 0, cells[i].id};
+    std::vector<int32_t> rep((size_t)n); std::vector<float> repId((size_t)n);
+    if (ani_cluster_greedy(dev[0].ctx, rows.data(), rows.size(), n, o.cluster, rep.data(), repId.data())) die("ani_cluster_greedy");
+    std::vector<ani_cgi_t>().swap(rows);
+    std::ofstream out(o.out + ".clusters");
+    std::vector<char> obuf(1 << 20); out.rdbuf()->pubsetbuf(obuf.data(), (std::streamsize)obuf.size());
+    for (int i = 0; i < n; i++) {
+      out << names[i] << "\t" << names[rep[i]] << "\t";
+      if (rep[i] == i) out << "NA\n"; else out << std::to_string(repId[i]) << "\n";
+    }
+    out.close();
+    if (out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".clusters" << std::endl; exit(1); }
+    trace("clusters written");
+  }
+  // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
+  // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
+  // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
+  // row by row.  Memory is O(results).
+  if (o.matrix) {
+    const int n = (int)names.size();
     std::stable_sort(cells.begin(), cells.end(), [](const Cell &x, const Cell &y) { return x.row != y.row ? x.row < y.row : x.col < y.col; });
     std::ofstream out(o.out + ".matrix");
     std::vector<char> obuf(1 << 20); out.rdbuf()->pubsetbuf(obuf.data(), (std::streamsize)obuf.size());

@@ -306,6 +306,17 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *sk, const ani_mapping_t *map
 int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *sk, const ani_seq_batch_t *queries, int32_t firstQueryId,
                       ani_cgi_t **out, size_t *m);
 
+/* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
+ * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
+ * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
+ * self rows are ignored.  {i, j} is an edge iff w(i, j) >= minIdentity.  Genomes are taken in id order: i is a representative iff no
+ * representative j < i has an edge to i; a member goes to the adjacent representative with the largest w, the smallest id on a tie.
+ * representative[i] = i for representatives; identityToRep[i] = w(i, representative[i]), 0 for representatives.
+ * ANI_ERR_ARG: an id outside [0, nGenomes) or minIdentity outside (0, 100]; ANI_ERR_LIMIT: n > 2^32 - 16 rows, or more than 2^32 - 16
+ * edge ends (twice the pairs at or above minIdentity).  n = 0: every genome is its own representative. */
+int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float minIdentity,
+                       int32_t *representative, float *identityToRep);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */
