@@ -5,6 +5,7 @@
     Sketch.compute_cgi(maps, total, qid)   ≙ cgi::computeCGI               (src/cgi/include/computeCoreIdentity.hpp:166)
     Sketch.map_cgi_batch(genomes, first)   ≙ the query loop of src/cgi/core_genome_identity.cpp:81-106
     Engine.cluster_greedy(rows, n, t)      greedy species clustering of the rows at an ANI threshold (no reference counterpart)
+    Engine.tree_average(rows, n)           average-linkage (UPGMA) tree of the genomes, scipy linkage form (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -116,6 +117,7 @@ def _bind(lib):
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
+        "ani_tree_average": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -381,6 +383,26 @@ class Engine:
         self._chk(self.lib.ani_cluster_greedy(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(min_identity),
                                               rep.ctypes.data if n_genomes > 0 else None, ident.ctypes.data if n_genomes > 0 else None))
         return rep, ident
+
+    def tree_average(self, rows, n_genomes, missing_identity=0.0):
+        """average-linkage (UPGMA) tree of the genomes over the pair distances 1 - w / 100 (ani_tree_average): `rows` as for
+        cluster_greedy, a pair without rows at 1 - missing_identity / 100.  -> scipy linkage matrix, float64 (n_genomes - 1, 4): child,
+        child (smaller id first), height, leaf count; (0, 4) for n_genomes <= 1."""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        n_genomes = int(n_genomes)
+        m = max(n_genomes - 1, 0)
+        children = np.empty(2 * m, dtype=np.int32)
+        height = np.empty(m, dtype=np.float32)
+        self._chk(self.lib.ani_tree_average(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
+                                            children.ctypes.data if m else None, height.ctypes.data if m else None))
+        z = np.empty((m, 4), dtype=np.float64)
+        z[:, 0:2] = children.reshape(m, 2)
+        z[:, 2] = height
+        count = np.ones(n_genomes + m, dtype=np.int64)
+        for s, (x, y) in enumerate(children.reshape(m, 2).tolist()):
+            count[n_genomes + s] = count[x] + count[y]
+        z[:, 3] = count[n_genomes:]
+        return z
 
 
 class FragmentSet:

@@ -1,7 +1,8 @@
 // engine_map.hip — mapping and reduction: L1 seed lookup + candidate regions, L2 sliding MinHash, identity filter
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
 // src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
-// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp).
+// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their average-linkage tree (ani_tree_average,
+// kernels/tree.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -9,6 +10,7 @@
 #include "kernels/l2.hpp"
 #include "kernels/reduce.hpp"
 #include "kernels/cluster.hpp"
+#include "kernels/tree.hpp"
 
 namespace anih {
 using namespace ani;
@@ -682,6 +684,74 @@ int cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, fl
   return ANI_OK;
 }
 
+// ---- average-linkage (UPGMA) tree of the pair values (ani_tree_average) ----
+// Device memory: 4 bytes per matrix cell (n x ld, ld = n rounded up to 64) plus 40 per genome; per row 20 + 2 x 12 + 12 bytes while the
+// pairs are folded, all of it released before the merges.  The merges are a plain enqueue loop, one k_tree_merge per merge, each
+// reading its pair from device memory; the result is copied back once at the end.  Every buffer is the pool's and goes back on return.
+int tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height)
+{
+  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, DMAT, ROWMIN, STATE, PART, OUT, NBUF };
+  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
+  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG, M = V - 1;
+  const uint64_t ld = ((uint64_t)nG + 63) & ~63ull;
+  const unsigned G = grid_for(V, kTreeRows);
+  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
+  TreeArgs t;
+  uint32_t *flags, *state;
+  TRY(buf(DMAT, (size_t)ld * V * 4, (void **)&t.D));
+  TRY(buf(FLAGS, 64, (void **)&flags)); TRY(buf(ROWMIN, V * 8, (void **)&t.rowMin)); TRY(buf(STATE, V * 12 + 16, (void **)&state));
+  TRY(buf(PART, (size_t)G * 16, (void **)&t.part)); TRY(buf(OUT, M * 12, (void **)&t.children));
+  t.ld = ld; t.n = nG;
+  t.size = (int32_t *)state; t.id = (int32_t *)state + V; t.active = state + 2 * V; t.pick = (int32_t *)state + 3 * V;
+  t.arrived = flags + 1; t.height = (float *)(t.children + 2 * M);
+  // flags: [0] a bad id (1) or identity (2), [1] the arrival counter of k_tree_merge
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
+  hipLaunchKernelGGL(k_tree_fill, dim3(nG), dim3(kTPB), 0, st, t.D, ld, nG, dMissing);
+  HIP_TRY(hipGetLastError());
+
+  if (n) {
+    // the pair values: keys and the stable sort as for the clustering, then one fold per pair into D
+    int b = 1;
+    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
+    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
+    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
+    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
+    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
+    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
+    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
+    size_t tb = 0;
+    int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
+    void *sortTmp = nullptr;
+    if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
+    if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
+    hipLaunchKernelGGL(k_tree_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                       (uint64_t)n, b, t.D, ld);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i : {ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, SORT}) B.b[i].release();
+  }
+
+  // row minima, the first pick, then one launch per merge (the last one picks nothing)
+  hipLaunchKernelGGL(k_tree_rowmin, dim3(nG), dim3(kTPB), 0, st, t);
+  hipLaunchKernelGGL(k_tree_first, dim3(1), dim3(kTPB), 0, st, t);
+  HIP_TRY(hipGetLastError());
+  for (int32_t s = 0; s + 1 < nG; s++) hipLaunchKernelGGL(k_tree_merge, dim3(G), dim3(kTPB), 0, st, t, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(children, t.children, M * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(height, t.height, M * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -892,6 +962,18 @@ int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG
   if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
   HIP_TRY(hipSetDevice(ctx->device));
   return cluster_greedy(ctx, rows, n, nGenomes, minIdentity, representative, identityToRep);
+}
+
+int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *height)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
+  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the tree takes at most 65536", nGenomes);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  if (nGenomes <= 1) return ANI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return tree_average(ctx, rows, n, nGenomes, missingIdentity, children, height);
 }
 
 }  // extern "C"

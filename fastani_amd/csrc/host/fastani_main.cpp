@@ -4,7 +4,8 @@
 // defaults (src/map/include/parseCmdArgs.hpp:114-234), same output files and formats (cgi::outputCGI
 // src/cgi/include/computeCoreIdentity.hpp:307-344, cgi::outputPhylip :353-448, cgi::outputVisualizationFile :103-153,
 // cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
-// (greedy species clusters over the .matrix cells, ani_cluster_greedy).  Sketch / Map / computeCGI run on the GPU(s)
+// (greedy species clusters over the .matrix cells, ani_cluster_greedy), `--tree` (extension) a .newick file (their average-linkage
+// tree, ani_tree_average).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -62,6 +63,7 @@ struct Options {
   float minFraction = 0.2f, maxRatioDiff = 100.0f;     // parseCmdArgs.hpp:121,:128 (the help text says 10.0; the code sets 100.0)
   bool visualize = false, matrix = false, sanityCheck = false;
   float cluster = 0.0f;                                // --cluster T: greedy clustering at w >= T (0 = off)
+  bool tree = false;                                   // --tree: average-linkage tree of the .matrix cells
   std::vector<std::string> refs, queries;
   std::vector<int> devices{0};
   std::string out, saveSketch, refSketch;
@@ -77,7 +79,7 @@ struct Options {
     "SYNOPSIS\n"
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
-    "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--tree] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -93,6 +95,8 @@ struct Options {
     "     --matrix    also output ANI values as lower triangular matrix (.matrix) [disabled by default]\n"
     "     --cluster <value>  also output greedy species clusters at this ANI threshold (0 < value <= 100), in input order (.clusters:\n"
     "                 genome, representative, ANI to it or NA for a representative) [disabled by default]\n"
+    "     --tree      also output the average-linkage (UPGMA) tree of the genomes over the distances 1 - ANI/100, a pair without\n"
+    "                 ANI at distance 1 (.newick) [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -145,6 +149,7 @@ Options parse(int argc, char **argv)
     else if (a == "--matrix") o.matrix = true;
     else if (a == "--cluster") { o.cluster = (float)atof(need(i));
       if (!(o.cluster > 0.0f && o.cluster <= 100.0f)) { std::cerr << "ERROR, --cluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
+    else if (a == "--tree") o.tree = true;
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -1181,6 +1186,51 @@ void write_clusters(const std::string &path, ani_ctx *ctx, float threshold, cons
   trace("clusters written");
 }
 
+// ---- .newick: the average-linkage tree of the cells (ani_tree_average on the first device, a pair without cells at identity 0), leaves
+// named as in the .matrix.  A node's depth below its leaves is half its merge distance, so a branch is half the difference of the two
+// merge heights (0 for a leaf).  Written with an explicit stack: a caterpillar tree of 65 536 leaves is as deep as it is wide.
+void write_newick_name(std::ostream &out, const std::string &name)
+{
+  bool quote = name.empty();
+  for (unsigned char c : name) quote |= std::isspace(c) || strchr("()[]':;,", c) != nullptr;
+  if (!quote) { out << name; return; }
+  out << '\'';
+  for (char c : name) { if (c == '\'') out << '\''; out << c; }
+  out << '\'';
+}
+
+void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
+{
+  const int n = (int)mc.names.size();
+  std::vector<ani_cgi_t> rows(mc.cells.size());
+  for (size_t i = 0; i < mc.cells.size(); i++) rows[i] = ani_cgi_t{mc.cells[i].col, mc.cells[i].row, 0, 0, mc.cells[i].id};
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
+  std::vector<int32_t> children(2 * m); std::vector<float> height(m);
+  if (ani_tree_average(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data())) die("ani_tree_average");
+  std::vector<ani_cgi_t>().swap(rows);
+  BufferedFile f(path);
+  auto h = [&](int node) { return node < n ? 0.0 : (double)height[(size_t)(node - n)]; };
+  char len[64];
+  struct Frame { int node, phase; };
+  std::vector<Frame> stack;
+  if (n > 0) stack.push_back(Frame{n > 1 ? 2 * n - 2 : 0, 0});
+  while (!stack.empty()) {
+    const Frame fr = stack.back();
+    if (fr.node < n) { write_newick_name(f.out, mc.names[(size_t)fr.node]); stack.pop_back(); continue; }
+    const size_t s = (size_t)(fr.node - n);
+    const int child = fr.phase == 0 ? -1 : children[2 * s + (size_t)fr.phase - 1];
+    if (fr.phase > 0) { snprintf(len, sizeof len, "%.9g", (h(fr.node) - h(child)) / 2); f.out << ':' << len; }
+    if (fr.phase == 2) { f.out << ')'; stack.pop_back(); continue; }
+    f.out << (fr.phase == 0 ? '(' : ',');
+    stack.back().phase++;
+    stack.push_back(Frame{children[2 * s + (size_t)fr.phase], 0});
+  }
+  f.out << ";\n";
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
+  trace("tree written");
+}
+
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
 // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
 // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
@@ -1288,8 +1338,9 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   MatrixCells mc;
-  if (o.matrix || o.cluster > 0.0f) mc = matrix_cells(o, res.rows, trusted);
+  if (o.matrix || o.cluster > 0.0f || o.tree) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
+  if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc);        // before write_matrix, which sorts the cells in place
   if (o.matrix) write_matrix(o.out + ".matrix", mc);
   write_visual(o, res);
   std::cerr << "INFO, skch::main, Time spent writing the output : " << secs_since(tOut) << " sec; total : " << secs_since(tStart) << " sec" << std::endl;

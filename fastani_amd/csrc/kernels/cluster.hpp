@@ -58,6 +58,22 @@ static __global__ void k_cluster_keys(const ani_cgi_t *__restrict__ rows, uint64
   vals[i] = (uint32_t)i;
 }
 
+// The pair value at sorted position i (i < n): true at the first position of a key that is not a self pair, with the pair {lo < hi}
+// and its rows folded in their order (the first sets w, every later one w = (w + id) / 2 in float); false everywhere else.  Shared
+// with the tree (tree.hpp), so that the .clusters and .newick files fold a pair as the .matrix cell does.
+__device__ __forceinline__ bool cluster_fold_at(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, const ani_cgi_t *__restrict__ rows,
+                                                uint64_t n, uint64_t i, int b, uint32_t *lo, uint32_t *hi, float *w)
+{
+  const uint64_t key = keys[i];
+  if (i != 0 && keys[i - 1] == key) return false;
+  *lo = (uint32_t)(key >> b); *hi = (uint32_t)(key & ((1ull << b) - 1ull));
+  if (*lo == *hi) return false;                                    // self rows have no pair value
+  float x = rows[vals[i]].identity;
+  for (uint64_t j = i + 1; j < n && keys[j] == key; j++) x = (x + rows[vals[j]].identity) / 2.0f;
+  *w = x;
+  return true;
+}
+
 // one lane per sorted position; the first position of every key folds the key's rows in their order.  Edges {lo < hi, w} go to
 // a compacted list (one cursor bump per wave) and count towards lowDeg[hi] / highDeg[lo].
 static __global__ void k_cluster_fold(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, const ani_cgi_t *__restrict__ rows,
@@ -66,17 +82,7 @@ static __global__ void k_cluster_fold(const uint64_t *__restrict__ keys, const u
 {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool edge = false; uint32_t lo = 0, hi = 0; float w = 0.0f;
-  if (i < n) {
-    const uint64_t key = keys[i];
-    if (i == 0 || keys[i - 1] != key) {
-      lo = (uint32_t)(key >> b); hi = (uint32_t)(key & ((1ull << b) - 1ull));
-      if (lo != hi) {                                              // self rows have no edge
-        w = rows[vals[i]].identity;
-        for (uint64_t j = i + 1; j < n && keys[j] == key; j++) w = (w + rows[vals[j]].identity) / 2.0f;
-        edge = w >= minIdentity;
-      }
-    }
-  }
+  if (i < n && cluster_fold_at(keys, vals, rows, n, i, b, &lo, &hi, &w)) edge = w >= minIdentity;
   const unsigned long long m = __ballot(edge);
   if (!m) return;
   uint32_t base = 0;

@@ -317,6 +317,21 @@ int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *sk, const ani_seq_batch_t 
 int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float minIdentity,
                        int32_t *representative, float *identityToRep);
 
+/* ---- average-linkage (UPGMA) tree of the genomes (no counterpart in the reference).  Rows as for
+ * ani_cluster_greedy: ids in ONE numbering [0, nGenomes), the rows of a pair folded in the order given into w(i, j), self rows ignored.
+ * Leaf distances: d(i, j) = (float)(1 - (double)w / 100) for a pair with rows, (float)(1 - (double)missingIdentity / 100) without.
+ * Clusters live in slots 0..nGenomes-1 (slot i starts as leaf i, size 1).  Merge s = 0..nGenomes-2 takes the active slots a < b with
+ * the smallest d(a, b) (ties: the smallest a, then the smallest b), merges b into slot a, retires b, and sets for every other active
+ * slot k d(a, k) = (float)((na * (double)d(a, k) + nb * (double)d(b, k)) / (double)(na + nb)), na and nb the cluster sizes.
+ * Output in scipy linkage form: merge s creates cluster id nGenomes + s (a leaf's id is its index); children[2s], children[2s + 1]
+ * are the ids of the two merged clusters, the smaller first; height[s] is d(a, b) at the merge (non-decreasing in s).
+ * children holds 2 (nGenomes - 1) values, height nGenomes - 1.  nGenomes <= 1: ANI_OK, nothing is read or written.
+ * ANI_ERR_ARG: a null pointer, nGenomes < 0, an id outside [0, nGenomes), a row identity outside (0, 100] (NaN included), or
+ * missingIdentity outside [0, 100]; ANI_ERR_LIMIT: nGenomes > 65536 or n > 2^32 - 16 rows (checked before any allocation);
+ * ANI_ERR_NOMEM: the device cannot hold the nGenomes^2 float matrix. */
+int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                     int32_t *children, float *height);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */
