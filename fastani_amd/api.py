@@ -6,6 +6,7 @@
     Sketch.map_cgi_batch(genomes, first)   ≙ the query loop of src/cgi/core_genome_identity.cpp:81-106
     Engine.cluster_greedy(rows, n, t)      greedy species clustering of the rows at an ANI threshold (no reference counterpart)
     Engine.tree_average(rows, n)           average-linkage (UPGMA) tree of the genomes, scipy linkage form (no reference counterpart)
+    Engine.tree_nj(rows, n)                neighbour-joining tree of the genomes: children and branch lengths (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -118,6 +119,7 @@ def _bind(lib):
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_average": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
+        "ani_tree_nj": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -403,6 +405,20 @@ class Engine:
             count[n_genomes + s] = count[x] + count[y]
         z[:, 3] = count[n_genomes:]
         return z
+
+    def tree_nj(self, rows, n_genomes, missing_identity=0.0):
+        """neighbour-joining tree of the genomes over the fixed-point pair distances (ani_tree_nj; the semantics are in ani_abi.h):
+        `rows` as for cluster_greedy, a pair without rows at missing_identity.  -> (children int64 (n_genomes - 1, 2), lengths float32
+        (n_genomes - 1, 2)): record s joins the nodes children[s] (smaller id first; a leaf's id is its index, join s makes node
+        n_genomes + s) with the branch lengths[s] above each; the last record holds the two nodes that remain (an unrooted tree)."""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        n_genomes = int(n_genomes)
+        m = max(n_genomes - 1, 0)
+        children = np.empty(2 * m, dtype=np.int32)
+        length = np.empty(2 * m, dtype=np.float32)
+        self._chk(self.lib.ani_tree_nj(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
+                                       children.ctypes.data if m else None, length.ctypes.data if m else None))
+        return children.reshape(m, 2).astype(np.int64), length.reshape(m, 2)
 
 
 class FragmentSet:

@@ -1,8 +1,8 @@
 // engine_map.hip — mapping and reduction: L1 seed lookup + candidate regions, L2 sliding MinHash, identity filter
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
 // src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
-// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their average-linkage tree (ani_tree_average,
-// kernels/tree.hpp).
+// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their trees: average linkage (ani_tree_average,
+// kernels/tree.hpp) and neighbour joining (ani_tree_nj, kernels/nj.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -11,6 +11,7 @@
 #include "kernels/reduce.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
+#include "kernels/nj.hpp"
 
 namespace anih {
 using namespace ani;
@@ -752,6 +753,96 @@ int tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, floa
   return ANI_OK;
 }
 
+// ---- neighbour-joining tree of the pair values (ani_tree_nj) ----
+// Device memory: 4 bytes per cell of the int32 matrix (n x ld, ld = n rounded up to 64) plus, beyond 64 genomes, the matrix the first
+// compaction writes (7/8 n on a side: 0.77 of the first); 40 bytes per genome; per row 20 + 2 x 12 + 12 bytes while the pairs are
+// folded, released before the joins.  The joins are a plain enqueue loop: per record one k_nj_scan, per join one k_nj_update, and
+// whenever an eighth of the matrix's positions is retired (the host knows when: one per join) a k_nj_map / k_nj_compact pair into
+// the other matrix.  Nothing is read back before the end.
+int tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *length)
+{
+  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, QMAT_A, QMAT_B, STATE_A, STATE_B, NEWPOS, PART, OUT, NBUF };
+  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
+  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
+  auto round64 = [](uint64_t x) { return (x + 63) & ~63ull; };
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG, M = V - 1;
+  const uint64_t ld = round64(V);
+  const uint64_t second = nG > 64 ? V * 7 / 8 : 0;                // positions of the first compacted matrix
+  constexpr unsigned kMaxGrid = 2048;                              // workgroups of a scan: 8 per CU
+  const int32_t qMissing = (int32_t)rint((100.0 - (double)missingIdentity) * 16777216.0 / 100.0);
+  NjArgs t, u;                                                     // the matrix in use, the other one
+  uint32_t *flags, *newPos; char *state[2];
+  TRY(buf(QMAT_A, (size_t)ld * V * 4, (void **)&t.q));
+  u.q = nullptr;
+  if (second) TRY(buf(QMAT_B, (size_t)round64(second) * second * 4, (void **)&u.q));
+  TRY(buf(FLAGS, 64, (void **)&flags)); TRY(buf(NEWPOS, ld * 4, (void **)&newPos));
+  TRY(buf(STATE_A, ld * 16, (void **)&state[0])); TRY(buf(STATE_B, ld * 16, (void **)&state[1]));
+  TRY(buf(PART, (size_t)kMaxGrid * 12, (void **)&t.partQ)); TRY(buf(OUT, M * 16, (void **)&t.children));
+  t.ld = ld; t.n = nG; t.cur = nG;
+  t.partAB = (uint32_t *)(t.partQ + kMaxGrid); t.length = (float *)(t.children + 2 * M);
+  // flags: [0] a bad id (1) or identity (2), [1] the arrival counter of k_nj_scan, [4..6] the pick
+  t.arrived = flags + 1; t.pick = (int32_t *)flags + 4;
+  u = NjArgs{u.q, 0, nG, 0, nullptr, nullptr, nullptr, t.pick, t.partQ, t.partAB, t.arrived, t.children, t.length};
+  auto set_state = [&](NjArgs &x, int i) { x.R = (int64_t *)state[i]; x.id = (int32_t *)(state[i] + ld * 8); x.active = (uint32_t *)(state[i] + ld * 12); };
+  set_state(t, 0); set_state(u, 1);
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
+  hipLaunchKernelGGL(k_nj_fill, dim3(nG), dim3(kTPB), 0, st, t.q, ld, nG, qMissing);
+  HIP_TRY(hipGetLastError());
+
+  if (n) {
+    // the pair values: keys and the stable sort as for the clustering, then one fold per pair into q
+    int b = 1;
+    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
+    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
+    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
+    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
+    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
+    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
+    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
+    size_t tb = 0;
+    int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
+    void *sortTmp = nullptr;
+    if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
+    if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
+    hipLaunchKernelGGL(k_nj_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                       (uint64_t)n, b, t.q, ld);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int i : {ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, SORT}) B.b[i].release();
+  }
+
+  hipLaunchKernelGGL(k_nj_rowsum, dim3((unsigned)ld), dim3(kTPB), 0, st, t);
+  HIP_TRY(hipGetLastError());
+  for (int32_t s = 0; s + 1 < nG; s++) {
+    const uint32_t cur = (uint32_t)t.cur, rowsPerTile = cur <= 4096 ? 16 : 64;
+    const uint64_t tiles = (uint64_t)((cur + kNjCols - 1) / kNjCols) * ((cur + rowsPerTile - 1) / rowsPerTile);
+    hipLaunchKernelGGL(k_nj_scan, dim3((unsigned)std::min<uint64_t>(tiles, kMaxGrid)), dim3(kTPB), 0, st, t, s, rowsPerTile);
+    if (s + 2 == nG) break;                                        // the last record joins nothing
+    hipLaunchKernelGGL(k_nj_update, dim3(grid_for(cur, kTPB)), dim3(kTPB), 0, st, t);
+    const uint64_t m = (uint64_t)(nG - s - 1);                     // active positions now
+    if (cur > 64 && 8 * m <= 7 * (uint64_t)cur) {
+      u.cur = (int32_t)m; u.ld = round64(m);
+      hipLaunchKernelGGL(k_nj_map, dim3(1), dim3(kTPB), 0, st, t, u, newPos);
+      hipLaunchKernelGGL(k_nj_compact, dim3(cur), dim3(kTPB), 0, st, t, u, (const uint32_t *)newPos);
+      std::swap(t, u);
+    }
+    if ((s & 255) == 255) HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(children, t.children, M * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(length, t.length, M * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -974,6 +1065,18 @@ int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGen
   if (nGenomes <= 1) return ANI_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   return tree_average(ctx, rows, n, nGenomes, missingIdentity, children, height);
+}
+
+int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *length)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !length))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
+  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the tree takes at most 65536", nGenomes);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  if (nGenomes <= 1) return ANI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return tree_nj(ctx, rows, n, nGenomes, missingIdentity, children, length);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // src/cgi/include/computeCoreIdentity.hpp:307-344, cgi::outputPhylip :353-448, cgi::outputVisualizationFile :103-153,
 // cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
 // (greedy species clusters over the .matrix cells, ani_cluster_greedy), `--tree` (extension) a .newick file (their average-linkage
-// tree, ani_tree_average).  Sketch / Map / computeCGI run on the GPU(s)
+// tree, ani_tree_average, or with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -64,6 +64,7 @@ struct Options {
   bool visualize = false, matrix = false, sanityCheck = false;
   float cluster = 0.0f;                                // --cluster T: greedy clustering at w >= T (0 = off)
   bool tree = false;                                   // --tree: average-linkage tree of the .matrix cells
+  bool treeNj = false;                                 // --treeMethod nj: their neighbour-joining tree instead
   std::vector<std::string> refs, queries;
   std::vector<int> devices{0};
   std::string out, saveSketch, refSketch;
@@ -79,7 +80,7 @@ struct Options {
     "SYNOPSIS\n"
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
-    "             [--tree] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--tree] [--treeMethod <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -97,6 +98,8 @@ struct Options {
     "                 genome, representative, ANI to it or NA for a representative) [disabled by default]\n"
     "     --tree      also output the average-linkage (UPGMA) tree of the genomes over the distances 1 - ANI/100, a pair without\n"
     "                 ANI at distance 1 (.newick) [disabled by default]\n"
+    "     --treeMethod <value>  the tree of --tree: average, or nj for the neighbour-joining tree (unrooted: three branches at the\n"
+    "                 top; branch lengths can be negative where the distances are not tree-like) [default : average]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -131,7 +134,7 @@ Options parse(int argc, char **argv)
 {
   Options o;
   std::string refName, refList, qryName, qryList;
-  bool help = false, version = false;
+  bool help = false, version = false, treeMethod = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -150,6 +153,8 @@ Options parse(int argc, char **argv)
     else if (a == "--cluster") { o.cluster = (float)atof(need(i));
       if (!(o.cluster > 0.0f && o.cluster <= 100.0f)) { std::cerr << "ERROR, --cluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "--tree") o.tree = true;
+    else if (a == "--treeMethod") { const std::string v = need(i); treeMethod = true; o.treeNj = v == "nj";
+      if (v != "average" && v != "nj") { std::cerr << "ERROR, --treeMethod takes average or nj" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -162,6 +167,7 @@ Options parse(int argc, char **argv)
   }
   if (help) usage(argv[0], 0);
   if (version) { std::cerr << "version 1.33\n\n"; exit(0); }                         // parseCmdArgs.hpp:194-198
+  if (treeMethod && !o.tree) { std::cerr << "ERROR, --treeMethod needs --tree" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -1231,6 +1237,63 @@ void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
   trace("tree written");
 }
 
+// ---- .newick with --treeMethod nj: the neighbour-joining tree of the cells (ani_tree_nj on the first device, a pair without cells at
+// identity 0).  The tree is unrooted, so the top is the customary trifurcation: the two children of the last join and the node
+// that remained beside it, whose branch is the sum of the last record's two lengths.  Branch lengths are ani_tree_nj's, unclamped.
+void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
+{
+  const int n = (int)mc.names.size();
+  std::vector<ani_cgi_t> rows(mc.cells.size());
+  for (size_t i = 0; i < mc.cells.size(); i++) rows[i] = ani_cgi_t{mc.cells[i].col, mc.cells[i].row, 0, 0, mc.cells[i].id};
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
+  std::vector<int32_t> children(2 * m); std::vector<float> length(2 * m);
+  if (ani_tree_nj(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), length.data())) die("ani_tree_nj");
+  std::vector<ani_cgi_t>().swap(rows);
+  BufferedFile f(path);
+  char len[64];
+  auto put_length = [&](double x) { snprintf(len, sizeof len, "%.9g", x); f.out << ':' << len; };
+  // a frame writes its node (a leaf's name, or its two children in brackets), then `length` above it
+  struct Frame { int node, phase; double length; };
+  std::vector<Frame> stack;
+  if (n == 1) write_newick_name(f.out, mc.names[0]);
+  if (n >= 2) {
+    // the top: the two nodes of the last record, or for n >= 3 the last join opened up beside the other node
+    const size_t last = 2 * (m - 1);
+    const int top = n >= 3 ? 2 * n - 3 : -1;                      // the node of join n - 3
+    const int other = children[last] == top ? 1 : 0;
+    f.out << '(';
+    if (n == 2) {
+      stack.push_back(Frame{children[1], 0, (double)length[1]});
+      stack.push_back(Frame{children[0], 0, (double)length[0]});
+    } else {
+      const size_t j = 2 * (size_t)(top - n);
+      stack.push_back(Frame{children[last + (size_t)other], 0, (double)length[last] + (double)length[last + 1]});
+      stack.push_back(Frame{children[j + 1], 0, (double)length[j + 1]});
+      stack.push_back(Frame{children[j], 0, (double)length[j]});
+    }
+    while (!stack.empty()) {
+      const Frame fr = stack.back();
+      if (fr.node >= n && fr.phase == 0) {                         // an inner node: its two children first
+        const size_t s = 2 * (size_t)(fr.node - n);
+        stack.back().phase = 1;
+        f.out << '(';
+        stack.push_back(Frame{children[s + 1], 0, (double)length[s + 1]});
+        stack.push_back(Frame{children[s], 0, (double)length[s]});
+        continue;
+      }
+      if (fr.node < n) write_newick_name(f.out, mc.names[(size_t)fr.node]); else f.out << ')';
+      put_length(fr.length);
+      stack.pop_back();
+      if (!stack.empty() && stack.back().phase == 0) f.out << ',';   // a sibling follows (a parent, phase 1, closes its bracket)
+    }
+    f.out << ')';
+  }
+  f.out << ";\n";
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
+  trace("tree written");
+}
+
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
 // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
 // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
@@ -1340,7 +1403,8 @@ int main(int argc, char **argv)
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
-  if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc);        // before write_matrix, which sorts the cells in place
+  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc);      // (both before write_matrix, which sorts the cells in place)
+  else if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc);
   if (o.matrix) write_matrix(o.out + ".matrix", mc);
   write_visual(o, res);
   std::cerr << "INFO, skch::main, Time spent writing the output : " << secs_since(tOut) << " sec; total : " << secs_since(tStart) << " sec" << std::endl;

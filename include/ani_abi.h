@@ -332,6 +332,30 @@ int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG
 int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
                      int32_t *children, float *height);
 
+/* ---- neighbour-joining tree of the genomes (Saitou & Nei, the Q criterion of Studier & Keppler; no counterpart in the reference;
+ * DESIGN.md section 2.13).  Defined on fixed-point integers, where the row sums and the criterion are exact, so that the result does
+ * not depend on the order of any reduction.
+ * 1. Rows and argument checks as for ani_tree_average: ids in ONE numbering [0, nGenomes), the rows of a pair folded in the order given
+ *    into w(i, j), self rows ignored.
+ * 2. Leaf distance, int32 in units of 2^-24: q(i, j) = (int32) rint((100.0 - (double)w) * 2^24 / 100.0) (round-half-even), with
+ *    w = missingIdentity for a pair without rows.
+ * 3. Nodes live in slots 0..nGenomes-1 (slot i starts as leaf i); m = active slots; R_i = sum over the active k != i of q(i, k), int64.
+ * 4. Join s = 0..nGenomes-3 (m >= 3) takes the active slots a < b with the smallest Q(a, b) = (m - 2) q(a, b) - R_a - R_b (int64);
+ *    ties: the smallest a, then the smallest b.
+ * 5. Its branch lengths: with t = (double)(R_a - R_b) / (double)(m - 2), len_a = (float)(((double)q(a, b) + t) * 0.5 / 2^24) and
+ *    len_b = (float)(((double)q(a, b) - t) * 0.5 / 2^24).  Not clamped: a negative branch (input that is not tree-like) is reported.
+ * 6. For every other active slot k, q(a, k) = clamp((q(a, k) + q(b, k) - q(a, b)) >> 1, +-(2^31 - 1)) (the sum in int64, the shift
+ *    arithmetic: floor); b is retired; the new node has id nGenomes + s and sits in slot a; R follows.
+ * 7. The last record, s = nGenomes - 2 (m = 2), holds the two remaining nodes with len_a = len_b = (float)((double)q(a, b) * 0.5 / 2^24);
+ *    for nGenomes >= 3 one of them is the node of join nGenomes - 3.
+ * 8. children[2s], children[2s + 1] are the ids of the two nodes of record s, the smaller id first; length[2s], length[2s + 1] the
+ *    branch above each, in that order.  children and length hold 2 (nGenomes - 1) values each.  nGenomes <= 1: ANI_OK, nothing is
+ *    read or written.
+ * Errors and limits as for ani_tree_average; ANI_ERR_NOMEM: the device cannot hold the nGenomes^2 int32 matrix (and the compacted
+ * copy, 0.77 of it, that the joins move to). */
+int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                int32_t *children, float *length);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */

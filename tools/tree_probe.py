@@ -1,8 +1,12 @@
-"""Timings of ani_tree_average (average-linkage tree) on synthetic row sets, on the GPU.  The call returns
-after its last device-to-host copy, so the wall clock around it includes the upload, the matrix, every merge launch and the read-back.
+"""Timings of ani_tree_average (average-linkage tree) and, with --method nj, of ani_tree_nj (neighbour joining,
+section 2.13) on synthetic row sets, on the GPU.  The call returns after its last device-to-host copy, so the wall clock around it
+includes the upload, the matrix, every merge launch and the read-back.
 
     python tools/tree_probe.py                 the row sets below, 1 warm-up + 3 timed calls each (median reported)
     python tools/tree_probe.py --only hub      only the row sets whose name starts with that (e.g. under rocprofv3)
+    python tools/tree_probe.py --method nj     ani_tree_nj on the same row sets, with the bytes its scans read by its own model
+                                               (nj_scan_bytes) and the rate that makes of the median
+    python tools/tree_probe.py --reps 1        timed calls per row set (default 3)
     python tools/tree_probe.py --cli 1000      in addition: fastANI --ql L --rl L --tree on that many 5 Mbp genomes, the
                                                ANI_CLI_TRACE marks of the run ("rows ordered" -> "tree written" is the tree's share)
 
@@ -45,12 +49,33 @@ def hub_rows(m):
     return rows
 
 
-def time_call(e, rows, n, reps=3):
+def nj_scan_bytes(n):
+    """what the scans of one ani_tree_nj call read, by the host loop of tree_nj (engine_map.hip): record s scans the tiles of 256
+    columns x 16 or 64 rows that reach above the diagonal of the current matrix, 4 bytes per cell, and the matrix is compacted to the
+    active positions whenever an eighth of its positions is retired -> (bytes, cells of the active upper triangles: the n^3 / 6)"""
+    cur, total, ideal = n, 0, 0
+    for s in range(n - 1):
+        rows_per_tile = 16 if cur <= 4096 else 64
+        r0 = np.arange(0, cur, rows_per_tile)
+        r1 = np.minimum(r0 + rows_per_tile, cur)
+        first = np.where(r0 >= 255, (r0 - 255) // 256 + 1, 0)       # the first tile column with c0 + 255 > r0
+        ld = (cur + 63) // 64 * 64
+        cols = np.maximum(ld - first * 256, 0)
+        total += int(((r1 - r0) * cols).sum()) * 4
+        m = n - s
+        ideal += m * (m - 1) // 2
+        if s + 2 < n and cur > 64 and 8 * (m - 1) <= 7 * cur:
+            cur = m - 1
+    return total, ideal
+
+
+def time_call(e, rows, n, reps=3, method="average"):
     children = np.empty(2 * (n - 1), dtype=np.int32)
-    height = np.empty(n - 1, dtype=np.float32)
+    height = np.empty(2 * (n - 1), dtype=np.float32)
+    fn = e.lib.ani_tree_nj if method == "nj" else e.lib.ani_tree_average
 
     def call():
-        rc = e.lib.ani_tree_average(e.h, rows.ctypes.data, len(rows), n, ctypes.c_float(0.0), children.ctypes.data, height.ctypes.data)
+        rc = fn(e.h, rows.ctypes.data, len(rows), n, ctypes.c_float(0.0), children.ctypes.data, height.ctypes.data)
         assert rc == 0, rc
     call()                                                         # warm-up: code objects, pool segments, page-locked staging
     ms = []
@@ -58,8 +83,11 @@ def time_call(e, rows, n, reps=3):
         t0 = time.perf_counter()
         call()
         ms.append((time.perf_counter() - t0) * 1e3)
-    assert (np.diff(height) >= 0).all()
-    return ms, float(height[-1])
+    if method == "nj":
+        assert sorted(children.tolist()) == list(range(2 * n - 2))
+        return ms, float(height.sum())
+    assert (np.diff(height[:n - 1]) >= 0).all()
+    return ms, float(height[n - 2])
 
 
 def cli_run(n):
@@ -98,11 +126,23 @@ def main():
             ("path 2000", lambda: path_rows(2000), 2000),
             ("hub 2000", lambda: hub_rows(2000), 2000)]
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
+    method = sys.argv[sys.argv.index("--method") + 1] if "--method" in sys.argv else "average"
+    reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
+    assert method in ("average", "nj"), method
     for name, make, n in sets:
         if not name.startswith(only):
             continue
         rows = make()
-        ms, top = time_call(e, rows, n)
+        ms, top = time_call(e, rows, n, reps, method)
+        if method == "nj":
+            med = float(np.median(ms))
+            nbytes, ideal = nj_scan_bytes(n)
+            print("%-14s rows %9d genomes %6d   ani_tree_nj %s ms (median %.1f, %.2f us per join)   scans read %.3f GB = %.2f x the %.3g "
+                  "active cells -> %.2f TB/s   tree length %.4f"
+                  % (name, len(rows), n, " ".join("%.1f" % x for x in ms), med, med * 1e3 / (n - 1), nbytes / 1e9, nbytes / 4 / ideal, ideal,
+                     nbytes / med / 1e9, top), flush=True)
+            del rows
+            continue
         print("%-14s rows %9d genomes %6d   ani_tree_average %s ms (median %.1f, %.2f us per merge)   root height %.4f"
               % (name, len(rows), n, " ".join("%.1f" % x for x in ms), float(np.median(ms)), float(np.median(ms)) * 1e3 / (n - 1), top), flush=True)
         del rows
