@@ -7,6 +7,8 @@
     Engine.cluster_greedy(rows, n, t)      greedy species clustering of the rows at an ANI threshold (no reference counterpart)
     Engine.tree_average(rows, n)           average-linkage (UPGMA) tree of the genomes, scipy linkage form (no reference counterpart)
     Engine.tree_nj(rows, n)                neighbour-joining tree of the genomes: children and branch lengths (no reference counterpart)
+    Sketch.signatures(size)                bottom-`size` signatures of the reference genomes from their minimizers (no reference counterpart)
+    Engine.signature_pairs(sig, len, k)    Mash-style ANI estimate between all pairs of signatures (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -22,6 +24,7 @@ MAPPING_DT = np.dtype([("queryLen", "<i4"), ("refStartPos", "<i4"), ("refEndPos"
                        ("nucIdentityUpperBound", "<f4"), ("sketchSize", "<i4"), ("conservedSketches", "<i4")])
 CGI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("countSeq", "<i4"),
                    ("totalQueryFragments", "<i4"), ("identity", "<f4")])
+SIGPAIR_DT = np.dtype([("a", "<i4"), ("b", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -120,6 +123,8 @@ def _bind(lib):
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_average": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_nj": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
+        "ani_sketch_signatures": (C.c_int, [vp, C.c_int32, vp, vp]),
+        "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -420,6 +425,20 @@ class Engine:
                                        children.ctypes.data if m else None, length.ctypes.data if m else None))
         return children.reshape(m, 2).astype(np.int64), length.reshape(m, 2)
 
+    def signature_pairs(self, sig, length, kmer_size, min_shared=1):
+        """all pairs a < b of the signatures `sig` (uint32 (n, size), rows ascending) of lengths `length` with at least min_shared
+        shared values among the first `size` of their union (ani_signature_pairs; the semantics are in ani_abi.h) -> SIGPAIR_DT
+        array ordered by (a, b): shared, size and the Mash-style identity estimate at k-mer size kmer_size."""
+        sig = np.ascontiguousarray(sig, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        if sig.ndim != 2 or length.shape != (sig.shape[0],):
+            raise ValueError("sig must be (n, size) and length (n,)")
+        n, size = sig.shape
+        p, m = C.c_void_p(), C.c_size_t()
+        self._chk(self.lib.ani_signature_pairs(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
+                                               int(min_shared), C.byref(p), C.byref(m)))
+        return self._take(p, m.value, SIGPAIR_DT)
+
 
 class FragmentSet:
     """Fragment sketches of a batch of query genomes kept on the device (ani_fragset)."""
@@ -565,6 +584,22 @@ class Sketch:
         p, n = C.c_void_p(), C.c_size_t()
         self.e._chk(self.e.lib.ani_sketch_export(self.h, C.byref(p), C.byref(n)))
         return self.e._take(p, n.value, MINIMIZER_DT)
+
+    def signatures(self, size=1000):
+        """the `size` smallest distinct minimizer hashes of every genome (ani_sketch_signatures) -> (sig uint32 (nGenomes, size), rows
+        ascending with the unused tail 0; len int32 (nGenomes,))"""
+        n = self._counts()[1]
+        size = int(size)
+        sig = np.zeros((n, max(size, 0)), dtype=np.uint32)
+        length = np.zeros(n, dtype=np.int32)
+        self.e._chk(self.e.lib.ani_sketch_signatures(self.h, size, sig.ctypes.data if sig.size else None, length.ctypes.data if n else None))
+        return sig, length
+
+    def _counts(self):
+        """(contigs, genomes) without the distinct-hash count that stats() computes"""
+        d, f = C.c_int32(), C.c_int32()
+        self.e._chk(self.e.lib.ani_sketch_stats(self.h, None, None, None, C.byref(d), C.byref(f)))
+        return d.value, f.value
 
     def save(self, path, names=None):
         arr = None

@@ -958,6 +958,27 @@ int ani_sketch_file_info(const char *path, ani_params_t *p, int32_t *nContigs, i
   return ANI_OK;
 }
 
+// the genome names of a sketch file without loading anything: nGenomes NUL-terminated strings, one after the other (ani_free releases them)
+int ani_sketch_file_names(const char *path, char **names, size_t *bytes)
+{
+  if (!path || !names || !bytes) return fail(ANI_ERR_ARG, "null argument");
+  FILE *f = fopen(path, "rb");
+  if (!f) return fail(ANI_ERR_ARG, "cannot open %s", path);
+  SketchFileHeader h;
+  bool ok = fread(&h, 1, sizeof h, f) == sizeof h && memcmp(h.magic, "ANISKTCH", 8) == 0 && h.version == 1;
+  struct stat st;
+  ok = ok && fstat(fileno(f), &st) == 0 && h.nGenomes >= 0 && h.offNames <= (uint64_t)st.st_size && h.namesBytes <= (uint64_t)st.st_size - h.offNames;
+  if (!ok) { fclose(f); return fail(ANI_ERR_ARG, "%s is not a version-1 sketch file", path); }
+  // one NUL more than the file holds: a truncated name table still ends every string
+  char *buf = (char *)calloc((size_t)h.namesBytes + (size_t)h.nGenomes + 1, 1);
+  if (!buf) { fclose(f); return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+  ok = fseeko(f, (off_t)h.offNames, SEEK_SET) == 0 && fread(buf, 1, (size_t)h.namesBytes, f) == (size_t)h.namesBytes;
+  fclose(f);
+  if (!ok) { free(buf); return fail(ANI_ERR_ARG, "%s is truncated", path); }
+  *names = buf; *bytes = (size_t)h.namesBytes;
+  return ANI_OK;
+}
+
 // genome name / contig lengths of a (loaded) sketch: what the command line needs to print results without the FASTA files
 const char *ani_sketch_genome_name(const ani_sketch *sk, int32_t g) { return (sk && g >= 0
     && g < (int32_t)sk->genomeNames.size()) ? sk->genomeNames[g].c_str() : ""; }

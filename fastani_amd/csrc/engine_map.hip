@@ -2,7 +2,9 @@
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
 // src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
 // clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their trees: average linkage (ani_tree_average,
-// kernels/tree.hpp) and neighbour joining (ani_tree_nj, kernels/nj.hpp).
+// kernels/tree.hpp) and neighbour joining (ani_tree_nj, kernels/nj.hpp); and the whole-genome sketch estimate that fills the pairs the
+// mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
+// ani_signature_pairs, kernels/sigdist.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -12,6 +14,7 @@
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
 #include "kernels/nj.hpp"
+#include "kernels/sigdist.hpp"
 
 namespace anih {
 using namespace ani;
@@ -843,6 +846,183 @@ int tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float mis
   return ANI_OK;
 }
 
+// ---- whole-genome sketch ANI (ani_sketch_signatures, ani_signature_pairs) ----
+namespace {
+struct SigBufs {
+  std::vector<DevBuf> b;
+  explicit SigBufs(size_t n) : b(n) {}
+  SigBufs(const SigBufs &) = delete;
+  ~SigBufs() { for (DevBuf &x : b) x.release(); }
+  int get(int i, size_t bytes, void **out) { const int rc = b[(size_t)i].ensure(bytes ? bytes : 1); *out = b[(size_t)i].p; return rc; }
+};
+}  // namespace
+
+// Per index chunk, from whichever form of its records is at hand (the index arrays of a resident chunk, else the 12-byte records a
+// streamed set keeps: nothing is rebuilt).  Round 1 keeps the records at or below a per-genome hash threshold that lets about
+// 2 size + 64 k-mers of the genome through (a k-mer that small is a window minimizer almost surely), sorts those few keys and numbers
+// the distinct ones; a genome that yields fewer than `size` that way (repeats, a short genome) goes through round 2 with every record.
+// Device memory: 8 bytes per genome, 4 + 4 per block of 2048 records, 2 x 8 bytes per kept record plus the sort's workspace,
+// 4 (size + 1) per genome for the result.
+int sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
+{
+  enum { THR, CNT, OFF, KEYS_A, KEYS_B, SORT, SIG, LEN, NBUF };
+  SigBufs B(NBUF);
+  ani_ctx *ctx = sk->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t kAll = 0xffffffffll;
+  for (const IndexChunk *ch : sk->chunks) {
+    const int32_t nG = ch->nGenomes;
+    if (nG <= 0) continue;
+    std::vector<SigSource> src;
+    if (ch->n) {
+      if (ch->resident) src.push_back(SigSource{ch->mHash, ch->mSeq, 1u, 0, (uint64_t)ch->n});
+      else for (const RecordPiece &pc : ch->pieces) if (pc.n) src.push_back(SigSource{pc.rec, (const int32_t *)pc.rec + 1, 3u, ch->c0, (uint64_t)pc.n});
+      if (src.empty()) return fail(ANI_ERR_INTERNAL, "index chunk of genomes [%d, %d) holds neither index arrays nor records", ch->g0, ch->g0 + nG);
+    }
+    uint64_t nBlocks = 0;
+    for (const SigSource &s : src) nBlocks += (s.n + kSigBlock - 1) / kSigBlock;
+    std::vector<int64_t> thr((size_t)nG);
+    const uint64_t want = 2 * (uint64_t)size + 64;
+    for (int32_t g = 0; g < nG; g++) {
+      uint64_t bases = 0;
+      for (int32_t c = sk->genomeContigStart[(size_t)(ch->g0 + g)]; c < sk->genomeContigStart[(size_t)(ch->g0 + g) + 1]; c++) bases += (uint64_t)sk->contigLen[(size_t)c];
+      const uint64_t recs = sk->genomeRecStart[(size_t)(ch->g0 + g) + 1] - sk->genomeRecStart[(size_t)(ch->g0 + g)];
+      thr[(size_t)g] = (bases <= want || recs <= want) ? kAll : (int64_t)std::min<uint64_t>((uint64_t)kAll, (want << 32) / bases);
+    }
+    int64_t *dThr; int32_t *dCnt, *dLen; uint32_t *dOff, *dSig;
+    TRY(B.get(THR, (size_t)nG * 8, (void **)&dThr)); TRY(B.get(CNT, nBlocks * 4, (void **)&dCnt)); TRY(B.get(OFF, nBlocks * 4, (void **)&dOff));
+    TRY(B.get(SIG, (size_t)nG * (size_t)size * 4, (void **)&dSig)); TRY(B.get(LEN, (size_t)nG * 4, (void **)&dLen));
+    std::vector<int32_t> hostLen((size_t)nG);
+    int bits = 1;
+    while (bits < 31 && ((uint32_t)(nG - 1) >> bits) != 0) bits++;
+    for (int round = 0; round < 2; round++) {
+      HIP_TRY(hipMemcpyAsync(dThr, thr.data(), (size_t)nG * 8, hipMemcpyHostToDevice, st));
+      uint64_t total = 0, at = 0;
+      for (const SigSource &s : src) {
+        const uint64_t nb = (s.n + kSigBlock - 1) / kSigBlock;
+        hipLaunchKernelGGL(k_sig_count, dim3((unsigned)nb), dim3(kTPB), 0, st, s, (const int32_t *)ch->contigGenome, (const int64_t *)dThr, dCnt + at);
+        at += nb;
+      }
+      HIP_TRY(hipGetLastError());
+      if (nBlocks) TRY(device_scan(ctx, dCnt, dOff, (uint32_t)nBlocks, &total));
+      uint64_t *keysA, *keysB;
+      TRY(B.get(KEYS_A, (size_t)total * 8, (void **)&keysA)); TRY(B.get(KEYS_B, (size_t)total * 8, (void **)&keysB));
+      if (total) {
+        at = 0;
+        for (const SigSource &s : src) {
+          const uint64_t nb = (s.n + kSigBlock - 1) / kSigBlock;
+          hipLaunchKernelGGL(k_sig_keys, dim3((unsigned)nb), dim3(kTPB), 0, st, s, (const int32_t *)ch->contigGenome, (const int64_t *)dThr,
+                             (const uint32_t *)dOff + at, keysA);
+          at += nb;
+        }
+        HIP_TRY(hipGetLastError());
+        size_t tb = 0;
+        int rc = ani_sort_keys_u64_bits(keysA, keysB, (size_t)total, 32 + bits, nullptr, &tb, st);
+        void *sortTmp = nullptr;
+        if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_keys_u64_bits(keysA, keysB, (size_t)total, 32 + bits, sortTmp, &tb, st); }
+        if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the signature keys failed (%d)", rc);
+      }
+      hipLaunchKernelGGL(k_sig_emit, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint64_t *)keysB, (uint32_t)total, (const int64_t *)dThr, size, dSig, dLen);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(hostLen.data(), dLen, (size_t)nG * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      bool again = false;
+      for (int32_t g = 0; g < nG && round == 0; g++) {
+        const bool more = hostLen[(size_t)g] < size && thr[(size_t)g] >= 0 && thr[(size_t)g] != kAll;
+        thr[(size_t)g] = more ? kAll : -1;
+        again = again || more;
+      }
+      if (!again) break;
+    }
+    HIP_TRY(hipMemcpyAsync(sig + (size_t)ch->g0 * (size_t)size, dSig, (size_t)nG * (size_t)size * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(len + ch->g0, hostLen.data(), (size_t)nG * 4);
+  }
+  return ANI_OK;
+}
+
+// identity of a pair from its exact integers (ani_abi.h): one double expression, rounded once
+static inline float sig_identity(int32_t shared, int32_t size, int32_t kmerSize)
+{
+  if (shared == 0) return 0.0f;
+  double id = 100.0 * (1.0 + log(2.0 * (double)shared / (double)(size + shared)) / (double)kmerSize);
+  if (id < 0.0) id = 0.0;
+  if (id > 100.0) id = 100.0;
+  return (float)id;
+}
+
+// the merge tiles by row pitch: T x T pairs per workgroup, 2 T rows of `pitch` words in LDS
+static void sigpair_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, int32_t n, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld)
+{
+  auto tiles = [&](int t) { return dim3((unsigned)((n + t - 1) / t), (unsigned)((n + t - 1) / t)); };
+  if (pitch <= 256) hipLaunchKernelGGL((k_sigpair_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, pitch, size, mat, ld);
+  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigpair_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, pitch, size, mat, ld);
+  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigpair_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, pitch, size, mat, ld);
+  else hipLaunchKernelGGL((k_sigpair_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, pitch, size, mat, ld);
+}
+
+// The rows are staged and validated first, then the matrix is taken.  Device memory: the rows twice (as given and at a pitch of whole quads), 4 bytes per cell of the n x n result matrix (its upper
+// triangle is used), 8 bytes per genome, 16 bytes per row returned.  Everything goes back to the pool on return.
+int signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared,
+                    ani_sigpair_t **rows, size_t *n)
+{
+  enum { RAW, LEN, SIG, FLAGS, MAT, CNT, OFF, OUT, NBUF };
+  SigBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG;
+  const int32_t pitch = (size + 3) & ~3;
+  const uint64_t ld = (V + 3) & ~(uint64_t)3;
+  uint32_t *dRaw, *dSig, *dFlags, *dMat, *dOff; int32_t *dLen, *dCnt;
+  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
+  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  TRY(B.get(CNT, V * 4, (void **)&dCnt)); TRY(B.get(OFF, V * 4, (void **)&dOff));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  B.b[RAW].release();
+  TRY(B.get(MAT, (size_t)ld * V * 4, (void **)&dMat));                 // (after the rows are known to be good: a bad row is ANI_ERR_ARG whatever the size)
+  sigpair_launch(st, dSig, dLen, nG, pitch, size, dMat, ld);
+  hipLaunchKernelGGL(k_sigpair_count, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, nG, minShared, dCnt);
+  HIP_TRY(hipGetLastError());
+  uint64_t total = 0;
+  TRY(device_scan(ctx, dCnt, dOff, (uint32_t)nG, &total));
+  ani_sigpair_t *out = (ani_sigpair_t *)malloc((total ? total : 1) * sizeof(ani_sigpair_t));
+  if (!out) return fail(ANI_ERR_NOMEM, "host allocation of %llu pair rows failed", (unsigned long long)total);
+  struct Guard { ani_sigpair_t *p; ~Guard() { free(p); } } guard{out};
+  if (total) {
+    uint4 *dOut;
+    TRY(B.get(OUT, (size_t)total * 16, (void **)&dOut));
+    hipLaunchKernelGGL(k_sigpair_write, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, nG, minShared, (const uint32_t *)dOff, dOut);
+    HIP_TRY(hipGetLastError());
+    // back through page-locked staging in pieces; the identities are host arithmetic (ani_abi.h)
+    const size_t piece = (size_t)1 << 21;
+    int32_t *stage = nullptr;
+    TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)total) * 16, (void **)&stage));
+    for (size_t r0 = 0; r0 < (size_t)total; r0 += piece) {
+      const size_t m = std::min<size_t>(piece, (size_t)total - r0);
+      HIP_TRY(hipMemcpyAsync(stage, dOut + r0, m * 16, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      const size_t step = 8192;
+      parallel_for((m + step - 1) / step, (uint64_t)m * 64, [&](size_t blk) {
+        for (size_t i = blk * step; i < std::min(m, (blk + 1) * step); i++) {
+          const int32_t *q = stage + 4 * i;
+          out[r0 + i] = ani_sigpair_t{q[0], q[1], q[2], q[3], sig_identity(q[2], q[3], kmerSize)};
+        }
+      });
+    }
+  }
+  guard.p = nullptr;
+  *rows = out; *n = (size_t)total;
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -1077,6 +1257,37 @@ int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes,
   if (nGenomes <= 1) return ANI_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   return tree_nj(ctx, rows, n, nGenomes, missingIdentity, children, length);
+}
+
+int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (sk->nGenomes > 0 && (!sig || !len)) return fail(ANI_ERR_ARG, "null argument");
+  if (sk->nGenomes <= 0) return ANI_OK;
+  HIP_TRY(hipSetDevice(sk->device));
+  return sketch_signatures(sk, size, sig, len);
+}
+
+int ani_signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                        ani_sigpair_t **rows, size_t *n)
+{
+  if (!ctx || !rows || !n || (nGenomes > 0 && (!sig || !len))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 0) return fail(ANI_ERR_ARG, "negative minShared");
+  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the pair step takes at most 65536", nGenomes);
+  for (int32_t g = 0; g < nGenomes; g++)
+    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
+  if (nGenomes <= 1) {                                                 // nothing to compare; a lone row is still checked
+    for (int32_t r = 1; nGenomes == 1 && r < len[0]; r++)
+      if (sig[r - 1] >= sig[r]) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+    *rows = (ani_sigpair_t *)malloc(sizeof(ani_sigpair_t)); *n = 0;
+    return *rows ? ANI_OK : fail(ANI_ERR_NOMEM, "host allocation failed");
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return signature_pairs(ctx, sig, len, nGenomes, size, kmerSize, minShared, rows, n);
 }
 
 }  // extern "C"

@@ -5,7 +5,9 @@
 // src/cgi/include/computeCoreIdentity.hpp:307-344, cgi::outputPhylip :353-448, cgi::outputVisualizationFile :103-153,
 // cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
 // (greedy species clusters over the .matrix cells, ani_cluster_greedy), `--tree` (extension) a .newick file (their average-linkage
-// tree, ani_tree_average, or with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj).  Sketch / Map / computeCGI run on the GPU(s)
+// tree, ani_tree_average, or with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj).  `--sketchANI` (extension) adds a .sketch
+// file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
+// tree that estimate for the pairs without a .matrix cell.  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -48,6 +50,7 @@
 #include <thread>
 #include <tuple>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "ani_abi.h"
@@ -65,6 +68,9 @@ struct Options {
   float cluster = 0.0f;                                // --cluster T: greedy clustering at w >= T (0 = off)
   bool tree = false;                                   // --tree: average-linkage tree of the .matrix cells
   bool treeNj = false;                                 // --treeMethod nj: their neighbour-joining tree instead
+  bool sketchANI = false, treeFill = false;            // --sketchANI: the .sketch file; --treeFill sketch: sketch estimates for the tree's missing pairs
+  int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
+  bool signatures() const { return sketchANI || treeFill; }
   std::vector<std::string> refs, queries;
   std::vector<int> devices{0};
   std::string out, saveSketch, refSketch;
@@ -80,7 +86,8 @@ struct Options {
     "SYNOPSIS\n"
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
-    "             [--tree] [--treeMethod <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
+    "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -100,6 +107,12 @@ struct Options {
     "                 ANI at distance 1 (.newick) [disabled by default]\n"
     "     --treeMethod <value>  the tree of --tree: average, or nj for the neighbour-joining tree (unrooted: three branches at the\n"
     "                 top; branch lengths can be negative where the distances are not tree-like) [default : average]\n"
+    "     --treeFill <value>  sketch: a pair without ANI enters the tree at the whole-genome sketch estimate (see --sketchANI) instead\n"
+    "                 of distance 1, if the two sketches share anything; the queries must be among the references [default : none]\n"
+    "     --sketchANI also output a Mash-style ANI estimate between the genomes, from the smallest minimizer hashes of each genome\n"
+    "                 (.sketch: genome, genome, estimate, shared/size); the queries must be among the references [disabled by default]\n"
+    "     --sketchSize <value>  hashes per genome sketch, 1 to 4096 [default : 1000]\n"
+    "     --sketchMinANI <value>  smallest estimate --sketchANI reports [default : 70]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -134,7 +147,7 @@ Options parse(int argc, char **argv)
 {
   Options o;
   std::string refName, refList, qryName, qryList;
-  bool help = false, version = false, treeMethod = false;
+  bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -155,6 +168,13 @@ Options parse(int argc, char **argv)
     else if (a == "--tree") o.tree = true;
     else if (a == "--treeMethod") { const std::string v = need(i); treeMethod = true; o.treeNj = v == "nj";
       if (v != "average" && v != "nj") { std::cerr << "ERROR, --treeMethod takes average or nj" << std::endl; exit(1); } }
+    else if (a == "--treeFill") { const std::string v = need(i); treeFill = true; o.treeFill = v == "sketch";
+      if (v != "none" && v != "sketch") { std::cerr << "ERROR, --treeFill takes none or sketch" << std::endl; exit(1); } }
+    else if (a == "--sketchANI") o.sketchANI = true;
+    else if (a == "--sketchSize") { o.sketchSize = atoi(need(i)); sketchSize = true;
+      if (o.sketchSize < 1 || o.sketchSize > 4096) { std::cerr << "ERROR, --sketchSize takes a size from 1 to 4096" << std::endl; exit(1); } }
+    else if (a == "--sketchMinANI") { o.sketchMinANI = (float)atof(need(i)); sketchMinANI = true;
+      if (!(o.sketchMinANI >= 0.0f && o.sketchMinANI <= 100.0f)) { std::cerr << "ERROR, --sketchMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -168,6 +188,9 @@ Options parse(int argc, char **argv)
   if (help) usage(argv[0], 0);
   if (version) { std::cerr << "version 1.33\n\n"; exit(0); }                         // parseCmdArgs.hpp:194-198
   if (treeMethod && !o.tree) { std::cerr << "ERROR, --treeMethod needs --tree" << std::endl; exit(1); }
+  if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
+  if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
+  if (sketchMinANI && !o.sketchANI) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -485,6 +508,38 @@ struct Mode {
   bool streaming;      // not -s / --visualize: one reader pool, references sharded over the devices (else whole sets in host memory, one device)
 };
 
+// Genome signatures for --sketchANI / --treeFill sketch, collected wherever a reference sketch comes into being (a shard, a block of a
+// sketch file, a reference split) and keyed by reference index, so that blocks, shards and splits end up in one table.
+struct SigTable {
+  int size = 0; std::vector<uint32_t> sig; std::vector<int32_t> len; std::vector<char> have; std::mutex mu;
+  void init(int s, size_t nRefs) { size = s; sig.assign(nRefs * (size_t)s, 0u); len.assign(nRefs, 0); have.assign(nRefs, 0); }
+  // the signatures of the sketch's genomes, which are the references [first, first + n)
+  void collect(const ani_sketch *sk, size_t first, size_t n)
+  {
+    if (!size || !n) return;
+    std::vector<uint32_t> s(n * (size_t)size); std::vector<int32_t> l(n);
+    if (ani_sketch_signatures(sk, size, s.data(), l.data())) { std::cerr << "ERROR, ani_sketch_signatures: " << ani_last_error() << std::endl; exit(1); }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t g = 0; g < n; g++) put(first + g, s.data() + g * (size_t)size, l[g]);
+  }
+  void put(size_t ref, const uint32_t *row, int32_t l) { std::copy(row, row + size, sig.begin() + (std::ptrdiff_t)(ref * (size_t)size)); len[ref] = l; have[ref] = 1; }
+};
+SigTable g_sigs;
+
+// --sketchANI / --treeFill sketch need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
+// and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped
+void check_sketch_genomes(const Options &o)
+{
+  std::unordered_set<std::string> refs(o.refs.begin(), o.refs.end());
+  if (refs.size() > 65536) {
+    std::cerr << "ERROR, --sketchANI and --treeFill sketch take at most 65536 genomes, this run has " << refs.size() << std::endl; exit(1); }
+  for (auto &q : o.queries)
+    if (!refs.count(q)) {
+      std::cerr << "ERROR, --sketchANI and --treeFill sketch compare the reference genomes: query " << q << " is not among the references" << std::endl;
+      exit(1);
+    }
+}
+
 // the reference's banner and input checks, then the options that cannot go together — before anything is read or sketched
 Mode check_options(Options &o, const ani_params_t &ap)
 {
@@ -516,6 +571,14 @@ Mode check_options(Options &o, const ani_params_t &ap)
   if (fromFile && !streaming) { std::cerr << "ERROR, --refSketch cannot be combined with --visualize or -s" << std::endl; exit(1); }
   if (!o.saveSketch.empty() && !streaming) {
     std::cerr << "ERROR, --saveSketch cannot be combined with --visualize or -s (those modes sketch per reference split)" << std::endl; exit(1); }
+  if (o.signatures() && fromFile) {               // the file's name table, read ahead of the blocks that will be loaded
+    char *names = nullptr; size_t bytes = 0;
+    if (ani_sketch_file_names(o.refSketch.c_str(), &names, &bytes)) die("reference sketch file");
+    const char *nm = names;
+    for (auto &r : o.refs) { r = nm; nm += r.size() + 1; }
+    ani_free(names);
+  }
+  if (o.signatures()) check_sketch_genomes(o);
   if (!streaming) o.devices.resize(1);            // the per-split / per-mapping paths are single-device
   if (!o.saveSketch.empty() && o.devices.size() > 1) { std::cerr << "ERROR, --saveSketch writes the sketch of one device: run it with --gpus 1" << std::endl;
     exit(1); }
@@ -820,6 +883,11 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
+    if (o.signatures()) {
+      for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
+        if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
+      trace("signatures collected");
+    }
     uint64_t occ = 0, uniq = 0; int32_t nChunks = 0; bool streamed = false;
     for (int d = 0; d < nDev; d++) {
       uint64_t oc = 0; int32_t nc = 0, st = 0;
@@ -1041,6 +1109,11 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
+    if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
+      SigTable part; part.init(g_sigs.size, refIdx.size());
+      part.collect(sk, 0, refIdx.size());
+      for (size_t g = 0; g < refIdx.size(); g++) g_sigs.put((size_t)refIdx[g], part.sig.data() + g * (size_t)part.size, part.len[g]);
+    }
     if (sp == 0) {
       std::cerr << "INFO [thread 0], skch::Sketch::build, minimizers picked from reference = " << occ << std::endl;
       std::cerr << "INFO [thread 0], skch::Sketch::index, unique minimizers = " << uniq << std::endl;
@@ -1205,11 +1278,19 @@ void write_newick_name(std::ostream &out, const std::string &name)
   out << '\'';
 }
 
-void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
+// the rows the trees are made of: the cells, then the fill cells of --treeFill sketch
+std::vector<ani_cgi_t> tree_rows(const MatrixCells &mc, const std::vector<Cell> &fill)
+{
+  std::vector<ani_cgi_t> rows; rows.reserve(mc.cells.size() + fill.size());
+  for (const Cell &c : mc.cells) rows.push_back(ani_cgi_t{c.col, c.row, 0, 0, c.id});
+  for (const Cell &c : fill) rows.push_back(ani_cgi_t{c.col, c.row, 0, 0, c.id});
+  return rows;
+}
+
+void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
 {
   const int n = (int)mc.names.size();
-  std::vector<ani_cgi_t> rows(mc.cells.size());
-  for (size_t i = 0; i < mc.cells.size(); i++) rows[i] = ani_cgi_t{mc.cells[i].col, mc.cells[i].row, 0, 0, mc.cells[i].id};
+  std::vector<ani_cgi_t> rows = tree_rows(mc, fill);
   const size_t m = n > 1 ? (size_t)n - 1 : 0;
   std::vector<int32_t> children(2 * m); std::vector<float> height(m);
   if (ani_tree_average(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data())) die("ani_tree_average");
@@ -1240,11 +1321,10 @@ void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
 // ---- .newick with --treeMethod nj: the neighbour-joining tree of the cells (ani_tree_nj on the first device, a pair without cells at
 // identity 0).  The tree is unrooted, so the top is the customary trifurcation: the two children of the last join and the node
 // that remained beside it, whose branch is the sum of the last record's two lengths.  Branch lengths are ani_tree_nj's, unclamped.
-void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
+void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
 {
   const int n = (int)mc.names.size();
-  std::vector<ani_cgi_t> rows(mc.cells.size());
-  for (size_t i = 0; i < mc.cells.size(); i++) rows[i] = ani_cgi_t{mc.cells[i].col, mc.cells[i].row, 0, 0, mc.cells[i].id};
+  std::vector<ani_cgi_t> rows = tree_rows(mc, fill);
   const size_t m = n > 1 ? (size_t)n - 1 : 0;
   std::vector<int32_t> children(2 * m); std::vector<float> length(2 * m);
   if (ani_tree_nj(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), length.data())) die("ani_tree_nj");
@@ -1292,6 +1372,46 @@ void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc)
   f.out.close();
   if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
   trace("tree written");
+}
+
+// ---- --sketchANI / --treeFill sketch: the whole-genome sketch estimate between the .matrix genomes (ani_signature_pairs on the first
+// device over the signatures collected from the reference sketches, minShared = 1).  .sketch: one line per pair whose estimate is at
+// least --sketchMinANI, in (a, b) order of the .matrix numbering: genome, genome, estimate, shared/size.  Fill cells: every pair
+// without a .matrix cell whose sketches share something, at the estimate (an estimate that the clamp leaves at 0 stays missing: it is
+// the tree's distance 1 either way).
+std::vector<Cell> sketch_pairs(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const size_t n = mc.names.size(), S = (size_t)g_sigs.size;
+  std::unordered_map<std::string, size_t> refOf;
+  for (size_t r = 0; r < o.refs.size(); r++) refOf.emplace(o.refs[r], r);
+  std::vector<uint32_t> sig(n * S); std::vector<int32_t> len(n);
+  for (size_t i = 0; i < n; i++) {
+    const auto it = refOf.find(mc.names[i]);
+    if (it == refOf.end() || !g_sigs.have[it->second]) { std::cerr << "ERROR, no genome sketch of " << mc.names[i] << std::endl; exit(1); }
+    std::copy(g_sigs.sig.begin() + (std::ptrdiff_t)(it->second * S), g_sigs.sig.begin() + (std::ptrdiff_t)((it->second + 1) * S), sig.begin() + (std::ptrdiff_t)(i * S));
+    len[i] = g_sigs.len[it->second];
+  }
+  ani_sigpair_t *rows = nullptr; size_t nr = 0;
+  if (ani_signature_pairs(ctx, sig.data(), len.data(), (int32_t)n, (int32_t)S, kmerSize, 1, &rows, &nr)) die("ani_signature_pairs");
+  trace("sketch pairs compared");
+  if (o.sketchANI) {
+    BufferedFile f(o.out + ".sketch");
+    for (size_t i = 0; i < nr; i++)
+      if (rows[i].identity >= o.sketchMinANI)
+        f.out << mc.names[(size_t)rows[i].a] << "\t" << mc.names[(size_t)rows[i].b] << "\t" << rows[i].identity << "\t" << rows[i].shared << "/" << rows[i].size << "\n";
+    f.out.close();
+    if (f.out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".sketch" << std::endl; exit(1); }
+    trace("sketch estimates written");
+  }
+  std::vector<Cell> fill;
+  if (o.treeFill) {
+    std::unordered_set<uint64_t> seen;
+    for (const Cell &c : mc.cells) seen.insert(((uint64_t)(uint32_t)c.row << 32) | (uint32_t)c.col);
+    for (size_t i = 0; i < nr; i++)
+      if (rows[i].identity > 0.0f && !seen.count(((uint64_t)(uint32_t)rows[i].b << 32) | (uint32_t)rows[i].a)) fill.push_back(Cell{rows[i].b, rows[i].a, rows[i].identity});
+  }
+  ani_free(rows);
+  return fill;
 }
 
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
@@ -1382,6 +1502,7 @@ int main(int argc, char **argv)
   Options o = parse(argc, argv);
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
+  if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
   Startup su(o, m, ap);
@@ -1401,10 +1522,12 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   MatrixCells mc;
-  if (o.matrix || o.cluster > 0.0f || o.tree) mc = matrix_cells(o, res.rows, trusted);
+  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
-  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc);      // (both before write_matrix, which sorts the cells in place)
-  else if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc);
+  std::vector<Cell> fill;
+  if (o.signatures()) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (both before write_matrix, which sorts the cells in place)
+  else if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc, fill);
   if (o.matrix) write_matrix(o.out + ".matrix", mc);
   write_visual(o, res);
   std::cerr << "INFO, skch::main, Time spent writing the output : " << secs_since(tOut) << " sec; total : " << secs_since(tStart) << " sec" << std::endl;

@@ -248,6 +248,10 @@ int ani_sketch_writer_close(ani_sketch_writer *w);
  * add fails and removes the file as well) */
 void ani_sketch_writer_abort(ani_sketch_writer *w);
 int ani_sketch_file_info(const char *path, ani_params_t *p, int32_t *nContigs, int32_t *nGenomes, uint64_t *nMinimizers);
+/* the genome names of a sketch file, read without loading it: *names holds the file's nGenomes NUL-terminated strings one after the
+ * other (a file saved without names holds empty strings; a genome beyond the table reads as empty), *bytes their total length;
+ * ani_free releases *names.  (The command line checks its queries against them before it maps anything.) */
+int ani_sketch_file_names(const char *path, char **names, size_t *bytes);
 const char *ani_sketch_genome_name(const ani_sketch *sk, int32_t genome);
 int ani_sketch_tables(const ani_sketch *sk, const int32_t **contigLen, const int32_t **genomeContigStart);
 
@@ -355,6 +359,31 @@ int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGen
  * copy, 0.77 of it, that the joins move to). */
 int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
                 int32_t *children, float *length);
+
+/* ---- whole-genome sketch ANI: a Mash-style estimate between the reference genomes from the minimizers the sketch already holds (no
+ * counterpart in the reference, which emits no row below about 80 % identity).  The smallest k-mer hashes of a
+ * genome are almost always window minimizers, so the smallest distinct minimizer hashes of a genome stand in for its bottom-s MinHash
+ * sketch.  Integers only: the result depends on no reduction order and no scheduling.
+ * 1. The signature of genome g at `size` (1 <= size <= 4096) is the ascending list of the `size` smallest distinct `hash` values among
+ *    the sketch's minimizer records whose seqId belongs to g; all of them if there are fewer.  len(g) = min(size, distinct hashes of g),
+ *    which can be 0.
+ * 2. A pair (a, b), a < b: U = the ascending distinct union of the two signatures; size(a, b) = min(size, |U|); shared(a, b) = the
+ *    number of values among the first size(a, b) of U that occur in both signatures.
+ * 3. identity(a, b), by the library on the host: 0 if shared = 0, else
+ *    100.0 * (1.0 + log(2.0 * shared / (double)(size(a, b) + shared)) / kmerSize) in double, clamped to [0, 100], rounded once to float
+ *    (the Mash distance -ln(2 j / (1 + j)) / k at j = shared / size).
+ * ani_sketch_signatures: every sketch the library can hold (built, loaded, from record parts; one or several index chunks; resident or
+ * streamed) — it reads the index arrays or the kept records, whichever are at hand, and rebuilds nothing.  sig[g * size ..] is row g,
+ * ascending, the unused tail 0; ids are the sketch's own (0 .. nGenomes - 1).  ANI_ERR_ARG: a null pointer, size outside [1, 4096].
+ * ani_signature_pairs: rows as ani_sketch_signatures lays them out (from one sketch or collected from several), genome ids = row
+ * numbers.  Returns the pairs with shared >= minShared (0: every pair), ordered by (a, b); ani_free releases *rows.  nGenomes of 0 or 1:
+ * no rows.  ANI_ERR_ARG: a null pointer, nGenomes < 0, size outside [1, 4096], kmerSize outside [1, 16], minShared < 0, a len outside
+ * [0, size], a row that does not ascend strictly inside its len; ANI_ERR_LIMIT: nGenomes > 65536 (arguments and limits are checked
+ * before anything is allocated); ANI_ERR_NOMEM: the device cannot hold the nGenomes^2 uint32 result matrix (or the host the rows). */
+typedef struct { int32_t a, b, shared, size; float identity; } ani_sigpair_t;
+int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig /* [nGenomes * size] */, int32_t *len /* [nGenomes] */);
+int ani_signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
+                        int32_t minShared, ani_sigpair_t **rows, size_t *n);
 
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut

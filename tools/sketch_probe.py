@@ -1,0 +1,108 @@
+"""Timings of the whole-genome sketch ANI on the GPU: ani_sketch_signatures on a sketch of synthetic genomes
+and ani_signature_pairs on synthetic signatures, at s = 1000.  Both calls return after their last device-to-host copy, so the wall
+clock around them includes uploads, kernels and read-back (for the pairs: the host arithmetic of the identities too).
+
+    python tools/sketch_probe.py                 1 000 / 10 000 / 65 536 genomes, 1 warm-up + 3 timed calls each (median reported)
+    python tools/sketch_probe.py --only 1000     one genome count (e.g. under rocprofv3)
+    python tools/sketch_probe.py --reps 1        timed calls per case (default 3)
+    python tools/sketch_probe.py --min-shared 1  the minShared of the pair call (default: above every pair, so no row comes back
+                                                 and the time is the comparison's; with 1 the read-back of the rows is included)
+
+Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
+smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
+rule of k_sigpair_merge (kernels/sigdist.hpp) on the host, on a sample of pairs for the larger counts, and scaled to all pairs.
+Genomes for the signature call: ani_synth_packed, 200 / 50 / 20 kb each for the three counts (a 20 kb genome has 1 600 minimizers).
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SIZE = 1000
+GENOME_LEN = {1000: 200000, 10000: 50000, 65536: 20000}
+
+
+def synthetic_signatures(rng, n, size=SIZE, universe=6000, step=700000):
+    sig = np.zeros((n, size), dtype=np.uint32)
+    length = np.zeros(n, dtype=np.int32)
+    for g in range(n):
+        s = np.flatnonzero(rng.random(universe) < rng.uniform(0.05, 0.7))[:size]
+        sig[g, :len(s)] = s.astype(np.uint32) * np.uint32(step)
+        length[g] = len(s)
+    return sig, length
+
+
+def merge_steps(x, y, size):
+    """steps of the two-pointer walk: union elements taken until `size` of them or the end of either row"""
+    u = np.union1d(x, y)
+    last = min(x[-1], y[-1]) if len(x) and len(y) else -1
+    return int(min(size, np.searchsorted(u, last, side="right")))
+
+
+def count_steps(rng, sig, length, sample=20000):
+    n = len(sig)
+    pairs = n * (n - 1) // 2
+    if pairs <= sample:
+        idx = [(a, b) for a in range(n) for b in range(a + 1, n)]
+    else:
+        a = rng.integers(0, n, sample)
+        b = rng.integers(0, n, sample)
+        idx = [(min(x, y), max(x, y)) for x, y in zip(a.tolist(), b.tolist()) if x != y]
+    total = sum(merge_steps(sig[a, :length[a]].astype(np.int64), sig[b, :length[b]].astype(np.int64), sig.shape[1]) for a, b in idx)
+    return total / len(idx) * pairs, len(idx) < pairs
+
+
+def timed(fn, reps):
+    fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return float(np.median(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--min-shared", type=int, default=SIZE + 1)
+    ap.add_argument("--skip-signatures", action="store_true")
+    a = ap.parse_args()
+    import torch
+    import fastani_amd
+    from fastani_amd.api import DeviceGenomes, Sketch
+    e = fastani_amd.engine(0)
+    rng = np.random.default_rng(1)
+    for n in (1000, 10000, 65536):
+        if a.only and n != a.only:
+            continue
+        sig, length = synthetic_signatures(rng, n)
+        steps, sampled = count_steps(rng, sig, length)
+        out = {}
+        t = timed(lambda: out.__setitem__("rows", len(e.signature_pairs(sig, length, 16, a.min_shared))), a.reps)
+        print("pairs      n=%6d s=%d: %9.3f ms   %.3e merge steps (%s)   %.3e steps/s   %d rows at minShared %d"
+              % (n, SIZE, t * 1e3, steps, "sampled" if sampled else "exact", steps / t, out["rows"], a.min_shared), flush=True)
+        if a.skip_signatures:
+            continue
+        L = GENOME_LEN[n]
+        words = (L + 15) // 16
+        buf = torch.empty(n * words, dtype=torch.int32, device="cuda:0")
+        e.synth_packed(5, 0, n, L, buf.data_ptr())
+        torch.cuda.synchronize()
+        sk = Sketch(e, e.params(16, 3000), DeviceGenomes(buf.data_ptr(), n, L))
+        got = {}
+        t = timed(lambda: got.__setitem__("len", sk.signatures(SIZE)[1]), a.reps)
+        print("signatures n=%6d s=%d: %9.3f ms   %d minimizers of %d-base genomes, %d full signatures"
+              % (n, SIZE, t * 1e3, sk.stats()["minimizers"], L, int((got["len"] == SIZE).sum())), flush=True)
+        sk.close()
+        del buf
+
+
+if __name__ == "__main__":
+    main()
