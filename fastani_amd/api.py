@@ -7,6 +7,8 @@
     Engine.cluster_greedy(rows, n, t)      greedy species clustering of the rows at an ANI threshold (no reference counterpart)
     Engine.tree_average(rows, n)           average-linkage (UPGMA) tree of the genomes, scipy linkage form (no reference counterpart)
     Engine.tree_nj(rows, n)                neighbour-joining tree of the genomes: children and branch lengths (no reference counterpart)
+    Engine.tree_single(rows, n)            single-linkage tree of the genomes (scipy linkage form) and, with return_edges, its minimum
+                                           spanning tree; memory follows the rows, no genome ceiling (no reference counterpart)
     Sketch.signatures(size)                bottom-`size` signatures of the reference genomes from their minimizers (no reference counterpart)
     Engine.signature_pairs(sig, len, k)    Mash-style ANI estimate between all pairs of signatures (no reference counterpart)
 
@@ -123,6 +125,8 @@ def _bind(lib):
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_average": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_nj": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
+        "ani_tree_single": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp, vp]),
+        "ani_tree_single_rounds": (C.c_int, [vp]),
         "ani_sketch_signatures": (C.c_int, [vp, C.c_int32, vp, vp]),
         "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     }
@@ -424,6 +428,34 @@ class Engine:
         self._chk(self.lib.ani_tree_nj(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
                                        children.ctypes.data if m else None, length.ctypes.data if m else None))
         return children.reshape(m, 2).astype(np.int64), length.reshape(m, 2)
+
+    def tree_single(self, rows, n_genomes, missing_identity=0.0, return_edges=False):
+        """single-linkage tree of the genomes over the pair distances min(1 - w / 100, 1 - missing_identity / 100) (ani_tree_single; the
+        semantics are in ani_abi.h): `rows` as for cluster_greedy, a pair without rows at 1 - missing_identity / 100.  -> scipy linkage
+        matrix, float64 (n_genomes - 1, 4), as tree_average gives it; with return_edges also `edges`, int64 (n_genomes - 1, 2): the leaf
+        pair (lo < hi) that caused each merge.  The merges below the missing distance are the minimum spanning forest of the rows'
+        pairs; cutting the linkage at 1 - T / 100 gives the connected components of the pairs with w >= T."""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        n_genomes = int(n_genomes)
+        m = max(n_genomes - 1, 0)
+        children = np.empty(2 * m, dtype=np.int32)
+        height = np.empty(m, dtype=np.float32)
+        edges = np.empty(2 * m, dtype=np.int32)
+        self._chk(self.lib.ani_tree_single(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
+                                           children.ctypes.data if m else None, height.ctypes.data if m else None,
+                                           edges.ctypes.data if m and return_edges else None))
+        z = np.empty((m, 4), dtype=np.float64)
+        z[:, 0:2] = children.reshape(m, 2)
+        z[:, 2] = height
+        count = np.ones(n_genomes + m, dtype=np.int64)
+        for s, (x, y) in enumerate(children.reshape(m, 2).tolist()):
+            count[n_genomes + s] = count[x] + count[y]
+        z[:, 3] = count[n_genomes:]
+        return (z, edges.reshape(m, 2).astype(np.int64)) if return_edges else z
+
+    def tree_single_rounds(self):
+        """spanning-forest rounds the last tree_single call of this engine took on the device (ani_tree_single_rounds)"""
+        return int(self.lib.ani_tree_single_rounds(self.h))
 
     def signature_pairs(self, sig, length, kmer_size, min_shared=1):
         """all pairs a < b of the signatures `sig` (uint32 (n, size), rows ascending) of lengths `length` with at least min_shared

@@ -2,7 +2,8 @@
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
 // src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
 // clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their trees: average linkage (ani_tree_average,
-// kernels/tree.hpp) and neighbour joining (ani_tree_nj, kernels/nj.hpp); and the whole-genome sketch estimate that fills the pairs the
+// kernels/tree.hpp), neighbour joining (ani_tree_nj, kernels/nj.hpp) and single linkage with its minimum spanning tree (ani_tree_single,
+// kernels/single.hpp); and the whole-genome sketch estimate that fills the pairs the
 // mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
 // ani_signature_pairs, kernels/sigdist.hpp).
 #include <atomic>
@@ -14,6 +15,7 @@
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
 #include "kernels/nj.hpp"
+#include "kernels/single.hpp"
 #include "kernels/sigdist.hpp"
 
 namespace anih {
@@ -846,6 +848,164 @@ int tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float mis
   return ANI_OK;
 }
 
+// ---- single-linkage tree = minimum spanning forest of the pairs with rows (ani_tree_single) ----
+// Device memory per row: 20 (rows) + 2 x 12 (keys and positions) + 12 (the sort's ping-pong) = 56 bytes during the first sort, then
+// 20 + 12 + 4 (edge positions) per row and 20 per edge while the edges are compacted; per edge 44 during the second sort and 32 during the
+// rounds; per genome 12 (component, hook, best edge) and 12 per forest edge of the result.  Nothing is proportional to nGenomes^2.
+// One count is read back per round (the live edges), which also bounds the loop; every buffer is the pool's and goes back on return.
+int tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height, int32_t *edges)
+{
+  const size_t V = (size_t)nG, M = V - 1;
+  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
+  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
+  std::vector<uint32_t> rec;                                       // the forest edges in rank order: lo, hi, bits(d)
+  ctx->treeSingleRounds = 0;
+
+  if (n) {
+    enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, FLAG, POS, E_LO, E_HI, DKEY_A, DKEY_B, IDX_A, IDX_B, U_LO, U_HI, CHOSEN, LIVE_A, LIVE_B,
+           COMP, PAR, BEST, REC, NBUF };
+    struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
+    auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
+    hipStream_t st = ctx->stream;
+    int b = 1;
+    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
+    // flags: [0] a bad id (1) or identity (2), [1] the live edges of a round, [2] a hook path that did not end
+    uint32_t *flags, *host = nullptr;
+    TRY(buf(FLAGS, 64, (void **)&flags));
+    TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+    HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
+
+    // the pair values: keys and the stable sort as for the clustering
+    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
+    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
+    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
+    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
+    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
+    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
+    uint64_t nE64 = 0;
+    uint32_t *pos = nullptr;
+    if (dmBits != 0) {                                             // (d_missing = 0: no pair lies below it)
+      size_t tb = 0;
+      int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
+      void *sortTmp = nullptr;
+      if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
+      if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
+      for (int i : {SORT, KEYS_A, VALS_A}) B.b[i].release();
+      // the edges (pairs below d_missing), compacted in (lo, hi) order
+      int32_t *flag;
+      TRY(buf(FLAG, n * 4, (void **)&flag)); TRY(buf(POS, n * 4, (void **)&pos));
+      hipLaunchKernelGGL(k_single_flag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                         (uint64_t)n, b, dmBits, flag);
+      HIP_TRY(hipGetLastError());
+      TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nE64));
+      B.b[FLAG].release();
+    }
+    const uint32_t nE = (uint32_t)nE64;
+    if (nE) {
+      uint32_t *eLo, *eHi, *idxA, *idxB; uint64_t *dKeyA, *dKeyB;
+      TRY(buf(E_LO, (size_t)nE * 4, (void **)&eLo)); TRY(buf(E_HI, (size_t)nE * 4, (void **)&eHi));
+      TRY(buf(DKEY_A, (size_t)nE * 8, (void **)&dKeyA)); TRY(buf(IDX_A, (size_t)nE * 4, (void **)&idxA));
+      hipLaunchKernelGGL(k_single_pairs, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                         (uint64_t)n, b, dmBits, (const uint32_t *)pos, eLo, eHi, dKeyA, idxA);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(st));
+      for (int i : {ROWS, KEYS_B, VALS_B, POS}) B.b[i].release();
+      // rule 3's order: a stable sort over the bits of d leaves equal distances in (lo, hi) order; an edge's position is its rank
+      TRY(buf(DKEY_B, (size_t)nE * 8, (void **)&dKeyB)); TRY(buf(IDX_B, (size_t)nE * 4, (void **)&idxB));
+      size_t tb = 0;
+      int rc = ani_sort_pairs_u64_u32(dKeyA, dKeyB, idxA, idxB, nE, 32, nullptr, &tb, st);
+      void *sortTmp = nullptr;
+      if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(dKeyA, dKeyB, idxA, idxB, nE, 32, sortTmp, &tb, st); }
+      if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair distances failed (%d)", rc);
+      for (int i : {SORT, DKEY_A, IDX_A}) B.b[i].release();
+      uint32_t *uLo, *uHi, *live[2], *comp, *par, *best; int32_t *chosen;
+      TRY(buf(U_LO, (size_t)nE * 4, (void **)&uLo)); TRY(buf(U_HI, (size_t)nE * 4, (void **)&uHi)); TRY(buf(CHOSEN, (size_t)nE * 4, (void **)&chosen));
+      hipLaunchKernelGGL(k_single_rank, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const uint32_t *)idxB, (const uint32_t *)eLo, (const uint32_t *)eHi,
+                         uLo, uHi, chosen);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(st));
+      for (int i : {E_LO, E_HI, IDX_B}) B.b[i].release();
+
+      // Boruvka rounds over the ranked edges.  A round in which e edges join two components hooks every component that has one, so the
+      // components with edges at least halve: ceil(log2 V) rounds with live edges, and one more that finds none.
+      TRY(buf(LIVE_A, (size_t)nE * 4, (void **)&live[0])); TRY(buf(LIVE_B, (size_t)nE * 4, (void **)&live[1]));
+      TRY(buf(COMP, V * 4, (void **)&comp)); TRY(buf(PAR, V * 4, (void **)&par)); TRY(buf(BEST, V * 4, (void **)&best));
+      const unsigned gridV = grid_for(V);
+      hipLaunchKernelGGL(k_single_init, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, best);
+      HIP_TRY(hipGetLastError());
+      const int maxRounds = b + 3;
+      const uint32_t *liveIn = nullptr; uint32_t nLive = nE;
+      for (int round = 0; nLive; round++) {
+        if (round >= maxRounds) return fail(ANI_ERR_INTERNAL, "the spanning forest did not converge after %d rounds", round);
+        uint32_t *liveOut = live[round & 1];
+        HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
+        hipLaunchKernelGGL(k_single_best, dim3(grid_for(nLive)), dim3(256), 0, st, liveIn, nLive, (const uint32_t *)uLo, (const uint32_t *)uHi,
+                           (const uint32_t *)comp, best, liveOut, flags + 1);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, flags + 1, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (host[1]) return fail(ANI_ERR_INTERNAL, "the hooks of round %d hold a cycle", round - 1);
+        if (host[0] > nLive) return fail(ANI_ERR_INTERNAL, "the live edges grew from %u to %u", nLive, host[0]);
+        ctx->treeSingleRounds = round + 1;
+        liveIn = liveOut; nLive = host[0];
+        if (!nLive) break;
+        hipLaunchKernelGGL(k_single_hook, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, (const uint32_t *)best, (const uint32_t *)uLo,
+                           (const uint32_t *)uHi, par, chosen);
+        hipLaunchKernelGGL(k_single_jump, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, par, flags + 2);
+        hipLaunchKernelGGL(k_single_label, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, (const uint32_t *)par, best);
+        HIP_TRY(hipGetLastError());
+      }
+      for (int i : {LIVE_A, LIVE_B}) B.b[i].release();
+
+      // the chosen edges, compacted in rank order
+      uint32_t *cpos, *dRec;
+      TRY(buf(POS, (size_t)nE * 4, (void **)&cpos));
+      uint64_t nRec = 0;
+      TRY(device_scan(ctx, chosen, cpos, nE, &nRec));
+      if (nRec > M) return fail(ANI_ERR_INTERNAL, "%llu forest edges over %d genomes", (unsigned long long)nRec, nG);
+      if (nRec) {
+        TRY(buf(REC, (size_t)nRec * 12, (void **)&dRec));
+        hipLaunchKernelGGL(k_single_records, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)chosen, (const uint32_t *)cpos, (const uint32_t *)uLo,
+                           (const uint32_t *)uHi, (const uint64_t *)dKeyB, dRec);
+        HIP_TRY(hipGetLastError());
+        rec.resize((size_t)nRec * 3);
+        HIP_TRY(hipMemcpyAsync(rec.data(), dRec, (size_t)nRec * 12, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+  }
+
+  // the linkage: the forest edges in rank order through a union-find, then rule 5's joins to leaf 0 (a cluster not yet joined when its
+  // smallest leaf k comes up: every smaller leaf is with leaf 0 by then)
+  std::vector<int32_t> up(V), id(V);
+  for (size_t i = 0; i < V; i++) { up[i] = (int32_t)i; id[i] = (int32_t)i; }
+  auto find = [&](int32_t x) { while (up[(size_t)x] != x) { up[(size_t)x] = up[(size_t)up[(size_t)x]]; x = up[(size_t)x]; } return x; };
+  size_t s = 0;
+  auto merge = [&](int32_t lo, int32_t hi, float d) {
+    const int32_t ra = find(lo), rb = find(hi);
+    if (ra == rb) return false;
+    const int32_t ia = id[(size_t)ra], ib = id[(size_t)rb];
+    children[2 * s] = ia < ib ? ia : ib; children[2 * s + 1] = ia < ib ? ib : ia;
+    height[s] = d;
+    if (edges) { edges[2 * s] = lo; edges[2 * s + 1] = hi; }
+    up[(size_t)rb] = ra; id[(size_t)ra] = (int32_t)(V + s);
+    s++;
+    return true;
+  };
+  for (size_t r = 0; r < rec.size(); r += 3) {
+    float d; memcpy(&d, &rec[r + 2], 4);
+    if (rec[r] >= V || rec[r + 1] >= V || !merge((int32_t)rec[r], (int32_t)rec[r + 1], d)) return fail(ANI_ERR_INTERNAL, "the forest edges hold a cycle");
+  }
+  for (size_t k = 1; k < V; k++) (void)merge(0, (int32_t)k, dMissing);
+  if (s != M) return fail(ANI_ERR_INTERNAL, "%zu merges over %d genomes", s, nG);
+  return ANI_OK;
+}
+
 // ---- whole-genome sketch ANI (ani_sketch_signatures, ani_signature_pairs) ----
 namespace {
 struct SigBufs {
@@ -1258,6 +1418,22 @@ int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes,
   HIP_TRY(hipSetDevice(ctx->device));
   return tree_nj(ctx, rows, n, nGenomes, missingIdentity, children, length);
 }
+
+int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *height,
+                    int32_t *edges)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
+  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the cluster ids of the tree take at most 2^30", nGenomes);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  if (nGenomes <= 1) return ANI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return tree_single(ctx, rows, n, nGenomes, missingIdentity, children, height, edges); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_tree_single_rounds(const ani_ctx *ctx) { return ctx ? ctx->treeSingleRounds : 0; }
 
 int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
 {

@@ -5,7 +5,8 @@
 // src/cgi/include/computeCoreIdentity.hpp:307-344, cgi::outputPhylip :353-448, cgi::outputVisualizationFile :103-153,
 // cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
 // (greedy species clusters over the .matrix cells, ani_cluster_greedy), `--tree` (extension) a .newick file (their average-linkage
-// tree, ani_tree_average, or with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj).  `--sketchANI` (extension) adds a .sketch
+// tree, ani_tree_average, with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj, or with `--treeMethod single` their
+// single-linkage tree and, in a .mst file, their minimum spanning tree, ani_tree_single).  `--sketchANI` (extension) adds a .sketch
 // file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
 // tree that estimate for the pairs without a .matrix cell.  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
@@ -68,6 +69,7 @@ struct Options {
   float cluster = 0.0f;                                // --cluster T: greedy clustering at w >= T (0 = off)
   bool tree = false;                                   // --tree: average-linkage tree of the .matrix cells
   bool treeNj = false;                                 // --treeMethod nj: their neighbour-joining tree instead
+  bool treeSingle = false;                             // --treeMethod single: their single-linkage tree instead, and the .mst file
   bool sketchANI = false, treeFill = false;            // --sketchANI: the .sketch file; --treeFill sketch: sketch estimates for the tree's missing pairs
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
   bool signatures() const { return sketchANI || treeFill; }
@@ -106,7 +108,10 @@ struct Options {
     "     --tree      also output the average-linkage (UPGMA) tree of the genomes over the distances 1 - ANI/100, a pair without\n"
     "                 ANI at distance 1 (.newick) [disabled by default]\n"
     "     --treeMethod <value>  the tree of --tree: average, or nj for the neighbour-joining tree (unrooted: three branches at the\n"
-    "                 top; branch lengths can be negative where the distances are not tree-like) [default : average]\n"
+    "                 top; branch lengths can be negative where the distances are not tree-like), or single for the single-linkage\n"
+    "                 tree, which takes any number of genomes and also writes the minimum spanning tree of the ANI graph (.mst: genome,\n"
+    "                 genome, ANI, ani or sketch for where the value comes from; one line per merge below distance 1, closest pair\n"
+    "                 first; the lines with ANI >= T are the connected components at T) [default : average]\n"
     "     --treeFill <value>  sketch: a pair without ANI enters the tree at the whole-genome sketch estimate (see --sketchANI) instead\n"
     "                 of distance 1, if the two sketches share anything; the queries must be among the references [default : none]\n"
     "     --sketchANI also output a Mash-style ANI estimate between the genomes, from the smallest minimizer hashes of each genome\n"
@@ -166,8 +171,9 @@ Options parse(int argc, char **argv)
     else if (a == "--cluster") { o.cluster = (float)atof(need(i));
       if (!(o.cluster > 0.0f && o.cluster <= 100.0f)) { std::cerr << "ERROR, --cluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "--tree") o.tree = true;
-    else if (a == "--treeMethod") { const std::string v = need(i); treeMethod = true; o.treeNj = v == "nj";
-      if (v != "average" && v != "nj") { std::cerr << "ERROR, --treeMethod takes average or nj" << std::endl; exit(1); } }
+    // (the refusal keeps its earlier wording in front: scripts and tests match on it)
+    else if (a == "--treeMethod") { const std::string v = need(i); treeMethod = true; o.treeNj = v == "nj"; o.treeSingle = v == "single";
+      if (v != "average" && v != "nj" && v != "single") { std::cerr << "ERROR, --treeMethod takes average or nj or single" << std::endl; exit(1); } }
     else if (a == "--treeFill") { const std::string v = need(i); treeFill = true; o.treeFill = v == "sketch";
       if (v != "none" && v != "sketch") { std::cerr << "ERROR, --treeFill takes none or sketch" << std::endl; exit(1); } }
     else if (a == "--sketchANI") o.sketchANI = true;
@@ -1287,14 +1293,10 @@ std::vector<ani_cgi_t> tree_rows(const MatrixCells &mc, const std::vector<Cell> 
   return rows;
 }
 
-void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
+// a linkage (children, height: scipy form) as newick
+void write_linkage(const std::string &path, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<float> &height)
 {
   const int n = (int)mc.names.size();
-  std::vector<ani_cgi_t> rows = tree_rows(mc, fill);
-  const size_t m = n > 1 ? (size_t)n - 1 : 0;
-  std::vector<int32_t> children(2 * m); std::vector<float> height(m);
-  if (ani_tree_average(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data())) die("ani_tree_average");
-  std::vector<ani_cgi_t>().swap(rows);
   BufferedFile f(path);
   auto h = [&](int node) { return node < n ? 0.0 : (double)height[(size_t)(node - n)]; };
   char len[64];
@@ -1315,7 +1317,56 @@ void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, co
   f.out << ";\n";
   f.out.close();
   if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
+}
+
+void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
+{
+  const int n = (int)mc.names.size();
+  std::vector<ani_cgi_t> rows = tree_rows(mc, fill);
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
+  std::vector<int32_t> children(2 * m); std::vector<float> height(m);
+  if (ani_tree_average(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data())) die("ani_tree_average");
+  std::vector<ani_cgi_t>().swap(rows);
+  write_linkage(path, mc, children, height);
   trace("tree written");
+}
+
+// ---- .newick with --treeMethod single: the single-linkage tree of the cells (ani_tree_single on the first device, a pair without cells at
+// identity 0), written like the average-linkage one; and .mst, the edges that caused its merges below distance 1 (the minimum spanning
+// forest of the cells), in merge order: genome, genome (the smaller .matrix index first), the pair's value as the .matrix folds and the
+// .clusters file prints it, and `ani` for a .matrix cell or `sketch` for a fill cell of --treeFill sketch.
+void write_tree_single(const std::string &path, const std::string &mstPath, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
+{
+  const int n = (int)mc.names.size();
+  std::vector<ani_cgi_t> rows = tree_rows(mc, fill);
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
+  std::vector<int32_t> children(2 * m), edges(2 * m); std::vector<float> height(m);
+  if (ani_tree_single(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data(), edges.data())) die("ani_tree_single");
+  std::vector<ani_cgi_t>().swap(rows);
+  write_linkage(path, mc, children, height);
+  trace("tree written");
+  // the forest edges' values: their cells folded in result order, as write_matrix folds them
+  struct Value { float w; bool sketch; };
+  std::unordered_map<uint64_t, Value> value;
+  size_t nForest = 0;
+  while (nForest < m && height[nForest] < 1.0f) nForest++;         // (heights do not fall)
+  auto key = [](int lo, int hi) { return ((uint64_t)(uint32_t)lo << 32) | (uint32_t)hi; };
+  for (size_t s = 0; s < nForest; s++) value.emplace(key(edges[2 * s], edges[2 * s + 1]), Value{0.0f, false});
+  for (const std::vector<Cell> *cells : {&mc.cells, &fill})
+    for (const Cell &c : *cells) {
+      const auto it = value.find(key(c.col, c.row));
+      if (it == value.end()) continue;
+      it->second.w = it->second.w > 0 ? (it->second.w + c.id) / 2 : c.id;
+      it->second.sketch = cells == &fill;
+    }
+  BufferedFile f(mstPath);
+  for (size_t s = 0; s < nForest; s++) {
+    const Value &v = value[key(edges[2 * s], edges[2 * s + 1])];
+    f.out << mc.names[(size_t)edges[2 * s]] << "\t" << mc.names[(size_t)edges[2 * s + 1]] << "\t" << std::to_string(v.w) << "\t" << (v.sketch ? "sketch" : "ani") << "\n";
+  }
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << mstPath << std::endl; exit(1); }
+  trace("spanning tree written");
 }
 
 // ---- .newick with --treeMethod nj: the neighbour-joining tree of the cells (ani_tree_nj on the first device, a pair without cells at
@@ -1526,7 +1577,8 @@ int main(int argc, char **argv)
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
   if (o.signatures()) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
-  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (both before write_matrix, which sorts the cells in place)
+  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)
+  else if (o.tree && o.treeSingle) write_tree_single(o.out + ".newick", o.out + ".mst", su.dev[0].ctx, mc, fill);
   else if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc, fill);
   if (o.matrix) write_matrix(o.out + ".matrix", mc);
   write_visual(o, res);

@@ -360,6 +360,35 @@ int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGen
 int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
                 int32_t *children, float *length);
 
+/* ---- single-linkage tree of the genomes and the minimum spanning tree of the pair graph (no counterpart in the reference; DESIGN.md
+ * section 2.15).  The one linkage that is a function of the pairs with rows alone: device memory is proportional to the rows plus the
+ * genomes, never to nGenomes^2, and there is no 65 536 ceiling.  The result depends on no reduction order and no schedule.
+ * 1. Rows and argument checks as for ani_tree_average: ids in ONE numbering [0, nGenomes), the rows of a pair folded in the order given
+ *    into w(i, j), self rows ignored, the same ANI_ERR_ARG cases.
+ * 2. Leaf distance, a float: dm = (float)(1 - (double)missingIdentity / 100); a pair with rows has
+ *    d = min((float)(1 - (double)w / 100), dm), a pair without rows d = dm.  The clamp is the one deliberate difference from
+ *    ani_tree_average: a pair with a row is never farther than a pair without.  At missingIdentity = 0 (the command line's) it changes
+ *    nothing.
+ * 3. The merges are Kruskal's over all nGenomes (nGenomes - 1) / 2 pairs in ascending order of (bits(d), lo, hi), lo < hi the leaf ids
+ *    (distances are >= 0, so their bit patterns order like their values): a pair whose leaves are already in one cluster is skipped,
+ *    every other pair is a merge.
+ * 4. Output in scipy linkage form, as for ani_tree_average: merge s = 0..nGenomes-2 creates cluster id nGenomes + s (a leaf's id is its
+ *    index); children[2s], children[2s + 1] are the ids of the two merged clusters, the smaller first; height[s] = d of the pair
+ *    (non-decreasing in s by construction); edges[2s] = lo and edges[2s + 1] = hi of the pair that caused merge s.  children and edges
+ *    hold 2 (nGenomes - 1) values, height nGenomes - 1; edges may be null.
+ * 5. A consequence of rule 3, and what lets the implementation stay sparse: at height dm every pair not yet joined is an edge and
+ *    (0, k) sorts first, so all merges at height dm are joins to leaf 0: each remaining cluster is joined to the cluster of leaf 0 in
+ *    ascending order of its smallest leaf k, with edges = (0, k).  The merges with bits(d) < bits(dm) are exactly the minimum spanning
+ *    forest of the pairs with rows under the strict total order (bits(d), lo, hi), so that forest is unique.
+ * 6. nGenomes <= 1: ANI_OK, nothing is read or written.  ANI_ERR_LIMIT: n > 2^32 - 16 rows, or nGenomes > 2^30 (cluster ids reach
+ *    2 nGenomes - 2 and are int32); ANI_ERR_NOMEM: the device cannot hold the buffers, 56 bytes per row at the peak plus 24 per genome.
+ *    All argument and limit checks run before any allocation.
+ * ani_tree_single_rounds: the spanning-forest rounds (Boruvka's, at most ceil(log2 nGenomes) + 1) the context's last ani_tree_single
+ * call took on the device; 0 if it needed none or there was no call (tools/tree_probe.py reports it). */
+int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                    int32_t *children, float *height, int32_t *edges);
+int ani_tree_single_rounds(const ani_ctx *ctx);
+
 /* ---- whole-genome sketch ANI: a Mash-style estimate between the reference genomes from the minimizers the sketch already holds (no
  * counterpart in the reference, which emits no row below about 80 % identity).  The smallest k-mer hashes of a
  * genome are almost always window minimizers, so the smallest distinct minimizer hashes of a genome stand in for its bottom-s MinHash

@@ -1,11 +1,16 @@
-"""Timings of ani_tree_average (average-linkage tree) and, with --method nj, of ani_tree_nj (neighbour joining,
-section 2.13) on synthetic row sets, on the GPU.  The call returns after its last device-to-host copy, so the wall clock around it
+"""Timings of ani_tree_average (average-linkage tree), with --method nj of ani_tree_nj (neighbour joining,
+section 2.13) and with --method single of ani_tree_single (single linkage / minimum spanning tree, section 2.15) on synthetic row sets,
+on the GPU.  The call returns after its last device-to-host copy, so the wall clock around it
 includes the upload, the matrix, every merge launch and the read-back.
 
     python tools/tree_probe.py                 the row sets below, 1 warm-up + 3 timed calls each (median reported)
     python tools/tree_probe.py --only hub      only the row sets whose name starts with that (e.g. under rocprofv3)
     python tools/tree_probe.py --method nj     ani_tree_nj on the same row sets, with the bytes its scans read by its own model
                                                (nj_scan_bytes) and the rate that makes of the median
+    python tools/tree_probe.py --method single ani_tree_single on the same row sets and on "species 150000" (above the dense trees'
+                                               ceiling), with its spanning-forest rounds, and ani_cluster_greedy at 95 on the same rows
+                                               as the yardstick: both calls upload, sort and fold the rows, so the difference is
+                                               what the forest stage costs
     python tools/tree_probe.py --reps 1        timed calls per row set (default 3)
     python tools/tree_probe.py --cli 1000      in addition: fastANI --ql L --rl L --tree on that many 5 Mbp genomes, the
                                                ANI_CLI_TRACE marks of the run ("rows ordered" -> "tree written" is the tree's share)
@@ -16,6 +21,7 @@ Row sets (identities from cluster_probe.species_rows: species of 50, ANI >= 95 i
     species 65536    4 * 10^6 rows over 65 536 genomes (the largest tree: a 17 GB matrix)
     path 2000        an ordered path of 2 000 genomes, every other pair missing
     hub 2000         genome 0 close to all 1 999 others, which are far from each other: the first merge rescans every row
+    species 150000   10^7 rows over 150 000 genomes (--method single only)
 """
 import ctypes
 import os
@@ -90,6 +96,35 @@ def time_call(e, rows, n, reps=3, method="average"):
     return ms, float(height[n - 2])
 
 
+def time_single(e, rows, n, reps=3):
+    """-> (ms of ani_tree_single, rounds, forest edges, ms of ani_cluster_greedy at 95 on the same rows)"""
+    children = np.empty(2 * (n - 1), dtype=np.int32)
+    height = np.empty(n - 1, dtype=np.float32)
+    edges = np.empty(2 * (n - 1), dtype=np.int32)
+    rep = np.empty(n, dtype=np.int32)
+    ident = np.empty(n, dtype=np.float32)
+
+    def single():
+        rc = e.lib.ani_tree_single(e.h, rows.ctypes.data, len(rows), n, ctypes.c_float(0.0), children.ctypes.data, height.ctypes.data, edges.ctypes.data)
+        assert rc == 0, rc
+
+    def greedy():
+        rc = e.lib.ani_cluster_greedy(e.h, rows.ctypes.data, len(rows), n, ctypes.c_float(95.0), rep.ctypes.data, ident.ctypes.data)
+        assert rc == 0, rc
+    out = []
+    for call in (single, greedy):
+        call()                                                     # warm-up: code objects, pool segments, page-locked staging
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        out.append(ms)
+    single()                                                       # (the rounds are those of the context's last ani_tree_single call)
+    assert (np.diff(height) >= 0).all()
+    return out[0], e.tree_single_rounds(), int((height < 1.0).sum()), out[1]
+
+
 def cli_run(n):
     import bench
     import orc
@@ -128,11 +163,22 @@ def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     method = sys.argv[sys.argv.index("--method") + 1] if "--method" in sys.argv else "average"
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
-    assert method in ("average", "nj"), method
+    assert method in ("average", "nj", "single"), method
+    if method == "single":
+        sets.append(("species 150000", lambda: species_rows(rng, 150000, 10 ** 7), 150000))
     for name, make, n in sets:
         if not name.startswith(only):
             continue
         rows = make()
+        if method == "single":
+            ms, rounds, forest, greedy_ms = time_single(e, rows, n, reps)
+            med, gmed = float(np.median(ms)), float(np.median(greedy_ms))
+            print("%-14s rows %9d genomes %6d   ani_tree_single %s ms (median %.2f)   %d rounds, %d forest edges   ani_cluster_greedy(95) %s ms "
+                  "(median %.2f)   difference %.2f ms"
+                  % (name, len(rows), n, " ".join("%.2f" % x for x in ms), med, rounds, forest, " ".join("%.2f" % x for x in greedy_ms), gmed, med - gmed),
+                  flush=True)
+            del rows
+            continue
         ms, top = time_call(e, rows, n, reps, method)
         if method == "nj":
             med = float(np.median(ms))
