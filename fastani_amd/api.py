@@ -11,6 +11,8 @@
                                            spanning tree; memory follows the rows, no genome ceiling (no reference counterpart)
     Sketch.signatures(size)                bottom-`size` signatures of the reference genomes from their minimizers (no reference counterpart)
     Engine.signature_pairs(sig, len, k)    Mash-style ANI estimate between all pairs of signatures (no reference counterpart)
+    Engine.tree_single_sketch(rows, n, sig, len, k)  tree_single with that estimate for every pair without rows, streamed strip by
+                                           strip: nothing of size n^2 anywhere, no genome ceiling (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -127,6 +129,8 @@ def _bind(lib):
         "ani_tree_nj": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
         "ani_tree_single": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp, vp]),
         "ani_tree_single_rounds": (C.c_int, [vp]),
+        "ani_tree_single_sketch": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+        "ani_tree_single_sketch_strips": (C.c_int, [vp, vp, C.c_size_t]),
         "ani_sketch_signatures": (C.c_int, [vp, C.c_int32, vp, vp]),
         "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     }
@@ -444,6 +448,13 @@ class Engine:
         self._chk(self.lib.ani_tree_single(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
                                            children.ctypes.data if m else None, height.ctypes.data if m else None,
                                            edges.ctypes.data if m and return_edges else None))
+        z = self._linkage(children, height, n_genomes)
+        return (z, edges.reshape(m, 2).astype(np.int64)) if return_edges else z
+
+    @staticmethod
+    def _linkage(children, height, n_genomes):
+        """children and height of a single-linkage call -> the scipy linkage matrix (the fourth column counts the leaves)"""
+        m = max(n_genomes - 1, 0)
         z = np.empty((m, 4), dtype=np.float64)
         z[:, 0:2] = children.reshape(m, 2)
         z[:, 2] = height
@@ -451,7 +462,43 @@ class Engine:
         for s, (x, y) in enumerate(children.reshape(m, 2).tolist()):
             count[n_genomes + s] = count[x] + count[y]
         z[:, 3] = count[n_genomes:]
-        return (z, edges.reshape(m, 2).astype(np.int64)) if return_edges else z
+        return z
+
+    def tree_single_sketch(self, rows, n_genomes, sig, length, kmer_size, min_shared=1, missing_identity=0.0, return_edges=False, return_source=False):
+        """tree_single over `rows` plus, for every pair without rows, the sketch estimate signature_pairs(sig, length, kmer_size,
+        min_shared) gives it if that is above 0 (ani_tree_single_sketch; the semantics are in ani_abi.h).  The sketch pairs are streamed
+        through the device a strip at a time, so nothing of size n_genomes ** 2 exists anywhere and there is no 65 536 ceiling.
+        -> the scipy linkage matrix as tree_single builds it; with return_edges also `edges`, int64 (n_genomes - 1, 2); with
+        return_source also `source`, uint8 (n_genomes - 1,): 0 a pair with rows, 1 a sketch pair, 2 a join to leaf 0."""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        sig = np.ascontiguousarray(sig, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n_genomes = int(n_genomes)
+        if sig.ndim != 2 or length.shape != (sig.shape[0],) or sig.shape[0] != max(n_genomes, 0):
+            raise ValueError("sig must be (n_genomes, size) and length (n_genomes,)")
+        m = max(n_genomes - 1, 0)
+        children = np.empty(2 * m, dtype=np.int32)
+        height = np.empty(m, dtype=np.float32)
+        edges = np.empty(2 * m, dtype=np.int32)
+        source = np.empty(m, dtype=np.uint8)
+        self._chk(self.lib.ani_tree_single_sketch(self.h, rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
+                                                  sig.ctypes.data if sig.size else None, length.ctypes.data if len(length) else None, sig.shape[1],
+                                                  int(kmer_size), int(min_shared), children.ctypes.data if m else None, height.ctypes.data if m else None,
+                                                  edges.ctypes.data if m and return_edges else None, source.ctypes.data if m and return_source else None))
+        out = (self._linkage(children, height, n_genomes),)
+        if return_edges:
+            out += (edges.reshape(m, 2).astype(np.int64),)
+        if return_source:
+            out += (source,)
+        return out if len(out) > 1 else out[0]
+
+    def tree_single_sketch_strips(self):
+        """edges each strip of the last tree_single_sketch call of this engine added to its fold (ani_tree_single_sketch_strips)"""
+        n = int(self.lib.ani_tree_single_sketch_strips(self.h, None, 0))
+        out = np.zeros(n, dtype=np.uint64)
+        if n:
+            self.lib.ani_tree_single_sketch_strips(self.h, out.ctypes.data, n)
+        return out
 
     def tree_single_rounds(self):
         """spanning-forest rounds the last tree_single call of this engine took on the device (ani_tree_single_rounds)"""

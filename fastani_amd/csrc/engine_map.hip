@@ -17,6 +17,7 @@
 #include "kernels/nj.hpp"
 #include "kernels/single.hpp"
 #include "kernels/sigdist.hpp"
+#include "kernels/sigstrip.hpp"
 
 namespace anih {
 using namespace ani;
@@ -850,173 +851,269 @@ int tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float mis
 
 // ---- single-linkage tree = minimum spanning forest of the pairs with rows (ani_tree_single) ----
 // Device memory per row: 20 (rows) + 2 x 12 (keys and positions) + 12 (the sort's ping-pong) = 56 bytes during the first sort, then
-// 20 + 12 + 4 (edge positions) per row and 20 per edge while the edges are compacted; per edge 44 during the second sort and 32 during the
-// rounds; per genome 12 (component, hook, best edge) and 12 per forest edge of the result.  Nothing is proportional to nGenomes^2.
+// 20 + 12 + 4 (edge positions) per row and 20 per edge while the edges are compacted; per edge 44 during the second sort and 33 during the
+// rounds; per genome 12 (component, hook, best edge) and 13 per forest edge of the result.  Nothing is proportional to nGenomes^2.
 // One count is read back per round (the live edges), which also bounds the loop; every buffer is the pool's and goes back on return.
-int tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height, int32_t *edges)
+// The pieces are shared with ani_tree_single_sketch (section 2.16), which folds further edges into the forest strip by strip.
+namespace {
+// edges on the device, every buffer the pool's: (lo, hi)-ordered with their sort input (dKey, idx), or ranked (lo, hi, d, src by rank)
+struct SingleEdges {
+  DevBuf lo, hi, dKey, idx, d, src; uint32_t n = 0;
+  SingleEdges() = default; SingleEdges(const SingleEdges &) = delete;
+  ~SingleEdges() { release(); }
+  void release() { for (DevBuf *x : {&lo, &hi, &dKey, &idx, &d, &src}) x->release(); n = 0; }
+  void swap(SingleEdges &o) { std::swap(lo, o.lo); std::swap(hi, o.hi); std::swap(dKey, o.dKey); std::swap(idx, o.idx); std::swap(d, o.d); std::swap(src, o.src); std::swap(n, o.n); }
+  ani::SingleList list() const { return ani::SingleList{lo.as<uint32_t>(), hi.as<uint32_t>(), d.as<uint32_t>(), src.as<uint8_t>(), n}; }
+};
+struct DevBufs {
+  std::vector<DevBuf> b;
+  explicit DevBufs(size_t n) : b(n) {}
+  DevBufs(const DevBufs &) = delete;
+  ~DevBufs() { for (DevBuf &x : b) x.release(); }
+  int get(int i, size_t bytes, void **out) { const int rc = b[(size_t)i].ensure(bytes ? bytes : 1); *out = b[(size_t)i].p; return rc; }
+};
+inline int id_bits(int32_t nG) { int b = 1; while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++; return b; }   // bit width of the largest id
+}  // namespace
+
+// The front half: the rows are uploaded and checked, the stable sort puts the rows of a pair next to each other in the order given, and
+// the pairs below d_missing come out as edges in (lo, hi) order with the input of the sort by distance.  pairKeys (may be null): the
+// sorted distinct keys lo << b | hi of every non-self pair with rows, whatever its distance.
+static int single_front(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, uint32_t dmBits, SingleEdges *edges, DevBuf *pairKeys, uint32_t *nKeys)
 {
-  const size_t V = (size_t)nG, M = V - 1;
-  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
-  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
-  std::vector<uint32_t> rec;                                       // the forest edges in rank order: lo, hi, bits(d)
-  ctx->treeSingleRounds = 0;
+  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, FLAG, POS, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const int b = id_bits(nG);
+  edges->n = 0;
+  if (nKeys) *nKeys = 0;
+  if (!n) return ANI_OK;
+  // flags: [0] a bad id (1) or identity (2)
+  uint32_t *flags, *host = nullptr;
+  TRY(B.get(FLAGS, 64, (void **)&flags));
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
 
-  if (n) {
-    enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, FLAG, POS, E_LO, E_HI, DKEY_A, DKEY_B, IDX_A, IDX_B, U_LO, U_HI, CHOSEN, LIVE_A, LIVE_B,
-           COMP, PAR, BEST, REC, NBUF };
-    struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
-    auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
-    hipStream_t st = ctx->stream;
-    int b = 1;
-    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
-    // flags: [0] a bad id (1) or identity (2), [1] the live edges of a round, [2] a hook path that did not end
-    uint32_t *flags, *host = nullptr;
-    TRY(buf(FLAGS, 64, (void **)&flags));
-    TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-    HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-
-    // the pair values: keys and the stable sort as for the clustering
-    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
-    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
-    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
-    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
-    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+  // the pair values: keys and the stable sort as for the clustering
+  ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
+  TRY(B.get(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(B.get(KEYS_A, n * 8, (void **)&keysA)); TRY(B.get(KEYS_B, n * 8, (void **)&keysB));
+  TRY(B.get(VALS_A, n * 4, (void **)&valsA)); TRY(B.get(VALS_B, n * 4, (void **)&valsB));
+  HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
+  hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
+  if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
+  if (dmBits == 0) return ANI_OK;                                  // (d_missing = 0: no pair lies below it, and nothing is left to mask)
+  size_t tb = 0;
+  int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
+  void *sortTmp = nullptr;
+  if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
+  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
+  for (int i : {SORT, KEYS_A, VALS_A}) B.b[(size_t)i].release();
+  int32_t *flag; uint32_t *pos;
+  TRY(B.get(FLAG, n * 4, (void **)&flag)); TRY(B.get(POS, n * 4, (void **)&pos));
+  if (pairKeys) {
+    hipLaunchKernelGGL(k_single_keyflag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (uint64_t)n, b, flag);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
-    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
-    uint64_t nE64 = 0;
-    uint32_t *pos = nullptr;
-    if (dmBits != 0) {                                             // (d_missing = 0: no pair lies below it)
-      size_t tb = 0;
-      int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
-      void *sortTmp = nullptr;
-      if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
-      if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
-      for (int i : {SORT, KEYS_A, VALS_A}) B.b[i].release();
-      // the edges (pairs below d_missing), compacted in (lo, hi) order
-      int32_t *flag;
-      TRY(buf(FLAG, n * 4, (void **)&flag)); TRY(buf(POS, n * 4, (void **)&pos));
-      hipLaunchKernelGGL(k_single_flag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                         (uint64_t)n, b, dmBits, flag);
-      HIP_TRY(hipGetLastError());
-      TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nE64));
-      B.b[FLAG].release();
-    }
-    const uint32_t nE = (uint32_t)nE64;
-    if (nE) {
-      uint32_t *eLo, *eHi, *idxA, *idxB; uint64_t *dKeyA, *dKeyB;
-      TRY(buf(E_LO, (size_t)nE * 4, (void **)&eLo)); TRY(buf(E_HI, (size_t)nE * 4, (void **)&eHi));
-      TRY(buf(DKEY_A, (size_t)nE * 8, (void **)&dKeyA)); TRY(buf(IDX_A, (size_t)nE * 4, (void **)&idxA));
-      hipLaunchKernelGGL(k_single_pairs, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                         (uint64_t)n, b, dmBits, (const uint32_t *)pos, eLo, eHi, dKeyA, idxA);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(st));
-      for (int i : {ROWS, KEYS_B, VALS_B, POS}) B.b[i].release();
-      // rule 3's order: a stable sort over the bits of d leaves equal distances in (lo, hi) order; an edge's position is its rank
-      TRY(buf(DKEY_B, (size_t)nE * 8, (void **)&dKeyB)); TRY(buf(IDX_B, (size_t)nE * 4, (void **)&idxB));
-      size_t tb = 0;
-      int rc = ani_sort_pairs_u64_u32(dKeyA, dKeyB, idxA, idxB, nE, 32, nullptr, &tb, st);
-      void *sortTmp = nullptr;
-      if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(dKeyA, dKeyB, idxA, idxB, nE, 32, sortTmp, &tb, st); }
-      if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair distances failed (%d)", rc);
-      for (int i : {SORT, DKEY_A, IDX_A}) B.b[i].release();
-      uint32_t *uLo, *uHi, *live[2], *comp, *par, *best; int32_t *chosen;
-      TRY(buf(U_LO, (size_t)nE * 4, (void **)&uLo)); TRY(buf(U_HI, (size_t)nE * 4, (void **)&uHi)); TRY(buf(CHOSEN, (size_t)nE * 4, (void **)&chosen));
-      hipLaunchKernelGGL(k_single_rank, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const uint32_t *)idxB, (const uint32_t *)eLo, (const uint32_t *)eHi,
-                         uLo, uHi, chosen);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(st));
-      for (int i : {E_LO, E_HI, IDX_B}) B.b[i].release();
-
-      // Boruvka rounds over the ranked edges.  A round in which e edges join two components hooks every component that has one, so the
-      // components with edges at least halve: ceil(log2 V) rounds with live edges, and one more that finds none.
-      TRY(buf(LIVE_A, (size_t)nE * 4, (void **)&live[0])); TRY(buf(LIVE_B, (size_t)nE * 4, (void **)&live[1]));
-      TRY(buf(COMP, V * 4, (void **)&comp)); TRY(buf(PAR, V * 4, (void **)&par)); TRY(buf(BEST, V * 4, (void **)&best));
-      const unsigned gridV = grid_for(V);
-      hipLaunchKernelGGL(k_single_init, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, best);
-      HIP_TRY(hipGetLastError());
-      const int maxRounds = b + 3;
-      const uint32_t *liveIn = nullptr; uint32_t nLive = nE;
-      for (int round = 0; nLive; round++) {
-        if (round >= maxRounds) return fail(ANI_ERR_INTERNAL, "the spanning forest did not converge after %d rounds", round);
-        uint32_t *liveOut = live[round & 1];
-        HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
-        hipLaunchKernelGGL(k_single_best, dim3(grid_for(nLive)), dim3(256), 0, st, liveIn, nLive, (const uint32_t *)uLo, (const uint32_t *)uHi,
-                           (const uint32_t *)comp, best, liveOut, flags + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, flags + 1, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (host[1]) return fail(ANI_ERR_INTERNAL, "the hooks of round %d hold a cycle", round - 1);
-        if (host[0] > nLive) return fail(ANI_ERR_INTERNAL, "the live edges grew from %u to %u", nLive, host[0]);
-        ctx->treeSingleRounds = round + 1;
-        liveIn = liveOut; nLive = host[0];
-        if (!nLive) break;
-        hipLaunchKernelGGL(k_single_hook, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, (const uint32_t *)best, (const uint32_t *)uLo,
-                           (const uint32_t *)uHi, par, chosen);
-        hipLaunchKernelGGL(k_single_jump, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, par, flags + 2);
-        hipLaunchKernelGGL(k_single_label, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, (const uint32_t *)par, best);
-        HIP_TRY(hipGetLastError());
-      }
-      for (int i : {LIVE_A, LIVE_B}) B.b[i].release();
-
-      // the chosen edges, compacted in rank order
-      uint32_t *cpos, *dRec;
-      TRY(buf(POS, (size_t)nE * 4, (void **)&cpos));
-      uint64_t nRec = 0;
-      TRY(device_scan(ctx, chosen, cpos, nE, &nRec));
-      if (nRec > M) return fail(ANI_ERR_INTERNAL, "%llu forest edges over %d genomes", (unsigned long long)nRec, nG);
-      if (nRec) {
-        TRY(buf(REC, (size_t)nRec * 12, (void **)&dRec));
-        hipLaunchKernelGGL(k_single_records, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)chosen, (const uint32_t *)cpos, (const uint32_t *)uLo,
-                           (const uint32_t *)uHi, (const uint64_t *)dKeyB, dRec);
-        HIP_TRY(hipGetLastError());
-        rec.resize((size_t)nRec * 3);
-        HIP_TRY(hipMemcpyAsync(rec.data(), dRec, (size_t)nRec * 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-    }
+    uint64_t nK = 0;
+    TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nK));
+    TRY(pairKeys->ensure(nK ? (size_t)nK * 8 : 8));
+    hipLaunchKernelGGL(k_single_keys, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (uint64_t)n, (const int32_t *)flag, (const uint32_t *)pos,
+                       pairKeys->as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    *nKeys = (uint32_t)nK;
   }
+  // the edges (pairs below d_missing), compacted in (lo, hi) order
+  hipLaunchKernelGGL(k_single_flag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                     (uint64_t)n, b, dmBits, flag);
+  HIP_TRY(hipGetLastError());
+  uint64_t nE64 = 0;
+  TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nE64));
+  B.b[FLAG].release();
+  const uint32_t nE = (uint32_t)nE64;
+  if (!nE) { HIP_TRY(hipStreamSynchronize(st)); return ANI_OK; }
+  TRY(edges->lo.ensure((size_t)nE * 4)); TRY(edges->hi.ensure((size_t)nE * 4)); TRY(edges->dKey.ensure((size_t)nE * 8)); TRY(edges->idx.ensure((size_t)nE * 4));
+  hipLaunchKernelGGL(k_single_pairs, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
+                     (uint64_t)n, b, dmBits, (const uint32_t *)pos, edges->lo.as<uint32_t>(), edges->hi.as<uint32_t>(), edges->dKey.as<uint64_t>(),
+                     edges->idx.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  edges->n = nE;
+  return ANI_OK;
+}
 
-  // the linkage: the forest edges in rank order through a union-find, then rule 5's joins to leaf 0 (a cluster not yet joined when its
-  // smallest leaf k comes up: every smaller leaf is with leaf 0 by then)
+// Rule 3's order: a stable sort over the bits of d leaves equal distances in (lo, hi) order, so an edge's position is its rank.  Takes
+// edges in (lo, hi) order (lo, hi, dKey, idx) and leaves them ranked (lo, hi, d, src), every one with the source byte given.
+static int single_rank(ani_ctx *ctx, SingleEdges *e, uint8_t source)
+{
+  if (!e->n) return ANI_OK;
+  hipStream_t st = ctx->stream;
+  const size_t nE = e->n;
+  enum { DKEY_B, IDX_B, SORT, NBUF };
+  DevBufs B(NBUF);
+  uint64_t *dKeyB; uint32_t *idxB;
+  TRY(B.get(DKEY_B, nE * 8, (void **)&dKeyB)); TRY(B.get(IDX_B, nE * 4, (void **)&idxB));
+  size_t tb = 0;
+  int rc = ani_sort_pairs_u64_u32(e->dKey.as<uint64_t>(), dKeyB, e->idx.as<uint32_t>(), idxB, nE, 32, nullptr, &tb, st);
+  void *sortTmp = nullptr;
+  if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(e->dKey.as<uint64_t>(), dKeyB, e->idx.as<uint32_t>(), idxB, nE, 32, sortTmp, &tb, st); }
+  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair distances failed (%d)", rc);
+  B.b[SORT].release(); e->dKey.release(); e->idx.release();
+  SingleEdges r;
+  TRY(r.lo.ensure(nE * 4)); TRY(r.hi.ensure(nE * 4)); TRY(r.d.ensure(nE * 4)); TRY(r.src.ensure(nE));
+  const ani::SingleList out = r.list();                            // (the launches take plain pointers, never the holder)
+  hipLaunchKernelGGL(k_single_rank, dim3(grid_for(nE)), dim3(256), 0, st, (uint32_t)nE, (const uint32_t *)idxB, (const uint32_t *)e->lo.as<uint32_t>(),
+                     (const uint32_t *)e->hi.as<uint32_t>(), (const uint64_t *)dKeyB, source, (uint32_t *)out.lo, (uint32_t *)out.hi, (uint32_t *)out.d,
+                     (uint8_t *)out.src);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  r.n = (uint32_t)nE;
+  e->swap(r);
+  return ANI_OK;
+}
+
+// Two ranked lists that share no edge -> one, in `x`; `y` is emptied.
+static int single_merge(ani_ctx *ctx, SingleEdges *x, SingleEdges *y)
+{
+  if (!y->n) return ANI_OK;
+  if (!x->n) { x->swap(*y); y->release(); return ANI_OK; }
+  const uint64_t nE = (uint64_t)x->n + y->n;
+  if (nE > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%llu edges in one fold: the forest stage takes fewer than 2^32 - 16", (unsigned long long)nE);
+  SingleEdges r;
+  TRY(r.lo.ensure((size_t)nE * 4)); TRY(r.hi.ensure((size_t)nE * 4)); TRY(r.d.ensure((size_t)nE * 4)); TRY(r.src.ensure((size_t)nE));
+  const ani::SingleList out = r.list();
+  hipLaunchKernelGGL(k_single_merge, dim3(grid_for((size_t)nE)), dim3(256), 0, ctx->stream, x->list(), y->list(), (uint32_t *)out.lo, (uint32_t *)out.hi,
+                     (uint32_t *)out.d, (uint8_t *)out.src);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  r.n = (uint32_t)nE;
+  x->swap(r);
+  y->release();
+  return ANI_OK;
+}
+
+// The forest stage: Boruvka rounds over a ranked edge list; the chosen edges stay, in rank order (a ranked list again).  A round in
+// which e edges join two components hooks every component that has one, so the components with edges at least halve: ceil(log2 V) rounds
+// with live edges, and one more that finds none.  The rounds are added to ctx->treeSingleRounds.
+static int single_forest(ani_ctx *ctx, int32_t nG, SingleEdges *e)
+{
+  if (!e->n) return ANI_OK;
+  enum { FLAGS, CHOSEN, LIVE_A, LIVE_B, COMP, PAR, BEST, POS, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG;
+  const uint32_t nE = e->n;
+  const int b = id_bits(nG);
+  // flags: [1] the live edges of a round, [2] a hook path that did not end
+  uint32_t *flags, *host = nullptr;
+  TRY(B.get(FLAGS, 64, (void **)&flags));
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
+  const uint32_t *uLo = e->lo.as<uint32_t>(), *uHi = e->hi.as<uint32_t>();
+  uint32_t *live[2], *comp, *par, *best; int32_t *chosen;
+  TRY(B.get(CHOSEN, (size_t)nE * 4, (void **)&chosen));
+  TRY(B.get(LIVE_A, (size_t)nE * 4, (void **)&live[0])); TRY(B.get(LIVE_B, (size_t)nE * 4, (void **)&live[1]));
+  TRY(B.get(COMP, V * 4, (void **)&comp)); TRY(B.get(PAR, V * 4, (void **)&par)); TRY(B.get(BEST, V * 4, (void **)&best));
+  HIP_TRY(hipMemsetAsync(chosen, 0, (size_t)nE * 4, st));
+  const unsigned gridV = grid_for(V);
+  hipLaunchKernelGGL(k_single_init, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, best);
+  HIP_TRY(hipGetLastError());
+  const int maxRounds = b + 3;
+  const uint32_t *liveIn = nullptr; uint32_t nLive = nE;
+  for (int round = 0; nLive; round++) {
+    if (round >= maxRounds) return fail(ANI_ERR_INTERNAL, "the spanning forest did not converge after %d rounds", round);
+    uint32_t *liveOut = live[round & 1];
+    HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
+    hipLaunchKernelGGL(k_single_best, dim3(grid_for(nLive)), dim3(256), 0, st, liveIn, nLive, uLo, uHi, (const uint32_t *)comp, best, liveOut, flags + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, flags + 1, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (host[1]) return fail(ANI_ERR_INTERNAL, "the hooks of round %d hold a cycle", round - 1);
+    if (host[0] > nLive) return fail(ANI_ERR_INTERNAL, "the live edges grew from %u to %u", nLive, host[0]);
+    ctx->treeSingleRounds++;
+    liveIn = liveOut; nLive = host[0];
+    if (!nLive) break;
+    hipLaunchKernelGGL(k_single_hook, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, (const uint32_t *)best, uLo, uHi, par, chosen);
+    hipLaunchKernelGGL(k_single_jump, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, par, flags + 2);
+    hipLaunchKernelGGL(k_single_label, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, (const uint32_t *)par, best);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int i : {LIVE_A, LIVE_B, COMP, PAR, BEST}) B.b[(size_t)i].release();
+
+  // the chosen edges, compacted in rank order
+  uint32_t *cpos;
+  TRY(B.get(POS, (size_t)nE * 4, (void **)&cpos));
+  uint64_t nRec = 0;
+  TRY(device_scan(ctx, chosen, cpos, nE, &nRec));
+  if (nRec > V - 1) return fail(ANI_ERR_INTERNAL, "%llu forest edges over %d genomes", (unsigned long long)nRec, nG);
+  SingleEdges f;
+  if (nRec) {
+    TRY(f.lo.ensure((size_t)nRec * 4)); TRY(f.hi.ensure((size_t)nRec * 4)); TRY(f.d.ensure((size_t)nRec * 4)); TRY(f.src.ensure((size_t)nRec));
+    const ani::SingleList out = f.list();
+    hipLaunchKernelGGL(k_single_records, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)chosen, (const uint32_t *)cpos, uLo, uHi,
+                       (const uint32_t *)e->d.as<uint32_t>(), (const uint8_t *)e->src.as<uint8_t>(), (uint32_t *)out.lo, (uint32_t *)out.hi, (uint32_t *)out.d,
+                       (uint8_t *)out.src);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    f.n = (uint32_t)nRec;
+  }
+  e->swap(f);
+  return ANI_OK;
+}
+
+// The linkage: the forest edges (brought back from the device) in rank order through a union-find, then rule 5's joins to leaf 0 (a
+// cluster not yet joined when its smallest leaf k comes up: every smaller leaf is with leaf 0 by then).  source (may be null): per merge
+// the forest edge's source byte, 2 for a join to leaf 0.
+static int single_finish(ani_ctx *ctx, const SingleEdges &forest, int32_t nG, float dMissing, int32_t *children, float *height, int32_t *edges, uint8_t *source)
+{
+  const size_t V = (size_t)nG, M = V - 1, nF = forest.n;
+  std::vector<uint32_t> lo(nF), hi(nF), dist(nF); std::vector<uint8_t> src(nF);
+  if (nF) {
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(lo.data(), forest.lo.p, nF * 4, hipMemcpyDeviceToHost, st)); HIP_TRY(hipMemcpyAsync(hi.data(), forest.hi.p, nF * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dist.data(), forest.d.p, nF * 4, hipMemcpyDeviceToHost, st)); HIP_TRY(hipMemcpyAsync(src.data(), forest.src.p, nF, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
   std::vector<int32_t> up(V), id(V);
   for (size_t i = 0; i < V; i++) { up[i] = (int32_t)i; id[i] = (int32_t)i; }
   auto find = [&](int32_t x) { while (up[(size_t)x] != x) { up[(size_t)x] = up[(size_t)up[(size_t)x]]; x = up[(size_t)x]; } return x; };
   size_t s = 0;
-  auto merge = [&](int32_t lo, int32_t hi, float d) {
-    const int32_t ra = find(lo), rb = find(hi);
+  auto merge = [&](int32_t a, int32_t c, float d, uint8_t from) {
+    const int32_t ra = find(a), rb = find(c);
     if (ra == rb) return false;
     const int32_t ia = id[(size_t)ra], ib = id[(size_t)rb];
     children[2 * s] = ia < ib ? ia : ib; children[2 * s + 1] = ia < ib ? ib : ia;
     height[s] = d;
-    if (edges) { edges[2 * s] = lo; edges[2 * s + 1] = hi; }
+    if (edges) { edges[2 * s] = a; edges[2 * s + 1] = c; }
+    if (source) source[s] = from;
     up[(size_t)rb] = ra; id[(size_t)ra] = (int32_t)(V + s);
     s++;
     return true;
   };
-  for (size_t r = 0; r < rec.size(); r += 3) {
-    float d; memcpy(&d, &rec[r + 2], 4);
-    if (rec[r] >= V || rec[r + 1] >= V || !merge((int32_t)rec[r], (int32_t)rec[r + 1], d)) return fail(ANI_ERR_INTERNAL, "the forest edges hold a cycle");
+  for (size_t r = 0; r < nF; r++) {
+    float d; memcpy(&d, &dist[r], 4);
+    if (lo[r] >= V || hi[r] >= V || !merge((int32_t)lo[r], (int32_t)hi[r], d, src[r])) return fail(ANI_ERR_INTERNAL, "the forest edges hold a cycle");
   }
-  for (size_t k = 1; k < V; k++) (void)merge(0, (int32_t)k, dMissing);
+  for (size_t k = 1; k < V; k++) (void)merge(0, (int32_t)k, dMissing, 2);
   if (s != M) return fail(ANI_ERR_INTERNAL, "%zu merges over %d genomes", s, nG);
   return ANI_OK;
 }
 
-// ---- whole-genome sketch ANI (ani_sketch_signatures, ani_signature_pairs; DESIGN.md section 2.14) ----
-namespace {
-struct SigBufs {
-  std::vector<DevBuf> b;
-  explicit SigBufs(size_t n) : b(n) {}
-  SigBufs(const SigBufs &) = delete;
-  ~SigBufs() { for (DevBuf &x : b) x.release(); }
-  int get(int i, size_t bytes, void **out) { const int rc = b[(size_t)i].ensure(bytes ? bytes : 1); *out = b[(size_t)i].p; return rc; }
-};
-}  // namespace
+int tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height, int32_t *edges)
+{
+  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
+  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
+  ctx->treeSingleRounds = 0;
+  SingleEdges e;
+  TRY(single_front(ctx, rows, n, nG, dmBits, &e, nullptr, nullptr));
+  TRY(single_rank(ctx, &e, 0));
+  TRY(single_forest(ctx, nG, &e));
+  return single_finish(ctx, e, nG, dMissing, children, height, edges, nullptr);
+}
 
+// ---- whole-genome sketch ANI (ani_sketch_signatures, ani_signature_pairs; DESIGN.md section 2.14) ----
 // Per index chunk, from whichever form of its records is at hand (the index arrays of a resident chunk, else the 12-byte records a
 // streamed set keeps: nothing is rebuilt).  Round 1 keeps the records at or below a per-genome hash threshold that lets about
 // 2 size + 64 k-mers of the genome through (a k-mer that small is a window minimizer almost surely), sorts those few keys and numbers
@@ -1026,7 +1123,7 @@ struct SigBufs {
 int sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
 {
   enum { THR, CNT, OFF, KEYS_A, KEYS_B, SORT, SIG, LEN, NBUF };
-  SigBufs B(NBUF);
+  DevBufs B(NBUF);
   ani_ctx *ctx = sk->ctx;
   hipStream_t st = ctx->stream;
   const int64_t kAll = 0xffffffffll;
@@ -1127,7 +1224,7 @@ int signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32
                     ani_sigpair_t **rows, size_t *n)
 {
   enum { RAW, LEN, SIG, FLAGS, MAT, CNT, OFF, OUT, NBUF };
-  SigBufs B(NBUF);
+  DevBufs B(NBUF);
   hipStream_t st = ctx->stream;
   const size_t V = (size_t)nG;
   const int32_t pitch = (size + 3) & ~3;
@@ -1181,6 +1278,112 @@ int signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32
   guard.p = nullptr;
   *rows = out; *n = (size_t)total;
   return ANI_OK;
+}
+
+// the strip tiles by row pitch, as sigpair_launch: rows [r0, r1), columns from r0 on
+static void sigstrip_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
+                            uint64_t ld)
+{
+  auto tiles = [&](uint32_t t) { return dim3((n - r0 + t - 1) / t, (r1 - r0 + t - 1) / t); };
+  if (pitch <= 256) hipLaunchKernelGGL((k_sigstrip_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigstrip_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigstrip_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else hipLaunchKernelGGL((k_sigstrip_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+}
+
+// ---- single-linkage tree of the rows plus the sketch estimates of the pairs without rows (ani_tree_single_sketch) ----
+// Forest 0 is ani_tree_single's forest of the pairs with rows.  The sketch pairs then come a strip of rows at a time: the strip's cells,
+// the cells that are edges (kSigStripShare of the free device memory bounds a strip: 4 bytes per cell, and 44 per edge while a strip's
+// edges are sorted, as if every cell were one), the edges ranked, merged with the forest so far, and the forest stage over the two.
+// Device memory: ani_tree_single's for the rows, the signatures twice while they are staged and once after, 4 s (s + 1) / 2 bytes of
+// distances, 8 bytes per pair with rows, and one strip.  Nothing follows nGenomes^2.
+constexpr double kSigStripShare = 0.5;
+
+int tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, const uint32_t *sig, const int32_t *len, int32_t size,
+                       int32_t kmerSize, int32_t minShared, int32_t *children, float *height, int32_t *edges, uint8_t *source)
+{
+  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
+  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
+  ctx->treeSingleRounds = 0; ctx->sigStripEdges.clear();
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG;
+  const int b = id_bits(nG);
+  SingleEdges forest;
+  DevBuf pairKeys; uint32_t nKeys = 0;
+  struct KeyGuard { DevBuf *k; ~KeyGuard() { k->release(); } } keyGuard{&pairKeys};
+  TRY(single_front(ctx, rows, n, nG, dmBits, &forest, &pairKeys, &nKeys));
+  TRY(single_rank(ctx, &forest, 0));
+  TRY(single_forest(ctx, nG, &forest));
+
+  // the signatures, staged and validated as for ani_signature_pairs
+  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, CNT, OFF, NBUF };
+  DevBufs B(NBUF);
+  const int32_t pitch = (size + 3) & ~3;
+  const uint64_t ld = (V + 3) & ~(uint64_t)3;
+  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat, *dOff; int32_t *dLen, *dCnt;
+  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
+  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  B.b[RAW].release();
+
+  if (dmBits != 0) {                                                 // (d_missing = 0: no pair lies below it)
+    // bits(d) of every (shared, size'): rule 3's identity in double on the host, then ani_tree_single's rule 2
+    const size_t S = (size_t)size;
+    std::vector<uint32_t> table(S * (S + 1) / 2);
+    parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
+      const int32_t sz = (int32_t)i + 1;
+      for (int32_t sh = 1; sh <= sz; sh++) {
+        const float w = sig_identity(sh, sz, kmerSize);
+        float d = (float)(1.0 - (double)w / 100.0);
+        if (!(d < dMissing)) d = dMissing;
+        memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &d, 4);
+      }
+    });
+    TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
+    HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    // strip height: a cell and, as if every cell were an edge, the 44 bytes of an edge in its sort, inside a share of what is free now
+    size_t freeB = 0, totalB = 0;
+    TRY(ani_device_memory(ctx, &freeB, &totalB));
+    uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (48.0 * (double)ld));
+    h = std::min<uint64_t>(h, 0xfffffff0ull / ld);                   // (the edges of a strip are numbered in 32 bits)
+    if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
+    h = std::max<uint64_t>(1, std::min<uint64_t>(h, V - 1));
+    TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat)); TRY(B.get(CNT, (size_t)h * 4, (void **)&dCnt)); TRY(B.get(OFF, (size_t)h * 4, (void **)&dOff));
+    const uint64_t *realKeys = pairKeys.as<uint64_t>();
+    for (uint64_t r0 = 0; r0 + 1 < V; r0 += h) {                     // (the last genome has no pair b > a)
+      const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V - 1), rows1 = r1 - (uint32_t)r0;
+      sigstrip_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
+      hipLaunchKernelGGL(k_sigstrip_count, dim3(rows1), dim3(kTPB), 0, st, dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared, (const uint32_t *)dTable, dmBits,
+                         realKeys, nKeys, b, dCnt);
+      HIP_TRY(hipGetLastError());
+      uint64_t nE = 0;
+      TRY(device_scan(ctx, dCnt, dOff, rows1, &nE));
+      ctx->sigStripEdges.push_back(nE);
+      if (!nE) continue;
+      SingleEdges e;
+      TRY(e.lo.ensure((size_t)nE * 4)); TRY(e.hi.ensure((size_t)nE * 4)); TRY(e.dKey.ensure((size_t)nE * 8)); TRY(e.idx.ensure((size_t)nE * 4));
+      uint32_t *eLo = e.lo.as<uint32_t>(), *eHi = e.hi.as<uint32_t>(), *idx = e.idx.as<uint32_t>(); uint64_t *dKey = e.dKey.as<uint64_t>();
+      hipLaunchKernelGGL(k_sigstrip_write, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, (const uint32_t *)dOff,
+                         eLo, eHi, dKey, idx);
+      HIP_TRY(hipGetLastError());
+      e.n = (uint32_t)nE;
+      TRY(single_rank(ctx, &e, 1));
+      TRY(single_merge(ctx, &forest, &e));
+      TRY(single_forest(ctx, nG, &forest));
+    }
+  }
+  return single_finish(ctx, forest, nG, dMissing, children, height, edges, source);
 }
 
 }  // namespace anih
@@ -1434,6 +1637,32 @@ int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGeno
 }
 
 int ani_tree_single_rounds(const ani_ctx *ctx) { return ctx ? ctx->treeSingleRounds : 0; }
+
+int ani_tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, const uint32_t *sig, const int32_t *len,
+                           int32_t size, int32_t kmerSize, int32_t minShared, int32_t *children, float *height, int32_t *edges, uint8_t *source)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height || !sig || !len))) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
+  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the cluster ids of the tree take at most 2^30", nGenomes);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  if (nGenomes <= 1) return ANI_OK;
+  for (int32_t g = 0; g < nGenomes; g++)
+    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return tree_single_sketch(ctx, rows, n, nGenomes, missingIdentity, sig, len, size, kmerSize, minShared, children, height, edges, source); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_tree_single_sketch_strips(const ani_ctx *ctx, uint64_t *edgesPerStrip, size_t cap)
+{
+  if (!ctx) return 0;
+  for (size_t i = 0; i < ctx->sigStripEdges.size() && i < cap && edgesPerStrip; i++) edgesPerStrip[i] = ctx->sigStripEdges[i];
+  return (int)ctx->sigStripEdges.size();
+}
 
 int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
 {

@@ -360,7 +360,8 @@ struct ani_ctx {
   size_t l2ChunkCandidates = (size_t)1 << 21;                                      // L2 chunk size (env ANI_TEST_L2_CHUNK, tests)
   // 16-bit code entries per L2 chunk (32-bit offsets; env ANI_TEST_L2_CODE_LIMIT, tests)
   uint64_t l2CodeLimit = 0xfffffff0ull;
-  int treeSingleRounds = 0;                                                        // spanning-forest rounds of the last ani_tree_single (ani_tree_single_rounds)
+  int treeSingleRounds = 0;                                                        // spanning-forest rounds of the last ani_tree_single[_sketch] (ani_tree_single_rounds)
+  std::vector<uint64_t> sigStripEdges;                                             // edges kept per strip of the last ani_tree_single_sketch
   // minimizers per index chunk (env ANI_MAX_INDEX_MINIMIZERS); indices are 32 bit
   uint64_t maxIndexMinimizers = 1700000000ull;
   // (engine_map.hip checks them against kernels/l1.hpp)           // env ANI_TEST_L1_FILTER_MIN / ANI_TEST_L1_LDS_MAX, read by ani_init (tests: per engine, not

@@ -8,7 +8,8 @@
 // tree, ani_tree_average, with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj, or with `--treeMethod single` their
 // single-linkage tree and, in a .mst file, their minimum spanning tree, ani_tree_single).  `--sketchANI` (extension) adds a .sketch
 // file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
-// tree that estimate for the pairs without a .matrix cell.  Sketch / Map / computeCGI run on the GPU(s)
+// tree that estimate for the pairs without a .matrix cell (streamed through ani_tree_single_sketch for a single-linkage tree of more
+// than 65 536 genomes).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -73,6 +74,8 @@ struct Options {
   bool sketchANI = false, treeFill = false;            // --sketchANI: the .sketch file; --treeFill sketch: sketch estimates for the tree's missing pairs
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
   bool signatures() const { return sketchANI || treeFill; }
+  // --tree --treeMethod single --treeFill sketch alone: the one use of the genome sketches that can be streamed (ani_tree_single_sketch)
+  bool streamable() const { return tree && treeSingle && treeFill && !sketchANI; }
   std::vector<std::string> refs, queries;
   std::vector<int> devices{0};
   std::string out, saveSketch, refSketch;
@@ -113,7 +116,8 @@ struct Options {
     "                 genome, ANI, ani or sketch for where the value comes from; one line per merge below distance 1, closest pair\n"
     "                 first; the lines with ANI >= T are the connected components at T) [default : average]\n"
     "     --treeFill <value>  sketch: a pair without ANI enters the tree at the whole-genome sketch estimate (see --sketchANI) instead\n"
-    "                 of distance 1, if the two sketches share anything; the queries must be among the references [default : none]\n"
+    "                 of distance 1, if the two sketches share anything; the queries must be among the references; at most 65536\n"
+    "                 genomes, any number with --treeMethod single and without --sketchANI [default : none]\n"
     "     --sketchANI also output a Mash-style ANI estimate between the genomes, from the smallest minimizer hashes of each genome\n"
     "                 (.sketch: genome, genome, estimate, shared/size); the queries must be among the references [disabled by default]\n"
     "     --sketchSize <value>  hashes per genome sketch, 1 to 4096 [default : 1000]\n"
@@ -533,11 +537,12 @@ struct SigTable {
 SigTable g_sigs;
 
 // --sketchANI / --treeFill sketch need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
-// and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped
+// and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
+// no ceiling: its sketch pairs are streamed (write_tree_single_streamed).
 void check_sketch_genomes(const Options &o)
 {
   std::unordered_set<std::string> refs(o.refs.begin(), o.refs.end());
-  if (refs.size() > 65536) {
+  if (refs.size() > 65536 && !o.streamable()) {
     std::cerr << "ERROR, --sketchANI and --treeFill sketch take at most 65536 genomes, this run has " << refs.size() << std::endl; exit(1); }
   for (auto &q : o.queries)
     if (!refs.count(q)) {
@@ -1335,6 +1340,8 @@ void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, co
 // identity 0), written like the average-linkage one; and .mst, the edges that caused its merges below distance 1 (the minimum spanning
 // forest of the cells), in merge order: genome, genome (the smaller .matrix index first), the pair's value as the .matrix folds and the
 // .clusters file prints it, and `ani` for a .matrix cell or `sketch` for a fill cell of --treeFill sketch.
+void write_mst(const std::string &mstPath, const MatrixCells &mc, const std::vector<int32_t> &edges, const std::vector<float> &height, const std::vector<Cell> &fill);
+
 void write_tree_single(const std::string &path, const std::string &mstPath, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
 {
   const int n = (int)mc.names.size();
@@ -1345,7 +1352,13 @@ void write_tree_single(const std::string &path, const std::string &mstPath, ani_
   std::vector<ani_cgi_t>().swap(rows);
   write_linkage(path, mc, children, height);
   trace("tree written");
-  // the forest edges' values: their cells folded in result order, as write_matrix folds them
+  write_mst(mstPath, mc, edges, height, fill);
+}
+
+// .mst: the forest edges' values are their cells folded in result order, as write_matrix folds them, or their fill cell
+void write_mst(const std::string &mstPath, const MatrixCells &mc, const std::vector<int32_t> &edges, const std::vector<float> &height, const std::vector<Cell> &fill)
+{
+  const size_t m = height.size();
   struct Value { float w; bool sketch; };
   std::unordered_map<uint64_t, Value> value;
   size_t nForest = 0;
@@ -1430,18 +1443,26 @@ void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc,
 // least --sketchMinANI, in (a, b) order of the .matrix numbering: genome, genome, estimate, shared/size.  Fill cells: every pair
 // without a .matrix cell whose sketches share something, at the estimate (an estimate that the clamp leaves at 0 stays missing: it is
 // the tree's distance 1 either way).
-std::vector<Cell> sketch_pairs(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+// the collected signatures in the .matrix numbering
+void matrix_signatures(const Options &o, const MatrixCells &mc, std::vector<uint32_t> &sig, std::vector<int32_t> &len)
 {
   const size_t n = mc.names.size(), S = (size_t)g_sigs.size;
   std::unordered_map<std::string, size_t> refOf;
   for (size_t r = 0; r < o.refs.size(); r++) refOf.emplace(o.refs[r], r);
-  std::vector<uint32_t> sig(n * S); std::vector<int32_t> len(n);
+  sig.assign(n * S, 0u); len.assign(n, 0);
   for (size_t i = 0; i < n; i++) {
     const auto it = refOf.find(mc.names[i]);
     if (it == refOf.end() || !g_sigs.have[it->second]) { std::cerr << "ERROR, no genome sketch of " << mc.names[i] << std::endl; exit(1); }
     std::copy(g_sigs.sig.begin() + (std::ptrdiff_t)(it->second * S), g_sigs.sig.begin() + (std::ptrdiff_t)((it->second + 1) * S), sig.begin() + (std::ptrdiff_t)(i * S));
     len[i] = g_sigs.len[it->second];
   }
+}
+
+std::vector<Cell> sketch_pairs(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const size_t n = mc.names.size(), S = (size_t)g_sigs.size;
+  std::vector<uint32_t> sig; std::vector<int32_t> len;
+  matrix_signatures(o, mc, sig, len);
   ani_sigpair_t *rows = nullptr; size_t nr = 0;
   if (ani_signature_pairs(ctx, sig.data(), len.data(), (int32_t)n, (int32_t)S, kmerSize, 1, &rows, &nr)) die("ani_signature_pairs");
   trace("sketch pairs compared");
@@ -1463,6 +1484,49 @@ std::vector<Cell> sketch_pairs(const Options &o, ani_ctx *ctx, int kmerSize, con
   }
   ani_free(rows);
   return fill;
+}
+
+// ---- --tree --treeMethod single --treeFill sketch beyond the pair step's 65 536 genomes (ANI_TEST_CLI_SINGLE_STREAM=1: at any size, for
+// tests): ani_tree_single_sketch makes the sketch pairs a strip at a time on the first device and folds them into the forest, so neither
+// the pairs nor their fill cells ever exist on the host.  The same .newick and .mst as write_tree_single over sketch_pairs' fill.  A
+// sketch edge's value in the .mst is ani_abi.h's estimate (rules 2 and 3 of the sketch ANI) of its two signatures, worked out here for
+// the at most n - 1 such edges.
+float sketch_estimate(const uint32_t *a, int32_t la, const uint32_t *b, int32_t lb, int32_t size, int kmerSize)
+{
+  int32_t pa = 0, pb = 0, steps = 0, shared = 0;
+  while (steps < size && pa < la && pb < lb) {
+    const uint32_t x = a[pa], y = b[pb];
+    pa += x <= y; pb += y <= x; shared += x == y;
+    steps++;
+  }
+  const int32_t u = std::min(size, steps + (la - pa) + (lb - pb));
+  if (shared == 0) return 0.0f;
+  const double id = 100.0 * (1.0 + log(2.0 * (double)shared / (double)(u + shared)) / (double)kmerSize);
+  return (float)std::min(100.0, std::max(0.0, id));
+}
+
+void write_tree_single_streamed(const Options &o, const std::string &path, const std::string &mstPath, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const int n = (int)mc.names.size();
+  const int32_t S = g_sigs.size;
+  std::vector<uint32_t> sig; std::vector<int32_t> len;
+  matrix_signatures(o, mc, sig, len);
+  std::vector<ani_cgi_t> rows = tree_rows(mc, {});
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
+  std::vector<int32_t> children(2 * m), edges(2 * m); std::vector<float> height(m); std::vector<uint8_t> source(m);
+  if (ani_tree_single_sketch(ctx, rows.data(), rows.size(), n, 0.0f, sig.data(), len.data(), S, kmerSize, 1, children.data(), height.data(), edges.data(),
+                             source.data())) die("ani_tree_single_sketch");
+  std::vector<ani_cgi_t>().swap(rows);
+  trace("sketch pairs folded");
+  write_linkage(path, mc, children, height);
+  trace("tree written");
+  std::vector<Cell> fill;
+  for (size_t s = 0; s < m; s++)
+    if (source[s] == 1) {
+      const int32_t a = edges[2 * s], b = edges[2 * s + 1];
+      fill.push_back(Cell{b, a, sketch_estimate(sig.data() + (size_t)a * (size_t)S, len[(size_t)a], sig.data() + (size_t)b * (size_t)S, len[(size_t)b], S, kmerSize)});
+    }
+  write_mst(mstPath, mc, edges, height, fill);
 }
 
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
@@ -1576,8 +1640,11 @@ int main(int argc, char **argv)
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
-  if (o.signatures()) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
-  if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)
+  const char *streamEnv = getenv("ANI_TEST_CLI_SINGLE_STREAM");
+  const bool streamed = o.streamable() && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
+  if (o.signatures() && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (streamed) write_tree_single_streamed(o, o.out + ".newick", o.out + ".mst", su.dev[0].ctx, ap.kmerSize, mc);
+  else if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)
   else if (o.tree && o.treeSingle) write_tree_single(o.out + ".newick", o.out + ".mst", su.dev[0].ctx, mc, fill);
   else if (o.tree) write_tree(o.out + ".newick", su.dev[0].ctx, mc, fill);
   if (o.matrix) write_matrix(o.out + ".matrix", mc);

@@ -127,12 +127,12 @@ static __global__ __launch_bounds__(kTPB) void k_sigpair_stage(const uint32_t *_
 //   size(a, b) = min(size, steps + what is left of either row),   shared(a, b) = ties among the steps.
 // Integers only and one lane per pair: no atomics, no dependence on any order.  T and the LDS words are chosen by the host from the
 // row pitch (sigpair_launch in engine_map.hip); pairs with b <= a, and genomes beyond n, are skipped.
-template <int T, int WORDS>
-static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_sigpair_merge(const uint32_t *__restrict__ sig, const int32_t *__restrict__ len,
-    int32_t n, int32_t pitch, int32_t size, uint32_t *__restrict__ mat, uint64_t ld)
+// sigpair_tile is the tile itself, shared with the strip kernel (sigstrip.hpp): tile coordinates count from genome `base`, rows end at
+// rowEnd, and the cell of (a, b) is mat[(a - base) * ld + b].  The whole matrix is base = 0, rowEnd = n.
+template <int T>
+__device__ __forceinline__ void sigpair_tile(uint32_t *tile, int32_t *tileLen, const uint32_t *__restrict__ sig, const int32_t *__restrict__ len, uint32_t n,
+    uint32_t base, uint32_t rowEnd, int32_t pitch, int32_t size, uint32_t *__restrict__ mat, uint64_t ld)
 {
-  __shared__ uint32_t tile[WORDS];
-  __shared__ int32_t tileLen[2 * T];
   const uint32_t ty = blockIdx.y, tx = blockIdx.x;
   if (tx < ty) return;
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
@@ -140,17 +140,17 @@ static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_sigpa
   const uint32_t rows = diag ? T : 2 * T, quads = (uint32_t)pitch / 4;
   uint4 *tile4 = (uint4 *)tile;
   for (uint32_t r = 0; r < rows; r++) {
-    const uint32_t g = (r < (uint32_t)T ? ty * T : tx * T - T) + r;
-    const int32_t l = g < (uint32_t)n ? len[g] : 0;
+    const uint64_t g = (uint64_t)base + (r < (uint32_t)T ? (uint64_t)ty * T : (uint64_t)tx * T - T) + r;
+    const int32_t l = g < n ? len[g] : 0;
     if (tid == 0) tileLen[r] = l;
-    const uint4 *src = (const uint4 *)(sig + (uint64_t)g * (uint32_t)pitch);
+    const uint4 *src = (const uint4 *)(sig + g * (uint32_t)pitch);
     for (uint32_t q = tid; q < ((uint32_t)l + 3) / 4; q += nt) tile4[r * quads + q] = src[q];
   }
   block_barrier();
   if (tid >= (uint32_t)(T * T)) return;
   const uint32_t i = tid / T, j = tid % T;
-  const uint32_t a = ty * T + i, b = tx * T + j;
-  if (a >= b || b >= (uint32_t)n) return;
+  const uint64_t a = (uint64_t)base + (uint64_t)ty * T + i, b = (uint64_t)base + (uint64_t)tx * T + j;
+  if (a >= b || b >= n || a >= rowEnd) return;
   const uint32_t rb = diag ? j : T + j;
   const uint32_t *A = tile + i * (uint32_t)pitch, *B = tile + rb * (uint32_t)pitch;
   const int32_t la = tileLen[i], lb = tileLen[rb];
@@ -162,7 +162,16 @@ static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_sigpa
   }
   int32_t u = steps + (la - pa) + (lb - pb);
   if (u > size) u = size;
-  mat[(uint64_t)a * ld + b] = ((uint32_t)shared << 16) | (uint32_t)u;
+  mat[(a - base) * ld + b] = ((uint32_t)shared << 16) | (uint32_t)u;
+}
+
+template <int T, int WORDS>
+static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_sigpair_merge(const uint32_t *__restrict__ sig, const int32_t *__restrict__ len,
+    int32_t n, int32_t pitch, int32_t size, uint32_t *__restrict__ mat, uint64_t ld)
+{
+  __shared__ uint32_t tile[WORDS];
+  __shared__ int32_t tileLen[2 * T];
+  sigpair_tile<T>(tile, tileLen, sig, len, (uint32_t)n, 0u, (uint32_t)n, pitch, size, mat, ld);
 }
 
 // one workgroup per row a

@@ -7,7 +7,8 @@
 //   (device_scan of the flags: the edges keep their (lo, hi) order)
 //   k_single_pairs    the edges, compacted: lo, hi, and bits(d) as the key of the second sort with the edge's position as its payload
 //   (stable radix sort over the 32 bits of d: position r of the result is the edge of rank r in the order (bits(d), lo, hi))
-//   k_single_rank     lo and hi of every edge by rank; chosen flags zeroed
+//   k_single_rank     lo, hi, bits(d) and a source byte of every edge by rank: a ranked edge list
+//   (the forest stage, single_forest in engine_map.hip, over a ranked edge list:)
 //   k_single_init     every vertex its own component, no best edge
 //   per round (Boruvka):
 //   k_single_best     a live edge whose ends lie in two components offers its rank to both (atomicMin) and stays live
@@ -15,7 +16,12 @@
 //   k_single_jump     every root of the round follows the hooks to the root that remains (compressing as it goes)
 //   k_single_label    vertex -> the new root of its old root; best edges cleared
 //   (device_scan of the chosen flags)
-//   k_single_records  the chosen edges in rank order: lo, hi, bits(d) per forest edge
+//   k_single_records  the chosen edges in rank order: the forest, itself a ranked edge list
+//
+// ani_tree_single_sketch folds further edges into a forest: MSF(A u B) = MSF(MSF(A) u B) under a strict order.
+//   k_single_keyflag / k_single_keys  the sorted distinct keys lo << b | hi of the non-self pairs with rows (they mask sketch pairs)
+//   k_single_merge    two ranked edge lists with no edge in common -> one: an edge's place is its index plus the edges of the other
+//                     list that sort before it (a binary search per lane)
 //
 // Ranks are a strict total order, so the spanning forest is unique and the chosen flags do not depend on the order in which the
 // atomics land or the workgroups run: per round and component, atomicMin leaves the smallest rank among its outgoing live edges,
@@ -57,12 +63,13 @@ static __global__ void k_single_pairs(const uint64_t *__restrict__ keys, const u
 }
 
 static __global__ void k_single_rank(uint32_t nE, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ eLo, const uint32_t *__restrict__ eHi,
-                                     uint32_t *__restrict__ uLo, uint32_t *__restrict__ uHi, int32_t *__restrict__ chosen)
+                                     const uint64_t *__restrict__ dKey, uint8_t source, uint32_t *__restrict__ uLo, uint32_t *__restrict__ uHi,
+                                     uint32_t *__restrict__ uD, uint8_t *__restrict__ uSrc)
 {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nE) return;
   const uint32_t p = idx[r];
-  uLo[r] = eLo[p]; uHi[r] = eHi[p]; chosen[r] = 0;
+  uLo[r] = eLo[p]; uHi[r] = eHi[p]; uD[r] = (uint32_t)dKey[r]; uSrc[r] = source;
 }
 
 static __global__ void k_single_init(uint32_t nV, uint32_t *__restrict__ comp, uint32_t *__restrict__ best)
@@ -136,14 +143,65 @@ static __global__ void k_single_label(uint32_t nV, uint32_t *__restrict__ comp, 
   best[v] = kSingleNone;
 }
 
-// pos[r]: chosen edges of smaller rank.  rec: 3 words per forest edge.
+// pos[r]: chosen edges of smaller rank.
 static __global__ void k_single_records(uint32_t nE, const int32_t *__restrict__ chosen, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ uLo,
-                                        const uint32_t *__restrict__ uHi, const uint64_t *__restrict__ dKey, uint32_t *__restrict__ rec)
+                                        const uint32_t *__restrict__ uHi, const uint32_t *__restrict__ uD, const uint8_t *__restrict__ uSrc,
+                                        uint32_t *__restrict__ fLo, uint32_t *__restrict__ fHi, uint32_t *__restrict__ fD, uint8_t *__restrict__ fSrc)
 {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nE || !chosen[r]) return;
-  uint32_t *o = rec + 3 * (uint64_t)pos[r];
-  o[0] = uLo[r]; o[1] = uHi[r]; o[2] = (uint32_t)dKey[r];
+  const uint32_t p = pos[r];
+  fLo[p] = uLo[r]; fHi[p] = uHi[r]; fD[p] = uD[r]; fSrc[p] = uSrc[r];
+}
+
+// ---- folding further edges into a forest (ani_tree_single_sketch) ----
+
+// per sorted position: 1 where a key starts that is not a self pair
+static __global__ void k_single_keyflag(const uint64_t *__restrict__ keys, uint64_t n, int b, int32_t *__restrict__ flag)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = keys[i];
+  flag[i] = (i == 0 || keys[i - 1] != key) && (key >> b) != (key & ((1ull << b) - 1ull)) ? 1 : 0;
+}
+
+static __global__ void k_single_keys(const uint64_t *__restrict__ keys, uint64_t n, const int32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                     uint64_t *__restrict__ out)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && flag[i]) out[pos[i]] = keys[i];
+}
+
+struct SingleList { const uint32_t *lo, *hi, *d; const uint8_t *src; uint32_t n; };
+
+// edges of the ranked list `l` that sort before (d, lo, hi), or at it too if `orEqual`
+__device__ __forceinline__ uint32_t single_edges_before(const SingleList &l, uint32_t d, uint32_t lo, uint32_t hi, bool orEqual)
+{
+  const uint64_t pair = ((uint64_t)lo << 32) | hi;
+  uint32_t a = 0, c = l.n;
+  while (a < c) {
+    const uint32_t mid = a + (c - a) / 2;
+    const uint32_t md = l.d[mid];
+    const uint64_t mp = ((uint64_t)l.lo[mid] << 32) | l.hi[mid];
+    const bool before = md != d ? md < d : (orEqual ? mp <= pair : mp < pair);
+    if (before) a = mid + 1; else c = mid;
+  }
+  return a;
+}
+
+// One lane per edge of x, then of y.  The lists share no edge (a sketch edge has no rows and belongs to one strip), so either rule alone
+// would do; taking "before" for x and "before or equal" for y keeps the places a permutation whatever the input.
+static __global__ void k_single_merge(SingleList x, SingleList y, uint32_t *__restrict__ oLo, uint32_t *__restrict__ oHi, uint32_t *__restrict__ oD,
+                                      uint8_t *__restrict__ oSrc)
+{
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= x.n + y.n) return;
+  const bool first = t < x.n;
+  const SingleList &mine = first ? x : y, &other = first ? y : x;
+  const uint32_t i = first ? t : t - x.n;
+  const uint32_t lo = mine.lo[i], hi = mine.hi[i], d = mine.d[i];
+  const uint32_t p = i + single_edges_before(other, d, lo, hi, !first);
+  oLo[p] = lo; oHi[p] = hi; oD[p] = d; oSrc[p] = mine.src[i];
 }
 
 }  // namespace ani

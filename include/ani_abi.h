@@ -384,7 +384,7 @@ int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes,
  *    2 nGenomes - 2 and are int32); ANI_ERR_NOMEM: the device cannot hold the buffers, 56 bytes per row at the peak plus 24 per genome.
  *    All argument and limit checks run before any allocation.
  * ani_tree_single_rounds: the spanning-forest rounds (Boruvka's, at most ceil(log2 nGenomes) + 1) the context's last ani_tree_single
- * call took on the device; 0 if it needed none or there was no call (tools/tree_probe.py reports it). */
+ * call took on the device (or the folds of its last ani_tree_single_sketch call, together); 0 if it needed none or there was no call (tools/tree_probe.py reports it). */
 int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
                     int32_t *children, float *height, int32_t *edges);
 int ani_tree_single_rounds(const ani_ctx *ctx);
@@ -413,6 +413,33 @@ typedef struct { int32_t a, b, shared, size; float identity; } ani_sigpair_t;
 int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig /* [nGenomes * size] */, int32_t *len /* [nGenomes] */);
 int ani_signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
                         int32_t minShared, ani_sigpair_t **rows, size_t *n);
+
+/* ---- single-linkage tree of the rows with the whole-genome sketch estimate for every pair without rows, streamed (no counterpart in the
+ * reference).  ani_tree_single over the rows and the fill of ani_signature_pairs in one call that never holds
+ * anything of size nGenomes^2, on the device or on the host: there is no 65 536 ceiling.
+ * 1. Defined by composition.  P = the pairs ani_signature_pairs(sig, len, nGenomes, size, kmerSize, minShared) returns.  F = the pairs
+ *    of P with identity > 0 that have no row in `rows` other than self rows (rows of either direction count, whatever their identity).
+ *    children, height and edges are those of ani_tree_single over `rows` followed by one row (a, b, identity) per pair of F, at the same
+ *    missingIdentity.  The order of F does not matter: a pair of F has one row.
+ * 2. source[s], one byte per merge: 0 if the pair that caused merge s has rows, 1 if it is a pair of F, 2 for a join to leaf 0 at the
+ *    missing distance (ani_tree_single's rule 5).  source may be null, and so may edges.
+ * 3. rows, nGenomes, missingIdentity, children, height, edges: as for ani_tree_single.  sig, len, size, kmerSize: as for
+ *    ani_signature_pairs, genome ids = row numbers = the ids of `rows`.  minShared >= 1.
+ * 4. ANI_ERR_ARG: every case of ani_tree_single (a null pointer, nGenomes < 0, an id outside [0, nGenomes), a row identity outside
+ *    (0, 100], missingIdentity outside [0, 100]) and of ani_signature_pairs (size outside [1, 4096], kmerSize outside [1, 16], a len
+ *    outside [0, size], a signature that does not ascend strictly inside its len), and minShared < 1.  ANI_ERR_LIMIT: ani_tree_single's
+ *    own, n > 2^32 - 16 rows or nGenomes > 2^30.  The checks of the scalar arguments and of len run before any allocation.
+ * 5. nGenomes <= 1: ANI_OK, nothing is read or written.
+ * 6. Memory.  The sketch pairs are made a strip of rows of the pair matrix at a time and folded into a forest of at most nGenomes - 1
+ *    edges.  Device: ani_tree_single's for the rows, 8 size nGenomes bytes while the signatures are staged (half of it after), 2 size^2
+ *    bytes of distances, 8 bytes per pair with rows, and one strip, whose height follows the free device memory.  Host: 13 bytes per
+ *    forest edge.  ANI_TEST_SIG_STRIP_ROWS (tests) forces a strip height; the result does not depend on it.
+ * ani_tree_single_rounds counts the spanning-forest rounds of all folds of the call.  ani_tree_single_sketch_strips: the strips of the
+ * context's last call (its return value) and, for the first `cap` of them, the edges each strip added to its fold (may be null). */
+int ani_tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                           const uint32_t *sig, const int32_t *len, int32_t size, int32_t kmerSize, int32_t minShared,
+                           int32_t *children, float *height, int32_t *edges /* may be null */, uint8_t *source /* may be null */);
+int ani_tree_single_sketch_strips(const ani_ctx *ctx, uint64_t *edgesPerStrip, size_t cap);
 
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut

@@ -1,6 +1,6 @@
 """Timings of ani_tree_average (average-linkage tree), with --method nj of ani_tree_nj (neighbour joining,
-section 2.13) and with --method single of ani_tree_single (single linkage / minimum spanning tree, section 2.15) on synthetic row sets,
-on the GPU.  The call returns after its last device-to-host copy, so the wall clock around it
+section 2.13), with --method single of ani_tree_single (single linkage / minimum spanning tree, section 2.15) and with --method
+single-sketch of ani_tree_single_sketch (the same with the sketch fill, streamed, section 2.16) on synthetic row sets, on the GPU.  The call returns after its last device-to-host copy, so the wall clock around it
 includes the upload, the matrix, every merge launch and the read-back.
 
     python tools/tree_probe.py                 the row sets below, 1 warm-up + 3 timed calls each (median reported)
@@ -11,6 +11,12 @@ includes the upload, the matrix, every merge launch and the read-back.
                                                ceiling), with its spanning-forest rounds, and ani_cluster_greedy at 95 on the same rows
                                                as the yardstick: both calls upload, sort and fold the rows, so the difference is
                                                what the forest stage costs
+    python tools/tree_probe.py --method single-sketch
+                                               ani_tree_single_sketch (section 2.16) on species rows plus signatures of 1000 values for
+                                               1 000, 10 000, 65 536 and 90 000 genomes: wall clock, strips, rounds and the edges each
+                                               strip kept; beside it ani_signature_pairs + the fill rule + ani_tree_single on the same
+                                               input, up to --compose-max genomes (default 10 000: the composition brings every pair
+                                               that shares a value to the host, 1.5 * 10^9 rows at 65 536), and the two results compared
     python tools/tree_probe.py --reps 1        timed calls per row set (default 3)
     python tools/tree_probe.py --cli 1000      in addition: fastANI --ql L --rl L --tree on that many 5 Mbp genomes, the
                                                ANI_CLI_TRACE marks of the run ("rows ordered" -> "tree written" is the tree's share)
@@ -125,6 +131,64 @@ def time_single(e, rows, n, reps=3):
     return out[0], e.tree_single_rounds(), int((height < 1.0).sum()), out[1]
 
 
+def species_signatures(rng, n, size=1000, per_species=50):
+    """signatures of `size` values below size / 5e6 * 2^32, where the bottom values of a 5 Mbp genome lie: unrelated genomes share about
+    one value by chance; a genome keeps 60 - 97 % of its species' values"""
+    top = int(size / 5e6 * 2 ** 32)
+    sig = np.empty((n, size), dtype=np.uint32)
+    for s0 in range(0, n, per_species):
+        m = min(per_species, n - s0)
+        base = rng.integers(0, top, size, dtype=np.uint32)
+        own = rng.integers(0, top, (m, size), dtype=np.uint32)
+        keep = rng.random((m, size)) < rng.uniform(0.6, 0.97, (m, 1))
+        sig[s0:s0 + m] = np.where(keep, base[None, :], own)
+    sig.sort(axis=1)
+    length = np.full(n, size, dtype=np.int32)
+    for g in np.nonzero((np.diff(sig.astype(np.int64), axis=1) <= 0).any(axis=1))[0]:      # a repeated value: the distinct ones, a shorter row
+        u = np.unique(sig[g])
+        sig[g] = 0
+        sig[g, :len(u)] = u
+        length[g] = len(u)
+    return sig, length
+
+
+def time_single_sketch(e, rows, n, sig, length, reps=3, compose=True):
+    from fastani_amd.api import CGI_DT
+
+    def streamed():
+        return e.tree_single_sketch(rows, n, sig, length, 16, 1, 0.0, return_edges=True, return_source=True)
+
+    def composed():
+        pairs = e.signature_pairs(sig, length, 16, 1)
+        q, r = rows["qryGenomeId"].astype(np.int64), rows["refGenomeId"].astype(np.int64)
+        have = np.unique(np.minimum(q, r)[q != r] * n + np.maximum(q, r)[q != r])
+        fill = pairs[(pairs["identity"] > 0) & ~np.isin(pairs["a"].astype(np.int64) * n + pairs["b"], have)]
+        extra = np.zeros(len(fill), dtype=CGI_DT)
+        extra["qryGenomeId"], extra["refGenomeId"], extra["identity"] = fill["a"], fill["b"], fill["identity"]
+        return e.tree_single(np.concatenate([rows, extra]), n, 0.0, return_edges=True) + (len(pairs),)
+    out = []
+    for call in (streamed, composed) if compose else (streamed,):
+        result = call()                                            # warm-up: code objects, pool segments, page-locked staging
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            result = call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        out.append((ms, result))
+        if call is streamed:
+            strips, rounds = e.tree_single_sketch_strips(), e.tree_single_rounds()
+    (ms, (z, edges, source)) = out[0]
+    line = "ani_tree_single_sketch %s ms (median %.1f)   %d strips, %d rounds, edges kept per strip %s   merges from rows / sketch / joins %s" % (
+        " ".join("%.1f" % x for x in ms), float(np.median(ms)), len(strips), rounds, " ".join(str(int(x)) for x in strips),
+        " / ".join(str(int(x)) for x in np.bincount(source, minlength=3)))
+    if compose:
+        (cms, (cz, cedges, npairs)) = out[1]
+        same = np.array_equal(z, cz) and np.array_equal(edges, cedges)
+        line += "   signature_pairs + fill + tree_single %s ms (median %.1f, %d pair rows)   %s" % (
+            " ".join("%.1f" % x for x in cms), float(np.median(cms)), npairs, "identical" if same else "DIFFERENT")
+    return line
+
+
 def cli_run(n):
     import bench
     import orc
@@ -163,7 +227,18 @@ def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     method = sys.argv[sys.argv.index("--method") + 1] if "--method" in sys.argv else "average"
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
-    assert method in ("average", "nj", "single"), method
+    assert method in ("average", "nj", "single", "single-sketch"), method
+    if method == "single-sketch":
+        compose_max = int(sys.argv[sys.argv.index("--compose-max") + 1]) if "--compose-max" in sys.argv else 10000
+        for n in (1000, 10000, 65536, 90000):
+            if not ("species %d" % n).startswith(only):
+                continue
+            rows = species_rows(rng, n, 100 * n)
+            sig, length = species_signatures(rng, n)
+            print("species %-6d rows %9d genomes %6d size 1000   %s" % (n, len(rows), n, time_single_sketch(e, rows, n, sig, length, reps, n <= compose_max)),
+                  flush=True)
+            del rows, sig
+        return 0
     if method == "single":
         sets.append(("species 150000", lambda: species_rows(rng, 150000, 10 ** 7), 150000))
     for name, make, n in sets:
