@@ -13,6 +13,8 @@
     Engine.signature_pairs(sig, len, k)    Mash-style ANI estimate between all pairs of signatures (no reference counterpart)
     Engine.tree_single_sketch(rows, n, sig, len, k)  tree_single with that estimate for every pair without rows, streamed strip by
                                            strip: nothing of size n^2 anywhere, no genome ceiling (no reference counterpart)
+    Engine.signature_neighbors(sig, len, k_mer, k)  the k nearest neighbours of every genome under that estimate, streamed strip by
+                                           strip, no genome ceiling (no reference counterpart)
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -29,6 +31,7 @@ MAPPING_DT = np.dtype([("queryLen", "<i4"), ("refStartPos", "<i4"), ("refEndPos"
 CGI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("countSeq", "<i4"),
                    ("totalQueryFragments", "<i4"), ("identity", "<f4")])
 SIGPAIR_DT = np.dtype([("a", "<i4"), ("b", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
+NEIGHBOR_DT = np.dtype([("neighbor", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -133,6 +136,8 @@ def _bind(lib):
         "ani_tree_single_sketch_strips": (C.c_int, [vp, vp, C.c_size_t]),
         "ani_sketch_signatures": (C.c_int, [vp, C.c_int32, vp, vp]),
         "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+        "ani_signature_neighbors": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+        "ani_signature_neighbors_strips": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -517,6 +522,29 @@ class Engine:
         self._chk(self.lib.ani_signature_pairs(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
                                                int(min_shared), C.byref(p), C.byref(m)))
         return self._take(p, m.value, SIGPAIR_DT)
+
+    def signature_neighbors(self, sig, length, kmer_size, k, min_shared=1, min_identity=0.0, rows=None):
+        """for every genome of `rows` = (begin, end) (None: all of them) its k nearest neighbours among all genomes under the estimate
+        of signature_pairs(sig, length, kmer_size, min_shared), identity >= min_identity, nearest first and ties by ascending id
+        (ani_signature_neighbors; the semantics are in ani_abi.h).  Streamed through the device a strip of rows at a time: no 65 536
+        ceiling.  -> (neighbors, count): NEIGHBOR_DT (end - begin, k), the unused slots (-1, 0, 0, 0.0), and int32 (end - begin,)."""
+        sig = np.ascontiguousarray(sig, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        if sig.ndim != 2 or length.shape != (sig.shape[0],):
+            raise ValueError("sig must be (n, size) and length (n,)")
+        n, size = sig.shape
+        begin, end = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+        m, k = max(end - begin, 0), int(k)
+        out = np.zeros((m, max(k, 0)), dtype=NEIGHBOR_DT)
+        count = np.zeros(m, dtype=np.int32)
+        self._chk(self.lib.ani_signature_neighbors(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
+                                                   int(min_shared), float(min_identity), k, begin, end, out.ctypes.data if out.size else None,
+                                                   count.ctypes.data if m else None))
+        return out, count
+
+    def signature_neighbors_strips(self):
+        """strips the last signature_neighbors call of this engine took (ani_signature_neighbors_strips)"""
+        return int(self.lib.ani_signature_neighbors_strips(self.h))
 
 
 class FragmentSet:

@@ -18,6 +18,7 @@
 #include "kernels/single.hpp"
 #include "kernels/sigdist.hpp"
 #include "kernels/sigstrip.hpp"
+#include "kernels/signeigh.hpp"
 
 namespace anih {
 using namespace ani;
@@ -1386,6 +1387,96 @@ int tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG
   return single_finish(ctx, forest, nG, dMissing, children, height, edges, source);
 }
 
+// ---- nearest neighbours under the sketch estimate (ani_signature_neighbors) ----
+// the rectangular tiles by row pitch, as sigpair_launch: rows [r0, r1), all columns
+static void signeigh_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
+                            uint64_t ld)
+{
+  auto tiles = [&](uint32_t t) { return dim3((n + t - 1) / t, (r1 - r0 + t - 1) / t); };
+  if (pitch <= 256) hipLaunchKernelGGL((k_signeigh_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else if (pitch <= 1024) hipLaunchKernelGGL((k_signeigh_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else if (pitch <= 2048) hipLaunchKernelGGL((k_signeigh_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+  else hipLaunchKernelGGL((k_signeigh_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
+}
+
+// The signatures are staged and validated as for ani_signature_pairs, the identity bits of every (shared, size') come from the host, and
+// the rows of the range go through the device a strip at a time: the strip's cells against every genome, then the k nearest of each row,
+// written into the row's place of the range's output and copied back through page-locked staging.  Every pair is merged once from
+// each of its ends.  Device memory: the signatures twice while they are staged and once after, 2 s (s + 1) bytes of identities,
+// 16 k + 4 bytes per row of the range, and one strip (kSigStripShare of what is free then, 4 bytes per cell).  Nothing follows nGenomes^2.
+int signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
+                        int32_t k, int32_t rowBegin, int32_t rowEnd, ani_signeighbor_t *out, int32_t *count)
+{
+  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, OUT, CNT, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG, R = (size_t)(rowEnd - rowBegin);
+  const int32_t pitch = (size + 3) & ~3;
+  const uint64_t ld = (V + 3) & ~(uint64_t)3;
+  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat; int32_t *dLen, *dCnt; uint4 *dOut;
+  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
+  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  B.b[RAW].release();
+
+  // bits(identity) of every (shared, size'): rule 3 in double on the host
+  const size_t S = (size_t)size;
+  std::vector<uint32_t> table(S * (S + 1) / 2);
+  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
+    const int32_t sz = (int32_t)i + 1;
+    for (int32_t sh = 1; sh <= sz; sh++) {
+      const float w = sig_identity(sh, sz, kmerSize);
+      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &w, 4);
+    }
+  });
+  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
+  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
+  uint32_t minBits; memcpy(&minBits, &lowest, 4);
+
+  TRY(B.get(OUT, R * (size_t)k * 16, (void **)&dOut)); TRY(B.get(CNT, R * 4, (void **)&dCnt));
+  // strip height: 4 bytes per cell inside a share of what is free now; the grid of the 4 x 4 tiles bounds it too
+  size_t freeB = 0, totalB = 0;
+  TRY(ani_device_memory(ctx, &freeB, &totalB));
+  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)ld));
+  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
+  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, R), 4 * 65535));
+  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat));
+  const size_t piece = std::max<size_t>(1, ((size_t)1 << 21) / (size_t)k);      // rows per copy: 32 MiB of staging at the most
+  ani_signeighbor_t *stage = nullptr; int32_t *stageCnt = nullptr;
+  TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)h) * (size_t)k * 16, (void **)&stage));
+  TRY(pinned_buffer(ctx, 1, (size_t)h * 4, (void **)&stageCnt));
+  for (uint64_t r0 = (uint64_t)rowBegin; r0 < (uint64_t)rowEnd; r0 += h) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, (uint64_t)rowEnd), rows1 = r1 - (uint32_t)r0;
+    const size_t at = (size_t)(r0 - (uint64_t)rowBegin);
+    signeigh_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
+    hipLaunchKernelGGL(k_signeigh_select, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)rowBegin, (uint32_t)nG, minShared,
+                       (const uint32_t *)dTable, minBits, k, dOut, dCnt);
+    HIP_TRY(hipGetLastError());
+    ctx->sigNeighStrips++;
+    HIP_TRY(hipMemcpyAsync(stageCnt, dCnt + at, (size_t)rows1 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(count + at, stageCnt, (size_t)rows1 * 4);
+    for (size_t p0 = 0; p0 < rows1; p0 += piece) {
+      const size_t m = std::min<size_t>(piece, rows1 - p0) * (size_t)k;
+      HIP_TRY(hipMemcpyAsync(stage, dOut + (at + p0) * (size_t)k, m * 16, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      memcpy(out + (at + p0) * (size_t)k, stage, m * 16);
+    }
+  }
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -1694,5 +1785,30 @@ int ani_signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, i
   HIP_TRY(hipSetDevice(ctx->device));
   return signature_pairs(ctx, sig, len, nGenomes, size, kmerSize, minShared, rows, n);
 }
+
+
+int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                            float minIdentity, int32_t k, int32_t rowBegin, int32_t rowEnd, ani_signeighbor_t *out, int32_t *count)
+{
+  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (k < 1 || k > ani::kSigNeighMaxK) return fail(ANI_ERR_ARG, "k %d outside [1, %d]", k, ani::kSigNeighMaxK);
+  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the neighbour lists take at most 2^30", nGenomes);
+  if (rowBegin < 0 || rowBegin > rowEnd || rowEnd > nGenomes) return fail(ANI_ERR_ARG, "rows [%d, %d) outside [0, %d]", rowBegin, rowEnd, nGenomes);
+  ctx->sigNeighStrips = 0;
+  if (nGenomes == 0 || rowBegin == rowEnd) return ANI_OK;
+  if (!sig || !len || !out || !count) return fail(ANI_ERR_ARG, "null argument");
+  for (int32_t g = 0; g < nGenomes; g++)
+    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return signature_neighbors(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, k, rowBegin, rowEnd, out, count); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_neighbors_strips(const ani_ctx *ctx) { return ctx ? ctx->sigNeighStrips : 0; }
 
 }  // extern "C"

@@ -362,6 +362,7 @@ struct ani_ctx {
   uint64_t l2CodeLimit = 0xfffffff0ull;
   int treeSingleRounds = 0;                                                        // spanning-forest rounds of the last ani_tree_single[_sketch] (ani_tree_single_rounds)
   std::vector<uint64_t> sigStripEdges;                                             // edges kept per strip of the last ani_tree_single_sketch
+  int sigNeighStrips = 0;                                                          // strips of the last ani_signature_neighbors
   // minimizers per index chunk (env ANI_MAX_INDEX_MINIMIZERS); indices are 32 bit
   uint64_t maxIndexMinimizers = 1700000000ull;
   // (engine_map.hip checks them against kernels/l1.hpp)           // env ANI_TEST_L1_FILTER_MIN / ANI_TEST_L1_LDS_MAX, read by ani_init (tests: per engine, not

@@ -9,7 +9,8 @@
 // single-linkage tree and, in a .mst file, their minimum spanning tree, ani_tree_single).  `--sketchANI` (extension) adds a .sketch
 // file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
 // tree that estimate for the pairs without a .matrix cell (streamed through ani_tree_single_sketch for a single-linkage tree of more
-// than 65 536 genomes).  Sketch / Map / computeCGI run on the GPU(s)
+// than 65 536 genomes), `--sketchNeighbors K` a .neighbors file (the K nearest genomes of every genome under that estimate,
+// ani_signature_neighbors: any number of genomes).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -73,7 +74,10 @@ struct Options {
   bool treeSingle = false;                             // --treeMethod single: their single-linkage tree instead, and the .mst file
   bool sketchANI = false, treeFill = false;            // --sketchANI: the .sketch file; --treeFill sketch: sketch estimates for the tree's missing pairs
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
-  bool signatures() const { return sketchANI || treeFill; }
+  int sketchNeighbors = 0;                             // --sketchNeighbors K: the .neighbors file (0 = off)
+  bool signatures() const { return sketchANI || treeFill || sketchNeighbors > 0; }
+  // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
+  bool pairStep() const { return sketchANI || (treeFill && !(tree && treeSingle)); }
   // --tree --treeMethod single --treeFill sketch alone: the one use of the genome sketches that can be streamed (ani_tree_single_sketch)
   bool streamable() const { return tree && treeSingle && treeFill && !sketchANI; }
   std::vector<std::string> refs, queries;
@@ -92,7 +96,7 @@ struct Options {
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
-    "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--sketchNeighbors <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -121,7 +125,10 @@ struct Options {
     "     --sketchANI also output a Mash-style ANI estimate between the genomes, from the smallest minimizer hashes of each genome\n"
     "                 (.sketch: genome, genome, estimate, shared/size); the queries must be among the references [disabled by default]\n"
     "     --sketchSize <value>  hashes per genome sketch, 1 to 4096 [default : 1000]\n"
-    "     --sketchMinANI <value>  smallest estimate --sketchANI reports [default : 70]\n"
+    "     --sketchMinANI <value>  smallest estimate --sketchANI and --sketchNeighbors report [default : 70]\n"
+    "     --sketchNeighbors <value>  also output, for every genome, its nearest genomes under that estimate, at most this many (1 to\n"
+    "                 1024), nearest first (.neighbors: genome, neighbour, estimate, shared/size; NA for a genome without one); any\n"
+    "                 number of genomes; the queries must be among the references [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -185,6 +192,8 @@ Options parse(int argc, char **argv)
       if (o.sketchSize < 1 || o.sketchSize > 4096) { std::cerr << "ERROR, --sketchSize takes a size from 1 to 4096" << std::endl; exit(1); } }
     else if (a == "--sketchMinANI") { o.sketchMinANI = (float)atof(need(i)); sketchMinANI = true;
       if (!(o.sketchMinANI >= 0.0f && o.sketchMinANI <= 100.0f)) { std::cerr << "ERROR, --sketchMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--sketchNeighbors") { o.sketchNeighbors = atoi(need(i));
+      if (o.sketchNeighbors < 1 || o.sketchNeighbors > 1024) { std::cerr << "ERROR, --sketchNeighbors takes a count from 1 to 1024" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -200,7 +209,7 @@ Options parse(int argc, char **argv)
   if (treeMethod && !o.tree) { std::cerr << "ERROR, --treeMethod needs --tree" << std::endl; exit(1); }
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
-  if (sketchMinANI && !o.sketchANI) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
+  if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -536,17 +545,18 @@ struct SigTable {
 };
 SigTable g_sigs;
 
-// --sketchANI / --treeFill sketch need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
+// --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
-// no ceiling: its sketch pairs are streamed (write_tree_single_streamed).
+// no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
 void check_sketch_genomes(const Options &o)
 {
   std::unordered_set<std::string> refs(o.refs.begin(), o.refs.end());
-  if (refs.size() > 65536 && !o.streamable()) {
+  if (refs.size() > 65536 && o.pairStep()) {
     std::cerr << "ERROR, --sketchANI and --treeFill sketch take at most 65536 genomes, this run has " << refs.size() << std::endl; exit(1); }
   for (auto &q : o.queries)
     if (!refs.count(q)) {
-      std::cerr << "ERROR, --sketchANI and --treeFill sketch compare the reference genomes: query " << q << " is not among the references" << std::endl;
+      std::cerr << "ERROR, --sketchANI" << (o.sketchNeighbors ? ", --sketchNeighbors" : "") << " and --treeFill sketch compare the reference genomes: query " << q
+                << " is not among the references" << std::endl;
       exit(1);
     }
 }
@@ -1529,6 +1539,32 @@ void write_tree_single_streamed(const Options &o, const std::string &path, const
   write_mst(mstPath, mc, edges, height, fill);
 }
 
+// ---- --sketchNeighbors K: the K nearest genomes of every .matrix genome under the sketch estimate, at least --sketchMinANI
+// (ani_signature_neighbors on the first device, minShared = 1: the lists come off the device, the pairs never exist on the host, and
+// there is no genome ceiling).  .neighbors: genomes in .matrix order, one line per neighbour, nearest first: genome, neighbour, estimate
+// as .sketch prints it, shared/size; a genome without a neighbour has one line of NA.
+void write_neighbors(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const size_t n = mc.names.size(), K = (size_t)o.sketchNeighbors;
+  std::vector<uint32_t> sig; std::vector<int32_t> len;
+  matrix_signatures(o, mc, sig, len);
+  std::vector<ani_signeighbor_t> nb(n * K); std::vector<int32_t> count(n);
+  if (ani_signature_neighbors(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchMinANI, o.sketchNeighbors, 0, (int32_t)n, nb.data(),
+                              count.data())) die("ani_signature_neighbors");
+  trace("sketch neighbours found");
+  BufferedFile f(o.out + ".neighbors");
+  for (size_t g = 0; g < n; g++) {
+    if (!count[g]) f.out << mc.names[g] << "\tNA\tNA\tNA\n";
+    for (size_t i = 0; i < (size_t)count[g]; i++) {
+      const ani_signeighbor_t &r = nb[g * K + i];
+      f.out << mc.names[g] << "\t" << mc.names[(size_t)r.neighbor] << "\t" << r.identity << "\t" << r.shared << "/" << r.size << "\n";
+    }
+  }
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".neighbors" << std::endl; exit(1); }
+  trace("sketch neighbours written");
+}
+
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
 // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
 // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
@@ -1637,12 +1673,13 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   MatrixCells mc;
-  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI) mc = matrix_cells(o, res.rows, trusted);
+  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
   const char *streamEnv = getenv("ANI_TEST_CLI_SINGLE_STREAM");
   const bool streamed = o.streamable() && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
-  if (o.signatures() && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if ((o.sketchANI || o.treeFill) && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (o.sketchNeighbors) write_neighbors(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (streamed) write_tree_single_streamed(o, o.out + ".newick", o.out + ".mst", su.dev[0].ctx, ap.kmerSize, mc);
   else if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)
   else if (o.tree && o.treeSingle) write_tree_single(o.out + ".newick", o.out + ".mst", su.dev[0].ctx, mc, fill);

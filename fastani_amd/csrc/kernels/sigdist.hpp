@@ -129,6 +129,20 @@ static __global__ __launch_bounds__(kTPB) void k_sigpair_stage(const uint32_t *_
 // row pitch (sigpair_launch in engine_map.hip); pairs with b <= a, and genomes beyond n, are skipped.
 // sigpair_tile is the tile itself, shared with the strip kernel (sigstrip.hpp): tile coordinates count from genome `base`, rows end at
 // rowEnd, and the cell of (a, b) is mat[(a - base) * ld + b].  The whole matrix is base = 0, rowEnd = n.
+// the merge of one pair, rows A and B of lengths la and lb (in LDS): shared << 16 | size
+__device__ __forceinline__ uint32_t sig_merge_rows(const uint32_t *A, int32_t la, const uint32_t *B, int32_t lb, int32_t size)
+{
+  int32_t pa = 0, pb = 0, steps = 0, shared = 0;
+  while (steps < size && pa < la && pb < lb) {
+    const uint32_t x = A[pa], y = B[pb];
+    pa += x <= y; pb += y <= x; shared += x == y;
+    steps++;
+  }
+  int32_t u = steps + (la - pa) + (lb - pb);
+  if (u > size) u = size;
+  return ((uint32_t)shared << 16) | (uint32_t)u;
+}
+
 template <int T>
 __device__ __forceinline__ void sigpair_tile(uint32_t *tile, int32_t *tileLen, const uint32_t *__restrict__ sig, const int32_t *__restrict__ len, uint32_t n,
     uint32_t base, uint32_t rowEnd, int32_t pitch, int32_t size, uint32_t *__restrict__ mat, uint64_t ld)
@@ -153,16 +167,7 @@ __device__ __forceinline__ void sigpair_tile(uint32_t *tile, int32_t *tileLen, c
   if (a >= b || b >= n || a >= rowEnd) return;
   const uint32_t rb = diag ? j : T + j;
   const uint32_t *A = tile + i * (uint32_t)pitch, *B = tile + rb * (uint32_t)pitch;
-  const int32_t la = tileLen[i], lb = tileLen[rb];
-  int32_t pa = 0, pb = 0, steps = 0, shared = 0;
-  while (steps < size && pa < la && pb < lb) {
-    const uint32_t x = A[pa], y = B[pb];
-    pa += x <= y; pb += y <= x; shared += x == y;
-    steps++;
-  }
-  int32_t u = steps + (la - pa) + (lb - pb);
-  if (u > size) u = size;
-  mat[(a - base) * ld + b] = ((uint32_t)shared << 16) | (uint32_t)u;
+  mat[(a - base) * ld + b] = sig_merge_rows(A, tileLen[i], B, tileLen[rb], size);
 }
 
 template <int T, int WORDS>

@@ -441,6 +441,40 @@ int ani_tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_
                            int32_t *children, float *height, int32_t *edges /* may be null */, uint8_t *source /* may be null */);
 int ani_tree_single_sketch_strips(const ani_ctx *ctx, uint64_t *edgesPerStrip, size_t cap);
 
+/* ---- nearest neighbours of every genome under the whole-genome sketch estimate, streamed (no counterpart in the reference; DESIGN.md
+ * section 2.17).  For each genome of a range of rows, its k closest relatives among all genomes and how close they are: O(n k) of output
+ * from the O(n^2) comparisons, which never leave the device.  There is no 65 536 ceiling.
+ * 1. Defined by composition.  P = the pairs ani_signature_pairs(sig, len, nGenomes, size, kmerSize, minShared) would return, were it free
+ *    of its ceiling; shared, size and identity of a pair are exactly its rules 2 and 3.
+ * 2. The candidates of genome g are the pairs of P that contain g and have identity >= minIdentity; the other genome of the pair is the
+ *    neighbour.
+ * 3. Candidates are ordered by identity descending, then neighbour id ascending.  Identities are non-negative floats, so the order of
+ *    their values is the order of their bit patterns; a minIdentity of -0.0 is 0.
+ * 4. count[g - rowBegin] = min(k, candidates of g).
+ * 5. out[(g - rowBegin) * k + i] is the i-th candidate of g, for i < count[g - rowBegin].
+ * 6. The unused slots of a list are {-1, 0, 0, 0.0f}.
+ * 7. Only the genomes of [rowBegin, rowEnd) get lists; their neighbours come from all of [0, nGenomes).  Rows are independent: a caller
+ *    may split the range, or ask for new genomes only.
+ * 8. ANI_ERR_ARG: a null pointer, nGenomes < 0, size outside [1, 4096], kmerSize outside [1, 16], minShared < 1, minIdentity outside
+ *    [0, 100] (NaN included), k outside [1, 1024], not 0 <= rowBegin <= rowEnd <= nGenomes, a len outside [0, size], a signature that
+ *    does not ascend strictly inside its len.
+ * 9. ANI_ERR_LIMIT: nGenomes > 2^30.
+ * 10. The checks of the scalar arguments run before any allocation.
+ * 11. nGenomes == 0 or rowBegin == rowEnd: ANI_OK after the scalar checks, nothing is read or written; sig, len, out and count may
+ *    then be null.
+ * 12. The result depends on no schedule, no reduction order and no strip height.
+ * 13. Memory.  The rows of the range go through the device a strip at a time.  Device: 8 size nGenomes bytes while the signatures are
+ *    staged (half of it after), 2 size^2 bytes of identities, one strip of rows x nGenomes 4-byte cells, whose height follows the free
+ *    device memory, and 16 k + 4 bytes per row of the range.  Nothing follows nGenomes^2.  ANI_TEST_SIG_STRIP_ROWS (tests) forces a
+ *    strip height.
+ * ani_signature_neighbors_strips: the strips the context's last ani_signature_neighbors call took; 0 if it needed none or there was no
+ * call (tools/sketch_probe.py reports it). */
+typedef struct { int32_t neighbor, shared, size; float identity; } ani_signeighbor_t;   /* 16 bytes */
+int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
+                            int32_t minShared, float minIdentity, int32_t k, int32_t rowBegin, int32_t rowEnd,
+                            ani_signeighbor_t *out /* [(rowEnd - rowBegin) * k] */, int32_t *count /* [rowEnd - rowBegin] */);
+int ani_signature_neighbors_strips(const ani_ctx *ctx);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */

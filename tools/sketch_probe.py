@@ -7,6 +7,11 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
     python tools/sketch_probe.py --reps 1        timed calls per case (default 3)
     python tools/sketch_probe.py --min-shared 1  the minShared of the pair call (default: above every pair, so no row comes back
                                                  and the time is the comparison's; with 1 the read-back of the rows is included)
+    python tools/sketch_probe.py --neighbors     ani_signature_neighbors instead, at 1 000 / 10 000 / 65 536 /
+                                                 90 000 genomes, minShared 1, minIdentity 0, --k neighbours (default 10): the call, its
+                                                 strips and, up to --compose-max genomes (default 10 000: beyond it the pair rows no
+                                                 longer fit a host comfortably, 43 GB at 65 536), ani_signature_pairs at minShared 1
+                                                 plus a numpy top-k over its rows, timed and compared with the call's lists
 
 Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
 smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
@@ -67,13 +72,73 @@ def timed(fn, reps):
     return float(np.median(t))
 
 
+def numpy_top_k(pairs, n, k):
+    """rules 2 - 6 of ani_signature_neighbors over the pair rows, minIdentity 0: a dense matrix of keys identityBits << 32 |
+    (0xffffffff - neighbour), 0 where there is no pair, the k largest of each row by partition, then sorted"""
+    from fastani_amd.api import NEIGHBOR_DT
+    a, b = pairs["a"].astype(np.int64), pairs["b"].astype(np.int64)
+    ident = pairs["identity"].view(np.uint32).astype(np.uint64) << np.uint64(32)
+    key = np.zeros((n, n), dtype=np.uint64)
+    key[a, b] = ident | (np.uint64(0xffffffff) - b.astype(np.uint64))
+    key[b, a] = ident | (np.uint64(0xffffffff) - a.astype(np.uint64))
+    shared = np.zeros((n, n), dtype=np.uint16)
+    size = np.zeros((n, n), dtype=np.uint16)
+    shared[a, b] = shared[b, a] = pairs["shared"]
+    size[a, b] = size[b, a] = pairs["size"]
+    kk = min(k, n)
+    top = -np.sort(-np.partition(key, n - kk, axis=1)[:, n - kk:].view(np.int64), axis=1)      # (keys are below 2^63: identities are at most 100.0)
+    top = top.astype(np.uint64)
+    have = top != 0
+    nb = np.where(have, np.uint64(0xffffffff) - (top & np.uint64(0xffffffff)), 0).astype(np.int64)
+    out = np.zeros((n, k), dtype=NEIGHBOR_DT)
+    out["neighbor"] = -1
+    rows = np.arange(n)[:, None]
+    out["neighbor"][:, :kk] = np.where(have, nb, -1)
+    out["shared"][:, :kk] = np.where(have, shared[rows, nb], 0)
+    out["size"][:, :kk] = np.where(have, size[rows, nb], 0)
+    out["identity"][:, :kk] = (top >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    return out, have.sum(axis=1).astype(np.int32)
+
+
+def neighbors(e, a):
+    rng = np.random.default_rng(1)
+    for n in (1000, 10000, 65536, 90000):
+        if a.only and n != a.only:
+            continue
+        sig, length = synthetic_signatures(rng, n)
+        got = {}
+        t = timed(lambda: got.__setitem__("r", e.signature_neighbors(sig, length, 16, a.k)), a.reps)
+        nb, count = got["r"]
+        line = "neighbors  n=%6d s=%d k=%d: %10.3f ms   %d strips   %d lists full, nearest estimate %.2f .. %.2f" % (
+            n, SIZE, a.k, t * 1e3, e.signature_neighbors_strips(), int((count == a.k).sum()), float(nb["identity"][:, 0].min()), float(nb["identity"][:, 0].max()))
+        if n <= a.compose_max:
+            rows = {}
+            tp = timed(lambda: rows.__setitem__("p", e.signature_pairs(sig, length, 16, 1)), a.reps)
+            want = {}
+            tk = timed(lambda: want.__setitem__("r", numpy_top_k(rows["p"], n, a.k)), a.reps)
+            wnb, wcount = want["r"]
+            assert np.array_equal(count, wcount) and all(np.array_equal(nb[f], wnb[f]) for f in ("neighbor", "shared", "size"))
+            assert np.array_equal(nb["identity"].view(np.uint32), wnb["identity"].view(np.uint32))
+            line += "   composition: pairs %.3f ms (%d rows) + numpy top-k %.3f ms = %.3f ms, lists identical" % (tp * 1e3, len(rows["p"]), tk * 1e3, (tp + tk) * 1e3)
+        else:
+            line += "   composition: not run"
+        print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", type=int, default=0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--min-shared", type=int, default=SIZE + 1)
     ap.add_argument("--skip-signatures", action="store_true")
+    ap.add_argument("--neighbors", action="store_true")
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
+    if a.neighbors:
+        import fastani_amd
+        neighbors(fastani_amd.engine(0), a)
+        return
     import torch
     import fastani_amd
     from fastani_amd.api import DeviceGenomes, Sketch
