@@ -72,6 +72,7 @@ int sort_arrays(const KeyT *keysIn, KeyT *keysOut, const ValT *valsIn, ValT *val
   constexpr bool kHasVal = !std::is_same<ValT, RadixNoVal>::value;
   if (endBit > (int)sizeof(KeyT) * 8) endBit = (int)sizeof(KeyT) * 8;
   if (beginBit < 0) beginBit = 0;
+  if (beginBit >= (int)sizeof(KeyT) * 8) return 9005;      // no such bit: the digit's shift would be by the key's width or more
   if (endBit < beginBit + 1) endBit = beginBit + 1;
   const int P = (endBit - beginBit + kRadixBits - 1) / kRadixBits;
   const uint64_t tiles = tiles_of(n);
