@@ -13,6 +13,7 @@
     Engine.signature_pairs(sig, len, k)    Mash-style ANI estimate between all pairs of signatures (no reference counterpart)
     Engine.tree_single_sketch(rows, n, sig, len, k)  tree_single with that estimate for every pair without rows, streamed strip by
                                            strip: nothing of size n^2 anywhere, no genome ceiling (no reference counterpart)
+    Engine.signature_screen(ref, len, qry, len, k_mer, k)  the k nearest references of every query under that estimate
     Engine.signature_neighbors(sig, len, k_mer, k)  the k nearest neighbours of every genome under that estimate, streamed strip by
                                            strip, no genome ceiling (no reference counterpart)
 
@@ -138,6 +139,9 @@ def _bind(lib):
         "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
         "ani_signature_neighbors": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
         "ani_signature_neighbors_strips": (C.c_int, [vp]),
+        "ani_signature_screen": (C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, vp]),
+        "ani_signature_screen_strips": (C.c_int, [vp]),
+        "ani_signature_screen_tile": (None, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -545,6 +549,36 @@ class Engine:
     def signature_neighbors_strips(self):
         """strips the last signature_neighbors call of this engine took (ani_signature_neighbors_strips)"""
         return int(self.lib.ani_signature_neighbors_strips(self.h))
+
+    def signature_screen(self, ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared=1, min_identity=0.0):
+        """for every query signature its k nearest references under the estimate of signature_pairs, identity >= min_identity, nearest
+        first and ties by ascending reference id (ani_signature_screen; the semantics are in ani_abi.h).  Only pairs of a query and a
+        reference are compared; the queries stream through the device a strip at a time, and neither side has a 65 536 ceiling.
+        -> (neighbors, count): NEIGHBOR_DT (nQry, k) of reference ids, the unused slots (-1, 0, 0, 0.0), and int32 (nQry,)."""
+        ref_sig, qry_sig = (np.ascontiguousarray(x, dtype=np.uint32) for x in (ref_sig, qry_sig))
+        ref_length, qry_length = (np.ascontiguousarray(x, dtype=np.int32) for x in (ref_length, qry_length))
+        if ref_sig.ndim != 2 or ref_length.shape != (ref_sig.shape[0],) or qry_sig.ndim != 2 or qry_length.shape != (qry_sig.shape[0],):
+            raise ValueError("ref_sig and qry_sig must be (n, size) and the lengths (n,)")
+        if ref_sig.shape[1] != qry_sig.shape[1]:
+            raise ValueError("the references have signatures of size %d, the queries of size %d" % (ref_sig.shape[1], qry_sig.shape[1]))
+        (nr, size), nq, k = ref_sig.shape, qry_sig.shape[0], int(k)
+        out = np.zeros((nq, max(k, 0)), dtype=NEIGHBOR_DT)
+        count = np.zeros(nq, dtype=np.int32)
+        self._chk(self.lib.ani_signature_screen(self.h, ref_sig.ctypes.data if nr else None, ref_length.ctypes.data if nr else None, nr,
+                                                qry_sig.ctypes.data if nq else None, qry_length.ctypes.data if nq else None, nq, size, int(kmer_size),
+                                                int(min_shared), float(min_identity), k, out.ctypes.data if out.size else None,
+                                                count.ctypes.data if nq else None))
+        return out, count
+
+    def signature_screen_strips(self):
+        """strips the last signature_screen call of this engine took (ani_signature_screen_strips)"""
+        return int(self.lib.ani_signature_screen_strips(self.h))
+
+    def signature_screen_tile(self):
+        """(queries, references) of the merge tile of the last strip of this engine's last signature_screen call (ani_signature_screen_tile)"""
+        tq, tr = C.c_int32(0), C.c_int32(0)
+        self.lib.ani_signature_screen_tile(self.h, C.byref(tq), C.byref(tr))
+        return tq.value, tr.value
 
 
 class FragmentSet:

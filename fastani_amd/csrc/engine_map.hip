@@ -19,6 +19,7 @@
 #include "kernels/sigdist.hpp"
 #include "kernels/sigstrip.hpp"
 #include "kernels/signeigh.hpp"
+#include "kernels/sigscreen.hpp"
 
 namespace anih {
 using namespace ani;
@@ -1388,6 +1389,21 @@ int tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG
 }
 
 // ---- nearest neighbours under the sketch estimate (ani_signature_neighbors) ----
+// bits(identity) of every (shared, size') with 1 <= shared <= size' <= size: rule 3 in double on the host
+static std::vector<uint32_t> sig_identity_table(int32_t size, int32_t kmerSize)
+{
+  const size_t S = (size_t)size;
+  std::vector<uint32_t> table(S * (S + 1) / 2);
+  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
+    const int32_t sz = (int32_t)i + 1;
+    for (int32_t sh = 1; sh <= sz; sh++) {
+      const float w = sig_identity(sh, sz, kmerSize);
+      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &w, 4);
+    }
+  });
+  return table;
+}
+
 // the rectangular tiles by row pitch, as sigpair_launch: rows [r0, r1), all columns
 static void signeigh_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
                             uint64_t ld)
@@ -1428,16 +1444,7 @@ int signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, i
   if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
   B.b[RAW].release();
 
-  // bits(identity) of every (shared, size'): rule 3 in double on the host
-  const size_t S = (size_t)size;
-  std::vector<uint32_t> table(S * (S + 1) / 2);
-  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
-    const int32_t sz = (int32_t)i + 1;
-    for (int32_t sh = 1; sh <= sz; sh++) {
-      const float w = sig_identity(sh, sz, kmerSize);
-      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &w, 4);
-    }
-  });
+  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
   TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
   HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1472,6 +1479,117 @@ int signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, i
       HIP_TRY(hipMemcpyAsync(stage, dOut + (at + p0) * (size_t)k, m * 16, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       memcpy(out + (at + p0) * (size_t)k, stage, m * 16);
+    }
+  }
+  return ANI_OK;
+}
+
+// ---- the nearest references of every query under the sketch estimate (ani_signature_screen) ----
+// The tile by strip height and row pitch.  A strip of at least T queries, T the edge of the pair tiles at this pitch, takes the square
+// tile; a lower one the thin tile of one query and 64 references, whose LDS is the query row alone.  ANI_TEST_SIG_SCREEN_SHAPE = square or
+// thin (tests, tools/sketch_probe.py) forces a shape.  shape[0 .. 2) = TQ, TR of the tile taken.
+static void sigscreen_launch(hipStream_t st, const uint32_t *refSig, const int32_t *refLen, uint32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, uint32_t q0,
+                             uint32_t q1, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld, int32_t *shape)
+{
+  const uint32_t T = pitch <= 1024 ? 16u : pitch <= 2048 ? 8u : 4u;
+  bool thin = q1 - q0 < T;
+  if (const char *ev = getenv("ANI_TEST_SIG_SCREEN_SHAPE")) { if (!strcmp(ev, "square")) thin = false; else if (!strcmp(ev, "thin")) thin = true; }
+  auto tiles = [&](uint32_t tq, uint32_t tr) { return dim3((nRef + tr - 1) / tr, (q1 - q0 + tq - 1) / tq); };
+#define ANI_SCREEN(TQ, TR, WORDS, LANES) hipLaunchKernelGGL((k_sigscreen_merge<TQ, TR, WORDS>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, \
+                                                            qryLen, q0, q1, pitch, size, mat, ld)
+  if (thin) {
+    if (pitch <= 1024) ANI_SCREEN(1, kSigScreenThinRefs, 1024, 64);
+    else ANI_SCREEN(1, kSigScreenThinRefs, kSigMaxSize, 64);
+  }
+  else if (pitch <= 256) ANI_SCREEN(16, 16, 8192, 256);
+  else if (pitch <= 1024) ANI_SCREEN(16, 16, kSigTileWords, 256);
+  else if (pitch <= 2048) ANI_SCREEN(8, 8, kSigTileWords, 64);
+  else ANI_SCREEN(4, 4, kSigTileWords, 64);
+#undef ANI_SCREEN
+  shape[0] = thin ? 1 : (int32_t)T; shape[1] = thin ? kSigScreenThinRefs : (int32_t)T;
+}
+
+// one set of signatures to the device: as given, then at a pitch of whole quads by k_sigpair_stage, which flags a row that does not ascend
+static int sigscreen_stage(ani_ctx *ctx, DevBuf &raw, DevBuf &staged, DevBuf &lens, const uint32_t *sig, const int32_t *len, size_t n, int32_t size, int32_t pitch,
+                           uint32_t *dFlags)
+{
+  hipStream_t st = ctx->stream;
+  TRY(raw.ensure(n * (size_t)size * 4)); TRY(staged.ensure(n * (size_t)pitch * 4)); TRY(lens.ensure(n * 4));
+  HIP_TRY(hipMemcpyAsync(raw.p, sig, n * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(lens.p, len, n * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)n), dim3(kTPB), 0, st, (const uint32_t *)raw.p, (const int32_t *)lens.p, size, pitch, staged.as<uint32_t>(), dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));                                   // (sig and len are the caller's pageable memory)
+  raw.release();
+  return ANI_OK;
+}
+
+// Both sets are staged and validated as for ani_signature_pairs, the references once; the identity bits of every (shared, size') come
+// from the host; the queries go through the device a strip at a time: the strip's cells against every reference, then the k nearest of
+// each query, written into the query's place of the output and copied back through page-locked staging.  Device memory: either set
+// twice while it is staged and once after, 2 s (s + 1) bytes of identities, 16 k + 4 bytes per query, and one strip (kSigStripShare of
+// what is free then, 4 bytes per cell).  Nothing follows nRef * nQry.
+int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                     int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+{
+  enum { RRAW, RLEN, RSIG, QRAW, QLEN, QSIG, FLAGS, TABLE, MAT, OUT, CNT, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t R = (size_t)nRef, Q = (size_t)nQry;
+  const int32_t pitch = (size + 3) & ~3;
+  const uint64_t ld = (R + 3) & ~(uint64_t)3;
+  uint32_t *dFlags, *dTable, *dMat; int32_t *dCnt; uint4 *dOut;
+  TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  if (R) { TRY(sigscreen_stage(ctx, B.b[RRAW], B.b[RSIG], B.b[RLEN], refSig, refLen, R, size, pitch, dFlags)); }
+  TRY(sigscreen_stage(ctx, B.b[QRAW], B.b[QSIG], B.b[QLEN], qrySig, qryLen, Q, size, pitch, dFlags));
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  if (!R) {                                                            // no references: every list is empty
+    for (size_t i = 0; i < Q * (size_t)k; i++) out[i] = ani_signeighbor_t{-1, 0, 0, 0.0f};
+    std::fill(count, count + Q, 0);
+    return ANI_OK;
+  }
+  const uint32_t *dRefSig = B.b[RSIG].as<uint32_t>(), *dQrySig = B.b[QSIG].as<uint32_t>();
+  const int32_t *dRefLen = B.b[RLEN].as<int32_t>(), *dQryLen = B.b[QLEN].as<int32_t>();
+
+  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
+  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
+  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
+  uint32_t minBits; memcpy(&minBits, &lowest, 4);
+
+  TRY(B.get(OUT, Q * (size_t)k * 16, (void **)&dOut)); TRY(B.get(CNT, Q * 4, (void **)&dCnt));
+  // strip height: 4 bytes per cell inside a share of what is free now; the grid of the 4 x 4 tiles bounds it too
+  size_t freeB = 0, totalB = 0;
+  TRY(ani_device_memory(ctx, &freeB, &totalB));
+  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)ld));
+  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
+  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, Q), 65535));
+  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat));
+  const size_t piece = std::max<size_t>(1, ((size_t)1 << 21) / (size_t)k);      // queries per copy: 32 MiB of staging at the most
+  ani_signeighbor_t *stage = nullptr; int32_t *stageCnt = nullptr;
+  TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)h) * (size_t)k * 16, (void **)&stage));
+  TRY(pinned_buffer(ctx, 1, (size_t)h * 4, (void **)&stageCnt));
+  for (uint64_t q0 = 0; q0 < Q; q0 += h) {
+    const uint32_t q1 = (uint32_t)std::min<uint64_t>(q0 + h, Q), rows1 = q1 - (uint32_t)q0;
+    sigscreen_launch(st, dRefSig, dRefLen, (uint32_t)nRef, dQrySig, dQryLen, (uint32_t)q0, q1, pitch, size, dMat, ld, ctx->sigScreenTile);
+    hipLaunchKernelGGL(k_sigscreen_select, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)q0, (uint32_t)nRef, minShared,
+                       (const uint32_t *)dTable, minBits, k, dOut, dCnt);
+    HIP_TRY(hipGetLastError());
+    ctx->sigScreenStrips++;
+    HIP_TRY(hipMemcpyAsync(stageCnt, dCnt + q0, (size_t)rows1 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(count + q0, stageCnt, (size_t)rows1 * 4);
+    for (size_t p0 = 0; p0 < rows1; p0 += piece) {
+      const size_t m = std::min<size_t>(piece, rows1 - p0) * (size_t)k;
+      HIP_TRY(hipMemcpyAsync(stage, dOut + ((size_t)q0 + p0) * (size_t)k, m * 16, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      memcpy(out + ((size_t)q0 + p0) * (size_t)k, stage, m * 16);
     }
   }
   return ANI_OK;
@@ -1810,5 +1928,36 @@ int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *le
 }
 
 int ani_signature_neighbors_strips(const ani_ctx *ctx) { return ctx ? ctx->sigNeighStrips : 0; }
+
+int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                         int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+{
+  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
+  if (nRef < 0 || nQry < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (k < 1 || k > ani::kSigNeighMaxK) return fail(ANI_ERR_ARG, "k %d outside [1, %d]", k, ani::kSigNeighMaxK);
+  if (nRef > (1 << 30) || nQry > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d references, %d queries: the screen takes at most 2^30 of either", nRef, nQry);
+  ctx->sigScreenStrips = 0; ctx->sigScreenTile[0] = ctx->sigScreenTile[1] = 0;
+  if (nQry == 0) return ANI_OK;
+  if (!qrySig || !qryLen || !out || !count || (nRef > 0 && (!refSig || !refLen))) return fail(ANI_ERR_ARG, "null argument");
+  for (int32_t g = 0; g < nRef; g++)
+    if (refLen[g] < 0 || refLen[g] > size) return fail(ANI_ERR_ARG, "reference signature %d has length %d outside [0, %d]", g, refLen[g], size);
+  for (int32_t g = 0; g < nQry; g++)
+    if (qryLen[g] < 0 || qryLen[g] > size) return fail(ANI_ERR_ARG, "query signature %d has length %d outside [0, %d]", g, qryLen[g], size);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return signature_screen(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, out, count); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_screen_strips(const ani_ctx *ctx) { return ctx ? ctx->sigScreenStrips : 0; }
+
+void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t *tileRefs)
+{
+  if (tileQueries) *tileQueries = ctx ? ctx->sigScreenTile[0] : 0;
+  if (tileRefs) *tileRefs = ctx ? ctx->sigScreenTile[1] : 0;
+}
 
 }  // extern "C"

@@ -10,7 +10,8 @@
 // file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
 // tree that estimate for the pairs without a .matrix cell (streamed through ani_tree_single_sketch for a single-linkage tree of more
 // than 65 536 genomes), `--sketchNeighbors K` a .neighbors file (the K nearest genomes of every genome under that estimate,
-// ani_signature_neighbors: any number of genomes).  Sketch / Map / computeCGI run on the GPU(s)
+// ani_signature_neighbors: any number of genomes), `--sketchScreen K` a .screen file (the K nearest references of every query under that
+// estimate, ani_signature_screen: the queries need not be references).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -75,7 +76,9 @@ struct Options {
   bool sketchANI = false, treeFill = false;            // --sketchANI: the .sketch file; --treeFill sketch: sketch estimates for the tree's missing pairs
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
   int sketchNeighbors = 0;                             // --sketchNeighbors K: the .neighbors file (0 = off)
-  bool signatures() const { return sketchANI || treeFill || sketchNeighbors > 0; }
+  int sketchScreen = 0;                                // --sketchScreen K: the .screen file (0 = off)
+  bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0; }   // these compare the references with each other
+  bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
   bool pairStep() const { return sketchANI || (treeFill && !(tree && treeSingle)); }
   // --tree --treeMethod single --treeFill sketch alone: the one use of the genome sketches that can be streamed (ani_tree_single_sketch)
@@ -96,7 +99,7 @@ struct Options {
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
-    "             [--sketchNeighbors <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--sketchNeighbors <value>] [--sketchScreen <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -125,10 +128,13 @@ struct Options {
     "     --sketchANI also output a Mash-style ANI estimate between the genomes, from the smallest minimizer hashes of each genome\n"
     "                 (.sketch: genome, genome, estimate, shared/size); the queries must be among the references [disabled by default]\n"
     "     --sketchSize <value>  hashes per genome sketch, 1 to 4096 [default : 1000]\n"
-    "     --sketchMinANI <value>  smallest estimate --sketchANI and --sketchNeighbors report [default : 70]\n"
+    "     --sketchMinANI <value>  smallest estimate --sketchANI, --sketchNeighbors and --sketchScreen report [default : 70]\n"
     "     --sketchNeighbors <value>  also output, for every genome, its nearest genomes under that estimate, at most this many (1 to\n"
     "                 1024), nearest first (.neighbors: genome, neighbour, estimate, shared/size; NA for a genome without one); any\n"
     "                 number of genomes; the queries must be among the references [disabled by default]\n"
+    "     --sketchScreen <value>  also output, for every query genome, its nearest reference genomes under that estimate, at most\n"
+    "                 this many (1 to 1024), nearest first (.screen: query, reference, estimate, shared/size; NA for a query without\n"
+    "                 one); the queries need not be among the references; any number of genomes [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -194,6 +200,8 @@ Options parse(int argc, char **argv)
       if (!(o.sketchMinANI >= 0.0f && o.sketchMinANI <= 100.0f)) { std::cerr << "ERROR, --sketchMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--sketchNeighbors") { o.sketchNeighbors = atoi(need(i));
       if (o.sketchNeighbors < 1 || o.sketchNeighbors > 1024) { std::cerr << "ERROR, --sketchNeighbors takes a count from 1 to 1024" << std::endl; exit(1); } }
+    else if (a == "--sketchScreen") { o.sketchScreen = atoi(need(i));
+      if (o.sketchScreen < 1 || o.sketchScreen > 1024) { std::cerr << "ERROR, --sketchScreen takes a count from 1 to 1024" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -209,7 +217,7 @@ Options parse(int argc, char **argv)
   if (treeMethod && !o.tree) { std::cerr << "ERROR, --treeMethod needs --tree" << std::endl; exit(1); }
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
-  if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
+  if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors && !o.sketchScreen) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -545,6 +553,33 @@ struct SigTable {
 };
 SigTable g_sigs;
 
+// --sketchScreen: the signatures of the queries that are no references of the run, keyed by query index.  They are made as reference
+// signatures are — the query's uploaded genomes sketched as a reference set, then ani_sketch_signatures — because the fragment sketches
+// the mapping uses leave out what is shorter than a fragment.  A query that is a reference takes the reference's row (refOfQuery).
+struct QuerySigs {
+  SigTable table; std::vector<int64_t> refOfQuery;      // refOfQuery[q]: the reference with the query's name, or -1
+  void init(int size, const std::vector<std::string> &queries, const std::vector<std::string> &refs)
+  {
+    std::unordered_map<std::string, size_t> refOf;
+    for (size_t r = 0; r < refs.size(); r++) refOf.emplace(refs[r], r);
+    refOfQuery.assign(queries.size(), -1);
+    for (size_t q = 0; q < queries.size(); q++) { const auto it = refOf.find(queries[q]); if (it != refOf.end()) refOfQuery[q] = (int64_t)it->second; }
+    table.init(size, queries.size());
+  }
+  bool needed(size_t first, size_t n) const { for (size_t q = first; q < first + n; q++) if (refOfQuery[q] < 0) return true; return false; }
+  // the queries [first, first + n), which are the genomes of `batch`; returns the error, or ""
+  std::string sketch(ani_ctx *ctx, const ani_params_t &ap, const ani_seq_batch_t &batch, size_t first, size_t n)
+  {
+    if (!table.size || !needed(first, n)) return "";
+    ani_sketch *sk = nullptr;
+    if (ani_sketch_build(ctx, &ap, &batch, &sk)) return ani_last_error();
+    table.collect(sk, first, n);
+    ani_sketch_destroy(sk);
+    return "";
+  }
+};
+QuerySigs g_qsigs;
+
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
 // no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
@@ -599,7 +634,8 @@ Mode check_options(Options &o, const ani_params_t &ap)
     for (auto &r : o.refs) { r = nm; nm += r.size() + 1; }
     ani_free(names);
   }
-  if (o.signatures()) check_sketch_genomes(o);
+  if (o.compareRefs()) check_sketch_genomes(o);
+  if (o.sketchScreen) g_qsigs.init(o.sketchSize, o.queries, o.refs);   // (after a sketch file's names have taken the references' place)
   if (!streaming) o.devices.resize(1);            // the per-split / per-mapping paths are single-device
   if (!o.saveSketch.empty() && o.devices.size() > 1) { std::cerr << "ERROR, --saveSketch writes the sketch of one device: run it with --gpus 1" << std::endl;
     exit(1); }
@@ -945,6 +981,7 @@ struct Streaming {
         ani_seq_batch_t db = dev_view(u);
         ani_cgi_t *rows = nullptr; size_t nRows = 0;
         if (ani_map_cgi_batch(su.dev[d].ctx, shard[d].sk, &db, firstQ, &rows, &nRows)) { msg = ani_last_error(); return false; }
+        if (o.sketchScreen && !(msg = g_qsigs.sketch(su.dev[d].ctx, ap, db, (size_t)firstQ, b - a)).empty()) { ani_free(rows); return false; }
         sliceRows[k].assign(rows, rows + nRows);
         ani_free(rows);
         ani_get_counters(su.dev[d].ctx, &c1);
@@ -983,6 +1020,8 @@ struct Streaming {
             const size_t k = kk + w0;
             ani_seq_batch_t db = dev_view(u);
             if (ani_fragset_build(su.dev[d].ctx, &ap, &db, &qsets[k].f)) { msg = ani_last_error(); return false; }
+            if (o.sketchScreen && !(msg = g_qsigs.sketch(su.dev[d].ctx, ap, db, qrySlices[k].first - nRefFiles, qrySlices[k].second - qrySlices[k].first)).empty())
+              return false;
             qsets[k].dev = d; qsets[k].firstQuery = (int32_t)(qrySlices[k].first - nRefFiles);
             return true;
           });
@@ -1116,6 +1155,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
   SliceBatch qbAll; for (auto &fd : Q) qbAll.add(fd);
   ani_seq_batch_t qb = qbAll.batch();
   const int nRef = (int)o.refs.size(), nQry = (int)o.queries.size();
+  if (o.sketchScreen) { const std::string e = g_qsigs.sketch(ctx, ap, qb, 0, (size_t)nQry); if (!e.empty()) { std::cerr << "ERROR, query sketch: " << e << std::endl; exit(1); } }
   // the reference splits its references round-robin over the -t threads whatever the mode; the split only shows in the -s check
   // (per split) and in the order of the .visual rows (thread 0's queries first, core_genome_identity.cpp:142-163)
   const int nSplits = o.threads;
@@ -1565,6 +1605,40 @@ void write_neighbors(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixC
   trace("sketch neighbours written");
 }
 
+// ---- --sketchScreen K: the K nearest references of every query under the sketch estimate, at least --sketchMinANI
+// (ani_signature_screen on the first device, minShared = 1; the reference signatures are the collected table as it stands, the query
+// signatures a reference's row or the query's own).  .screen: queries in query-list order, one line per reference, nearest first, ties in
+// reference-list order: query, reference, estimate as .sketch prints it, shared/size; a query without a hit has one line of NA.
+void write_screen(const Options &o, ani_ctx *ctx, int kmerSize)
+{
+  const size_t nR = o.refs.size(), nQ = o.queries.size(), K = (size_t)o.sketchScreen, S = (size_t)g_sigs.size;
+  for (size_t r = 0; r < nR; r++) if (!g_sigs.have[r]) { std::cerr << "ERROR, no genome sketch of " << o.refs[r] << std::endl; exit(1); }
+  std::vector<uint32_t> qsig(nQ * S); std::vector<int32_t> qlen(nQ);
+  for (size_t q = 0; q < nQ; q++) {
+    const int64_t r = g_qsigs.refOfQuery[q];
+    if (r < 0 && !g_qsigs.table.have[q]) { std::cerr << "ERROR, no genome sketch of " << o.queries[q] << std::endl; exit(1); }
+    const SigTable &t = r >= 0 ? g_sigs : g_qsigs.table;
+    const size_t row = r >= 0 ? (size_t)r : q;
+    std::copy(t.sig.begin() + (std::ptrdiff_t)(row * S), t.sig.begin() + (std::ptrdiff_t)((row + 1) * S), qsig.begin() + (std::ptrdiff_t)(q * S));
+    qlen[q] = t.len[row];
+  }
+  std::vector<ani_signeighbor_t> nb(nQ * K); std::vector<int32_t> count(nQ);
+  if (ani_signature_screen(ctx, g_sigs.sig.data(), g_sigs.len.data(), (int32_t)nR, qsig.data(), qlen.data(), (int32_t)nQ, g_sigs.size, kmerSize, 1, o.sketchMinANI,
+                           o.sketchScreen, nb.data(), count.data())) die("ani_signature_screen");
+  trace("sketch screen done");
+  BufferedFile f(o.out + ".screen");
+  for (size_t q = 0; q < nQ; q++) {
+    if (!count[q]) f.out << o.queries[q] << "\tNA\tNA\tNA\n";
+    for (size_t i = 0; i < (size_t)count[q]; i++) {
+      const ani_signeighbor_t &r = nb[q * K + i];
+      f.out << o.queries[q] << "\t" << o.refs[(size_t)r.neighbor] << "\t" << r.identity << "\t" << r.shared << "/" << r.size << "\n";
+    }
+  }
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".screen" << std::endl; exit(1); }
+  trace("sketch screen written");
+}
+
 // ---- outputPhylip (computeCoreIdentity.hpp:353-448), streamed: the reference fills a dense N x N float matrix (32 GB at 90 k
 // genomes); here every trusted result becomes a (row, column, identity) entry, the entries are ordered by (row, column) with the
 // result order kept inside a cell (first value sets the cell, a later one averages: :411-421), and the lower triangle is written
@@ -1680,6 +1754,7 @@ int main(int argc, char **argv)
   const bool streamed = o.streamable() && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
   if ((o.sketchANI || o.treeFill) && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchNeighbors) write_neighbors(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (o.sketchScreen) write_screen(o, su.dev[0].ctx, ap.kmerSize);
   if (streamed) write_tree_single_streamed(o, o.out + ".newick", o.out + ".mst", su.dev[0].ctx, ap.kmerSize, mc);
   else if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)
   else if (o.tree && o.treeSingle) write_tree_single(o.out + ".newick", o.out + ".mst", su.dev[0].ctx, mc, fill);

@@ -59,29 +59,27 @@ static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_signe
   signeigh_tile<T>(tile, tileLen, sig, len, n, r0, r1, pitch, size, mat, ld);
 }
 
-// the identity bits of cell v = row[b] of genome a, if the pair is a candidate
+// the identity bits of cell v = row[b] of genome a, if the pair is a candidate.  SELF: the row is genome a's own among the columns, and
+// its cell (a, a) was never written; a row of other genomes (sigscreen.hpp: a query against the references) has no such cell.
+template <bool SELF>
 __device__ __forceinline__ bool signeigh_candidate(const uint32_t *__restrict__ row, uint32_t a, uint32_t b, int32_t minShared, const uint32_t *__restrict__ table,
                                                    uint32_t minBits, uint32_t *id)
 {
-  if (b == a) return false;                            // (the one cell of the row that was never written)
+  if (SELF && b == a) return false;                    // (the one cell of the row that was never written)
   const uint32_t v = row[b], shared = v >> 16, size = v & 0xffffu;
   if ((int32_t)shared < minShared || shared > size) return false;
   *id = table[sigstrip_entry(shared, size)];
   return *id >= minBits;
 }
 
-// One workgroup per row a = r0 + blockIdx.x of the strip; out and count are those of the whole row range, which begins at rowBegin.
-static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t *__restrict__ mat, uint64_t ld, uint32_t r0, uint32_t rowBegin, uint32_t n,
-                                                                 int32_t minShared, const uint32_t *__restrict__ table, uint32_t minBits, int32_t k,
-                                                                 uint4 *__restrict__ out, int32_t *__restrict__ count)
+// The select of one row of n cells by one workgroup: the list goes to o[0 .. k) and its length to *cnt.  hist, keys, ws, sel and cursor
+// are the workgroup's LDS (kSigNeighBins, kSigNeighMaxK, 8, 2 and 1 entries).  Shared by k_signeigh_select and k_sigscreen_select.
+template <bool SELF>
+__device__ __forceinline__ void signeigh_select_row(uint32_t *hist, uint64_t *keys, int *ws, uint32_t *sel, uint32_t *cursor, const uint32_t *__restrict__ row,
+                                                    uint32_t a, uint32_t n, int32_t minShared, const uint32_t *__restrict__ table, uint32_t minBits, int32_t k,
+                                                    uint4 *__restrict__ o, int32_t *__restrict__ cnt)
 {
-  __shared__ uint32_t hist[kSigNeighBins];
-  __shared__ uint64_t keys[kSigNeighMaxK];
-  __shared__ int ws[8];
-  __shared__ uint32_t sel[2], cursor;
   const uint32_t tid = threadIdx.x;
-  const uint32_t a = r0 + blockIdx.x;
-  const uint32_t *row = mat + (uint64_t)blockIdx.x * ld;
 
   // the identity t = prefix of the k-th largest key and `need`, the cells at t among the k; or every candidate, if there are at most k
   uint32_t prefix = 0, mask = 0;
@@ -93,7 +91,7 @@ static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t 
     block_barrier();
     for (uint32_t b = tid; b < n; b += kTPB) {
       uint32_t id;
-      if (signeigh_candidate(row, a, b, minShared, table, minBits, &id) && (id & mask) == prefix) atomicAdd(&hist[(id >> shift) & (uint32_t)(nb - 1)], 1u);
+      if (signeigh_candidate<SELF>(row, a, b, minShared, table, minBits, &id) && (id & mask) == prefix) atomicAdd(&hist[(id >> shift) & (uint32_t)(nb - 1)], 1u);
     }
     block_barrier();
     // thread t holds the bins top, top - 1, ..., top - 7: the scan runs from the largest digit down
@@ -117,16 +115,16 @@ static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t 
   const int m = all ? need : k;                        // the length of the list
   const int above = all ? m : k - need;                // cells above t (every candidate, if all are taken): by cursor, in any order
 
-  if (tid == 0) cursor = 0u;
+  if (tid == 0) *cursor = 0u;
   block_barrier();
   int eq = 0;                                          // cells at t seen so far
   for (uint32_t base = 0; base < n; base += kTPB) {
     const uint32_t b = base + tid;
     uint32_t id = 0;
-    const bool cand = b < n && signeigh_candidate(row, a, b, minShared, table, minBits, &id);
+    const bool cand = b < n && signeigh_candidate<SELF>(row, a, b, minShared, table, minBits, &id);
     const uint64_t key = ((uint64_t)id << 32) | (uint64_t)(0xffffffffu - b);
     if (cand && (all || id > prefix)) {
-      const uint32_t slot = atomicAdd(&cursor, 1u);
+      const uint32_t slot = atomicAdd(cursor, 1u);
       if (slot < (uint32_t)above) keys[slot] = key;
     }
     if (!all && eq < need) {                           // (the same in every thread)
@@ -139,7 +137,6 @@ static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t 
   }
   if (m > 0) block_sort(keys, m);                      // ascending; frames itself with barriers
 
-  uint4 *o = out + (uint64_t)(a - rowBegin) * (uint32_t)k;
   for (int i = tid; i < k; i += kTPB) {
     uint4 r;
     if (i < m) {
@@ -149,7 +146,21 @@ static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t 
     } else { r.x = 0xffffffffu; r.y = 0u; r.z = 0u; r.w = 0u; }
     o[i] = r;
   }
-  if (tid == 0) count[a - rowBegin] = m;
+  if (tid == 0) *cnt = m;
+}
+
+// One workgroup per row a = r0 + blockIdx.x of the strip; out and count are those of the whole row range, which begins at rowBegin.
+static __global__ __launch_bounds__(kTPB) void k_signeigh_select(const uint32_t *__restrict__ mat, uint64_t ld, uint32_t r0, uint32_t rowBegin, uint32_t n,
+                                                                 int32_t minShared, const uint32_t *__restrict__ table, uint32_t minBits, int32_t k,
+                                                                 uint4 *__restrict__ out, int32_t *__restrict__ count)
+{
+  __shared__ uint32_t hist[kSigNeighBins];
+  __shared__ uint64_t keys[kSigNeighMaxK];
+  __shared__ int ws[8];
+  __shared__ uint32_t sel[2], cursor;
+  const uint32_t a = r0 + blockIdx.x;
+  signeigh_select_row<true>(hist, keys, ws, sel, &cursor, mat + (uint64_t)blockIdx.x * ld, a, n, minShared, table, minBits, k,
+                            out + (uint64_t)(a - rowBegin) * (uint32_t)k, count + (a - rowBegin));
 }
 
 }  // namespace ani

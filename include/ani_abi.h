@@ -475,6 +475,40 @@ int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *le
                             ani_signeighbor_t *out /* [(rowEnd - rowBegin) * k] */, int32_t *count /* [rowEnd - rowBegin] */);
 int ani_signature_neighbors_strips(const ani_ctx *ctx);
 
+/* ---- screening of query genomes against reference genomes under the whole-genome sketch estimate, streamed (no counterpart in the
+ * reference).  For each query its k closest references and how close they are: a few new genomes against a
+ * large fixed set.  The two sets are separate arrays, and only pairs of a query and a reference are compared.
+ * 1. Defined by composition.  C = the signatures of the nRef references followed by the nQry queries, laid out as ani_sketch_signatures
+ *    lays out rows.  P = the pairs ani_signature_pairs(C, nRef + nQry, size, kmerSize, minShared) would return, were it free of its
+ *    ceiling; shared, size and identity of a pair are exactly its rules 2 and 3.
+ * 2. The candidates of query q are the pairs (r, nRef + q) of P with r < nRef and identity >= minIdentity; the neighbour is r, a
+ *    reference id.  Pairs between two queries or between two references play no part.  A query whose signature equals a reference's is
+ *    a candidate of that reference at identity 100.
+ * 3. Order, cut, records and unused slots are rules 3 - 6 of ani_signature_neighbors: identity descending, by bit pattern, then
+ *    reference id ascending; count[q] = min(k, candidates of q); out[q * k + i] is the i-th candidate of q for i < count[q]; the unused
+ *    slots are {-1, 0, 0, 0.0f}; a minIdentity of -0.0 is 0.
+ * 4. ANI_ERR_ARG: a null pointer, nRef < 0 or nQry < 0, size outside [1, 4096], kmerSize outside [1, 16], minShared < 1, minIdentity
+ *    outside [0, 100] (NaN included), k outside [1, 1024], a len outside [0, size], a signature in either set that does not ascend
+ *    strictly inside its len.
+ * 5. ANI_ERR_LIMIT: nRef > 2^30 or nQry > 2^30.  The checks of the scalar arguments run before any allocation.
+ * 6. nQry == 0: ANI_OK after the scalar checks, nothing is read or written; the array pointers may then be null.  nRef == 0 with
+ *    nQry > 0: every count is 0 and every slot is unused; refSig and refLen may be null.
+ * 7. The result depends on no schedule, no reduction order, no strip height and no tile shape.
+ * 8. Memory.  The reference signatures are staged once; the queries go through the device a strip at a time.  Device: 8 size bytes per
+ *    genome of either set while it is staged (half of it after), 2 size^2 bytes of identities, one strip of rows x nRef 4-byte cells,
+ *    whose height follows the free device memory, and 16 k + 4 bytes per query.  Nothing follows nRef * nQry, and there is no 65 536
+ *    ceiling on either side.  ANI_TEST_SIG_STRIP_ROWS (tests) forces a strip height, ANI_TEST_SIG_SCREEN_SHAPE = square | thin the
+ *    shape of the merge tile, which otherwise follows the strip height.
+ * 9. ani_signature_screen_strips: the strips the context's last ani_signature_screen call took; 0 if it needed none or there was no
+ *    call.  ani_signature_screen_tile: the queries x references of the merge tile of that call's last strip, 0 x 0 likewise
+ *    (tools/sketch_probe.py reports both). */
+int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef,
+                         const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                         int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k,
+                         ani_signeighbor_t *out /* [nQry * k] */, int32_t *count /* [nQry] */);
+int ani_signature_screen_strips(const ani_ctx *ctx);
+void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t *tileRefs);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */

@@ -12,6 +12,12 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
                                                  strips and, up to --compose-max genomes (default 10 000: beyond it the pair rows no
                                                  longer fit a host comfortably, 43 GB at 65 536), ani_signature_pairs at minShared 1
                                                  plus a numpy top-k over its rows, timed and compared with the call's lists
+    python tools/sketch_probe.py --screen        ani_signature_screen at 1 / 16 / 1 000 queries x 10 000 references,
+                                                 minShared 1, minIdentity 0, --k references (default 10): the call under the tile shape
+                                                 its strip height selects and under either forced shape, its strips and tile, and the
+                                                 route without it: ani_signature_neighbors over references + queries for the query rows
+                                                 at k = 1024, cut to the references on the host; lists compared.  Every line: min .. max
+                                                 of the timed calls, by the wall clock and by HIP events around the call
 
 Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
 smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
@@ -125,6 +131,76 @@ def neighbors(e, a):
         print(line, flush=True)
 
 
+def timed_events(fn, reps):
+    """1 warm-up + reps calls -> (wall seconds, HIP-event seconds) of each; the events are recorded right before and after the call,
+    which returns after its last copy"""
+    import torch
+    fn()
+    wall, dev = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        t0 = time.perf_counter()
+        fn()
+        wall.append(time.perf_counter() - t0)
+        e1.record()
+        e1.synchronize()
+        dev.append(e0.elapsed_time(e1) / 1e3)
+    return wall, dev
+
+
+def span(ts):
+    return "%.3f .. %.3f ms" % (min(ts) * 1e3, max(ts) * 1e3)
+
+
+def screen(e, a):
+    from fastani_amd.api import NEIGHBOR_DT
+    rng = np.random.default_rng(1)
+    n_ref, shape_env = 10000, "ANI_TEST_SIG_SCREEN_SHAPE"
+    ref, ref_len = synthetic_signatures(rng, n_ref)
+    qry_all, qry_len_all = synthetic_signatures(rng, 1000)
+    qry_all[0], qry_len_all[0] = ref[77], ref_len[77]                  # one query that is a reference
+    for n_qry in (1, 16, 1000):
+        if a.only and n_qry != a.only:
+            continue
+        qry, qry_len = qry_all[:n_qry], qry_len_all[:n_qry]
+        got, dev_of = {}, {}
+        for shape in (None, "square", "thin"):
+            os.environ.pop(shape_env, None)
+            if shape:
+                os.environ[shape_env] = shape
+            wall, dev = timed_events(lambda: got.__setitem__(shape, e.signature_screen(ref, ref_len, qry, qry_len, 16, a.k)), a.reps)
+            dev_of[shape] = dev
+            print("screen     nQry=%5d nRef=%d s=%d k=%d shape %-7s tile %2d x %2d, %d strips: wall %s   HIP events %s"
+                  % ((n_qry, n_ref, SIZE, a.k, shape or "default") + e.signature_screen_tile() + (e.signature_screen_strips(), span(wall), span(dev))), flush=True)
+        os.environ.pop(shape_env, None)
+        for shape in ("square", "thin"):
+            assert all(np.array_equal(got[shape][i], got[None][i]) for i in (0, 1)), shape
+        # the route without the call: neighbour lists of the query rows over references + queries, cut to the references on the host
+        sig, length = np.concatenate([ref, qry]), np.concatenate([ref_len, qry_len])
+        old = {}
+
+        def route():
+            nb, _ = e.signature_neighbors(sig, length, 16, 1024, rows=(n_ref, n_ref + n_qry))
+            out = np.zeros((n_qry, a.k), dtype=NEIGHBOR_DT)
+            out["neighbor"] = -1
+            count = np.zeros(n_qry, dtype=np.int32)
+            for q in range(n_qry):
+                keep = nb[q][(nb[q]["neighbor"] >= 0) & (nb[q]["neighbor"] < n_ref)][:a.k]
+                out[q, :len(keep)] = keep
+                count[q] = len(keep)
+            old["r"] = (out, count)
+
+        wall, dev = timed_events(route, a.reps)
+        exact = n_qry - 1 + a.k <= 1024                                # (the 1024 entries hold the k references whatever the queries among them)
+        same = all(np.array_equal(old["r"][i], got[None][i]) for i in (0, 1))
+        assert same or not exact
+        print("neighbours nQry=%5d nRef=%d s=%d k=1024 + host cut, %d strips: wall %s   HIP events %s   lists %s   screen / route by HIP events: %.3f .. %.3f"
+              % (n_qry, n_ref, SIZE, e.signature_neighbors_strips(), span(wall), span(dev), "identical" if same else "differ (cut too short)",
+                 min(dev_of[None]) / max(dev), max(dev_of[None]) / min(dev)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", type=int, default=0)
@@ -132,12 +208,13 @@ def main():
     ap.add_argument("--min-shared", type=int, default=SIZE + 1)
     ap.add_argument("--skip-signatures", action="store_true")
     ap.add_argument("--neighbors", action="store_true")
+    ap.add_argument("--screen", action="store_true")
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
-    if a.neighbors:
+    if a.neighbors or a.screen:
         import fastani_amd
-        neighbors(fastani_amd.engine(0), a)
+        (neighbors if a.neighbors else screen)(fastani_amd.engine(0), a)
         return
     import torch
     import fastani_amd
