@@ -14,6 +14,8 @@
     Engine.tree_single_sketch(rows, n, sig, len, k)  tree_single with that estimate for every pair without rows, streamed strip by
                                            strip: nothing of size n^2 anywhere, no genome ceiling (no reference counterpart)
     Engine.signature_screen(ref, len, qry, len, k_mer, k)  the k nearest references of every query under that estimate
+    Engine.signature_screen_contain(ref, len, qry, len, k_mer, k, mode)  the same under the containment estimate: partial genomes,
+                                           plasmids and contigs against whole references, or references inside a larger assembly
     Engine.signature_neighbors(sig, len, k_mer, k)  the k nearest neighbours of every genome under that estimate, streamed strip by
                                            strip, no genome ceiling (no reference counterpart)
 
@@ -140,6 +142,8 @@ def _bind(lib):
         "ani_signature_neighbors": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
         "ani_signature_neighbors_strips": (C.c_int, [vp]),
         "ani_signature_screen": (C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, vp]),
+        "ani_signature_screen_contain": (C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                                   vp, vp]),
         "ani_signature_screen_strips": (C.c_int, [vp]),
         "ani_signature_screen_tile": (None, [vp, vp, vp]),
     }
@@ -555,6 +559,24 @@ class Engine:
         first and ties by ascending reference id (ani_signature_screen; the semantics are in ani_abi.h).  Only pairs of a query and a
         reference are compared; the queries stream through the device a strip at a time, and neither side has a 65 536 ceiling.
         -> (neighbors, count): NEIGHBOR_DT (nQry, k) of reference ids, the unused slots (-1, 0, 0, 0.0), and int32 (nQry,)."""
+        return self._screen(ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, None)
+
+    CONTAIN_MODES = {"query": 0, "reference": 1, "max": 2}
+
+    def signature_screen_contain(self, ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, mode="query", min_shared=1, min_identity=0.0):
+        """signature_screen under the containment estimate (ani_signature_screen_contain; the semantics are in ani_abi.h): shared values
+        over the whole of both signatures, divided by the part of one signature that lies where the other is complete.  mode "query"
+        (0): how much of the query is in the reference, for partial genomes, plasmids and contigs; "reference" (1): how much of the
+        reference is in the query, for references inside a larger assembly; "max" (2): the larger of the two, symmetric.
+        -> (neighbors, count) as signature_screen; the size field of a record is the denominator."""
+        if isinstance(mode, str):
+            if mode not in self.CONTAIN_MODES:
+                raise ValueError("mode %r: one of %s, or 0 .. 2" % (mode, ", ".join(sorted(self.CONTAIN_MODES))))
+            mode = self.CONTAIN_MODES[mode]
+        return self._screen(ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, int(mode))
+
+    def _screen(self, ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, mode):
+        """the two screen calls: mode None is ani_signature_screen, 0 .. 2 ani_signature_screen_contain"""
         ref_sig, qry_sig = (np.ascontiguousarray(x, dtype=np.uint32) for x in (ref_sig, qry_sig))
         ref_length, qry_length = (np.ascontiguousarray(x, dtype=np.int32) for x in (ref_length, qry_length))
         if ref_sig.ndim != 2 or ref_length.shape != (ref_sig.shape[0],) or qry_sig.ndim != 2 or qry_length.shape != (qry_sig.shape[0],):
@@ -564,18 +586,22 @@ class Engine:
         (nr, size), nq, k = ref_sig.shape, qry_sig.shape[0], int(k)
         out = np.zeros((nq, max(k, 0)), dtype=NEIGHBOR_DT)
         count = np.zeros(nq, dtype=np.int32)
-        self._chk(self.lib.ani_signature_screen(self.h, ref_sig.ctypes.data if nr else None, ref_length.ctypes.data if nr else None, nr,
-                                                qry_sig.ctypes.data if nq else None, qry_length.ctypes.data if nq else None, nq, size, int(kmer_size),
-                                                int(min_shared), float(min_identity), k, out.ctypes.data if out.size else None,
-                                                count.ctypes.data if nq else None))
+        head = (self.h, ref_sig.ctypes.data if nr else None, ref_length.ctypes.data if nr else None, nr, qry_sig.ctypes.data if nq else None,
+                qry_length.ctypes.data if nq else None, nq, size, int(kmer_size), int(min_shared), float(min_identity), k)
+        tail = (out.ctypes.data if out.size else None, count.ctypes.data if nq else None)
+        if mode is None:
+            self._chk(self.lib.ani_signature_screen(*head, *tail))
+        else:
+            self._chk(self.lib.ani_signature_screen_contain(*head, mode, *tail))
         return out, count
 
     def signature_screen_strips(self):
-        """strips the last signature_screen call of this engine took (ani_signature_screen_strips)"""
+        """strips the last signature_screen or signature_screen_contain call of this engine took (ani_signature_screen_strips)"""
         return int(self.lib.ani_signature_screen_strips(self.h))
 
     def signature_screen_tile(self):
-        """(queries, references) of the merge tile of the last strip of this engine's last signature_screen call (ani_signature_screen_tile)"""
+        """(queries, references) of the merge tile of the last strip of this engine's last signature_screen or signature_screen_contain
+        call (ani_signature_screen_tile)"""
         tq, tr = C.c_int32(0), C.c_int32(0)
         self.lib.ani_signature_screen_tile(self.h, C.byref(tq), C.byref(tr))
         return tq.value, tr.value

@@ -20,6 +20,7 @@
 #include "kernels/sigstrip.hpp"
 #include "kernels/signeigh.hpp"
 #include "kernels/sigscreen.hpp"
+#include "kernels/sigcontain.hpp"
 
 namespace anih {
 using namespace ani;
@@ -1404,6 +1405,25 @@ static std::vector<uint32_t> sig_identity_table(int32_t size, int32_t kmerSize)
   return table;
 }
 
+// bits(identity) of every (shared, d) with 1 <= shared <= d <= size under the containment estimate (ani_signature_screen_contain, rule 5),
+// in the same triangular layout
+static std::vector<uint32_t> sig_contain_table(int32_t size, int32_t kmerSize)
+{
+  const size_t S = (size_t)size;
+  std::vector<uint32_t> table(S * (S + 1) / 2);
+  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
+    const int32_t d = (int32_t)i + 1;
+    for (int32_t sh = 1; sh <= d; sh++) {
+      double id = 100.0 * pow((double)sh / (double)d, 1.0 / (double)kmerSize);
+      if (id < 0.0) id = 0.0;
+      if (id > 100.0) id = 100.0;
+      const float w = (float)id;
+      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)d)], &w, 4);
+    }
+  });
+  return table;
+}
+
 // the rectangular tiles by row pitch, as sigpair_launch: rows [r0, r1), all columns
 static void signeigh_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
                             uint64_t ld)
@@ -1487,16 +1507,21 @@ int signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, i
 // ---- the nearest references of every query under the sketch estimate (ani_signature_screen) ----
 // The tile by strip height and row pitch.  A strip of at least T queries, T the edge of the pair tiles at this pitch, takes the square
 // tile; a lower one the thin tile of one query and 64 references, whose LDS is the query row alone.  ANI_TEST_SIG_SCREEN_SHAPE = square or
-// thin (tests, tools/sketch_probe.py) forces a shape.  shape[0 .. 2) = TQ, TR of the tile taken.
+// thin (tests, tools/sketch_probe.py) forces a shape.  shape[0 .. 2) = TQ, TR of the tile taken.  mode < 0: the Mash merge of
+// k_sigscreen_merge; otherwise the containment walk of k_sigcontain_merge in that mode, in the same shapes, the
+// square tiles with kSigContainPad more words of LDS for their row pitch there.
 static void sigscreen_launch(hipStream_t st, const uint32_t *refSig, const int32_t *refLen, uint32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, uint32_t q0,
-                             uint32_t q1, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld, int32_t *shape)
+                             uint32_t q1, int32_t pitch, int32_t size, int32_t mode, uint32_t *mat, uint64_t ld, int32_t *shape)
 {
   const uint32_t T = pitch <= 1024 ? 16u : pitch <= 2048 ? 8u : 4u;
   bool thin = q1 - q0 < T;
   if (const char *ev = getenv("ANI_TEST_SIG_SCREEN_SHAPE")) { if (!strcmp(ev, "square")) thin = false; else if (!strcmp(ev, "thin")) thin = true; }
   auto tiles = [&](uint32_t tq, uint32_t tr) { return dim3((nRef + tr - 1) / tr, (q1 - q0 + tq - 1) / tq); };
-#define ANI_SCREEN(TQ, TR, WORDS, LANES) hipLaunchKernelGGL((k_sigscreen_merge<TQ, TR, WORDS>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, \
-                                                            qryLen, q0, q1, pitch, size, mat, ld)
+#define ANI_SCREEN(TQ, TR, WORDS, LANES) do { \
+    if (mode < 0) hipLaunchKernelGGL((k_sigscreen_merge<TQ, TR, WORDS>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, qryLen, q0, q1, pitch, size, \
+                                     mat, ld); \
+    else hipLaunchKernelGGL((k_sigcontain_merge<TQ, TR, (TQ > 1 ? WORDS + kSigContainPad : WORDS)>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, \
+                            qryLen, q0, q1, pitch, size, mode, mat, ld); } while (0)
   if (thin) {
     if (pitch <= 1024) ANI_SCREEN(1, kSigScreenThinRefs, 1024, 64);
     else ANI_SCREEN(1, kSigScreenThinRefs, kSigMaxSize, 64);
@@ -1529,8 +1554,10 @@ static int sigscreen_stage(ani_ctx *ctx, DevBuf &raw, DevBuf &staged, DevBuf &le
 // each query, written into the query's place of the output and copied back through page-locked staging.  Device memory: either set
 // twice while it is staged and once after, 2 s (s + 1) bytes of identities, 16 k + 4 bytes per query, and one strip (kSigStripShare of
 // what is free then, 4 bytes per cell).  Nothing follows nRef * nQry.
-int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                     int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+// Shared by the two estimates: mode < 0 is ani_signature_screen (the Mash merge, sig_identity_table), mode 0 .. 2 is
+// ani_signature_screen_contain (the containment walk in that mode, sig_contain_table); everything else is the same code.
+static int screen_run(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                      int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out, int32_t *count)
 {
   enum { RRAW, RLEN, RSIG, QRAW, QLEN, QSIG, FLAGS, TABLE, MAT, OUT, CNT, NBUF };
   DevBufs B(NBUF);
@@ -1556,7 +1583,7 @@ int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen
   const uint32_t *dRefSig = B.b[RSIG].as<uint32_t>(), *dQrySig = B.b[QSIG].as<uint32_t>();
   const int32_t *dRefLen = B.b[RLEN].as<int32_t>(), *dQryLen = B.b[QLEN].as<int32_t>();
 
-  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
+  const std::vector<uint32_t> table = mode < 0 ? sig_identity_table(size, kmerSize) : sig_contain_table(size, kmerSize);
   TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
   HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1577,7 +1604,7 @@ int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen
   TRY(pinned_buffer(ctx, 1, (size_t)h * 4, (void **)&stageCnt));
   for (uint64_t q0 = 0; q0 < Q; q0 += h) {
     const uint32_t q1 = (uint32_t)std::min<uint64_t>(q0 + h, Q), rows1 = q1 - (uint32_t)q0;
-    sigscreen_launch(st, dRefSig, dRefLen, (uint32_t)nRef, dQrySig, dQryLen, (uint32_t)q0, q1, pitch, size, dMat, ld, ctx->sigScreenTile);
+    sigscreen_launch(st, dRefSig, dRefLen, (uint32_t)nRef, dQrySig, dQryLen, (uint32_t)q0, q1, pitch, size, mode, dMat, ld, ctx->sigScreenTile);
     hipLaunchKernelGGL(k_sigscreen_select, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)q0, (uint32_t)nRef, minShared,
                        (const uint32_t *)dTable, minBits, k, dOut, dCnt);
     HIP_TRY(hipGetLastError());
@@ -1593,6 +1620,19 @@ int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen
     }
   }
   return ANI_OK;
+}
+
+int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                     int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+{
+  return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, -1, out, count);
+}
+
+// ---- the same under the containment estimate (ani_signature_screen_contain) ----
+int signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                             int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out, int32_t *count)
+{
+  return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
 }
 
 }  // namespace anih
@@ -1929,8 +1969,11 @@ int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *le
 
 int ani_signature_neighbors_strips(const ani_ctx *ctx) { return ctx ? ctx->sigNeighStrips : 0; }
 
-int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                         int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+// the two screen calls: the checks of ani_signature_screen's rules 4 - 6 and, with `contain`, of ani_signature_screen_contain's rule 7,
+// then the call; without `contain` it is ani_signature_screen and the mode plays no part
+static int screen_entry(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                        int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, bool contain, int32_t mode, ani_signeighbor_t *out,
+                        int32_t *count)
 {
   if (!ctx) return fail(ANI_ERR_ARG, "null argument");
   if (nRef < 0 || nQry < 0) return fail(ANI_ERR_ARG, "negative genome count");
@@ -1939,6 +1982,7 @@ int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *re
   if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
   if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
   if (k < 1 || k > ani::kSigNeighMaxK) return fail(ANI_ERR_ARG, "k %d outside [1, %d]", k, ani::kSigNeighMaxK);
+  if (contain && (mode < ANI_CONTAIN_QUERY || mode > ANI_CONTAIN_MAX)) return fail(ANI_ERR_ARG, "containment mode %d outside [0, 2]", mode);
   if (nRef > (1 << 30) || nQry > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d references, %d queries: the screen takes at most 2^30 of either", nRef, nQry);
   ctx->sigScreenStrips = 0; ctx->sigScreenTile[0] = ctx->sigScreenTile[1] = 0;
   if (nQry == 0) return ANI_OK;
@@ -1948,8 +1992,24 @@ int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *re
   for (int32_t g = 0; g < nQry; g++)
     if (qryLen[g] < 0 || qryLen[g] > size) return fail(ANI_ERR_ARG, "query signature %d has length %d outside [0, %d]", g, qryLen[g], size);
   HIP_TRY(hipSetDevice(ctx->device));
-  try { return signature_screen(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, out, count); }
+  try {
+    if (contain) return signature_screen_contain(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
+    return signature_screen(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, out, count);
+  }
   catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                         int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
+{
+  return screen_entry(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, false, -1, out, count);
+}
+
+int ani_signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen,
+                                 int32_t nQry, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out,
+                                 int32_t *count)
+{
+  return screen_entry(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, true, mode, out, count);
 }
 
 int ani_signature_screen_strips(const ani_ctx *ctx) { return ctx ? ctx->sigScreenStrips : 0; }

@@ -363,7 +363,7 @@ struct ani_ctx {
   int treeSingleRounds = 0;                                                        // spanning-forest rounds of the last ani_tree_single[_sketch] (ani_tree_single_rounds)
   std::vector<uint64_t> sigStripEdges;                                             // edges kept per strip of the last ani_tree_single_sketch
   int sigNeighStrips = 0;                                                          // strips of the last ani_signature_neighbors
-  int sigScreenStrips = 0;                                                         // strips of the last ani_signature_screen
+  int sigScreenStrips = 0;                                                         // strips of the last screen call (ani_signature_screen, ani_signature_screen_contain)
   int32_t sigScreenTile[2] = {0, 0};                                               // queries x references of the tile of its last strip
   // minimizers per index chunk (env ANI_MAX_INDEX_MINIMIZERS); indices are 32 bit
   uint64_t maxIndexMinimizers = 1700000000ull;

@@ -11,7 +11,8 @@
 // tree that estimate for the pairs without a .matrix cell (streamed through ani_tree_single_sketch for a single-linkage tree of more
 // than 65 536 genomes), `--sketchNeighbors K` a .neighbors file (the K nearest genomes of every genome under that estimate,
 // ani_signature_neighbors: any number of genomes), `--sketchScreen K` a .screen file (the K nearest references of every query under that
-// estimate, ani_signature_screen: the queries need not be references).  Sketch / Map / computeCGI run on the GPU(s)
+// estimate, ani_signature_screen: the queries need not be references; with `--sketchContain query|reference|max` under the containment
+// estimate, ani_signature_screen_contain).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -77,6 +78,7 @@ struct Options {
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
   int sketchNeighbors = 0;                             // --sketchNeighbors K: the .neighbors file (0 = off)
   int sketchScreen = 0;                                // --sketchScreen K: the .screen file (0 = off)
+  int sketchContain = -1;                              // --sketchContain MODE: .screen under the containment estimate (an ani_contain_mode; -1 = off)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
@@ -99,7 +101,8 @@ struct Options {
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
-    "             [--sketchNeighbors <value>] [--sketchScreen <value>] [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
+    "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [-o <value>] [-s] [-v]\n"
+    "             [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -135,6 +138,10 @@ struct Options {
     "     --sketchScreen <value>  also output, for every query genome, its nearest reference genomes under that estimate, at most\n"
     "                 this many (1 to 1024), nearest first (.screen: query, reference, estimate, shared/size; NA for a query without\n"
     "                 one); the queries need not be among the references; any number of genomes [disabled by default]\n"
+    "     --sketchContain <value>  with --sketchScreen: the containment estimate instead, for inputs of unequal size or completeness.\n"
+    "                 query: the share of the query's sketch found in the reference (partial genomes, plasmids, contigs); reference:\n"
+    "                 the share of the reference's sketch found in the query (references inside a larger assembly); max: the larger\n"
+    "                 of the two.  The fourth column of .screen is then shared/denominator [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -169,7 +176,7 @@ Options parse(int argc, char **argv)
 {
   Options o;
   std::string refName, refList, qryName, qryList;
-  bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false;
+  bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -202,6 +209,9 @@ Options parse(int argc, char **argv)
       if (o.sketchNeighbors < 1 || o.sketchNeighbors > 1024) { std::cerr << "ERROR, --sketchNeighbors takes a count from 1 to 1024" << std::endl; exit(1); } }
     else if (a == "--sketchScreen") { o.sketchScreen = atoi(need(i));
       if (o.sketchScreen < 1 || o.sketchScreen > 1024) { std::cerr << "ERROR, --sketchScreen takes a count from 1 to 1024" << std::endl; exit(1); } }
+    else if (a == "--sketchContain") { const std::string v = need(i); sketchContain = true;
+      o.sketchContain = v == "query" ? ANI_CONTAIN_QUERY : v == "reference" ? ANI_CONTAIN_REF : v == "max" ? ANI_CONTAIN_MAX : -1;
+      if (o.sketchContain < 0) { std::cerr << "ERROR, --sketchContain takes query or reference or max" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -218,6 +228,7 @@ Options parse(int argc, char **argv)
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
   if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors && !o.sketchScreen) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
+  if (sketchContain && !o.sketchScreen) { std::cerr << "ERROR, --sketchContain needs --sketchScreen" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -1609,6 +1620,7 @@ void write_neighbors(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixC
 // (ani_signature_screen on the first device, minShared = 1; the reference signatures are the collected table as it stands, the query
 // signatures a reference's row or the query's own).  .screen: queries in query-list order, one line per reference, nearest first, ties in
 // reference-list order: query, reference, estimate as .sketch prints it, shared/size; a query without a hit has one line of NA.
+// With --sketchContain the call is ani_signature_screen_contain in that mode and the last column shared/denominator.
 void write_screen(const Options &o, ani_ctx *ctx, int kmerSize)
 {
   const size_t nR = o.refs.size(), nQ = o.queries.size(), K = (size_t)o.sketchScreen, S = (size_t)g_sigs.size;
@@ -1623,8 +1635,12 @@ void write_screen(const Options &o, ani_ctx *ctx, int kmerSize)
     qlen[q] = t.len[row];
   }
   std::vector<ani_signeighbor_t> nb(nQ * K); std::vector<int32_t> count(nQ);
-  if (ani_signature_screen(ctx, g_sigs.sig.data(), g_sigs.len.data(), (int32_t)nR, qsig.data(), qlen.data(), (int32_t)nQ, g_sigs.size, kmerSize, 1, o.sketchMinANI,
-                           o.sketchScreen, nb.data(), count.data())) die("ani_signature_screen");
+  if (o.sketchContain >= 0) {
+    if (ani_signature_screen_contain(ctx, g_sigs.sig.data(), g_sigs.len.data(), (int32_t)nR, qsig.data(), qlen.data(), (int32_t)nQ, g_sigs.size, kmerSize, 1,
+                                     o.sketchMinANI, o.sketchScreen, o.sketchContain, nb.data(), count.data())) die("ani_signature_screen_contain");
+  }
+  else if (ani_signature_screen(ctx, g_sigs.sig.data(), g_sigs.len.data(), (int32_t)nR, qsig.data(), qlen.data(), (int32_t)nQ, g_sigs.size, kmerSize, 1, o.sketchMinANI,
+                                o.sketchScreen, nb.data(), count.data())) die("ani_signature_screen");
   trace("sketch screen done");
   BufferedFile f(o.out + ".screen");
   for (size_t q = 0; q < nQ; q++) {

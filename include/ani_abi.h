@@ -499,15 +499,48 @@ int ani_signature_neighbors_strips(const ani_ctx *ctx);
  *    whose height follows the free device memory, and 16 k + 4 bytes per query.  Nothing follows nRef * nQry, and there is no 65 536
  *    ceiling on either side.  ANI_TEST_SIG_STRIP_ROWS (tests) forces a strip height, ANI_TEST_SIG_SCREEN_SHAPE = square | thin the
  *    shape of the merge tile, which otherwise follows the strip height.
- * 9. ani_signature_screen_strips: the strips the context's last ani_signature_screen call took; 0 if it needed none or there was no
- *    call.  ani_signature_screen_tile: the queries x references of the merge tile of that call's last strip, 0 x 0 likewise
- *    (tools/sketch_probe.py reports both). */
+ * 9. ani_signature_screen_strips: the strips the context's last screen call of either kind (ani_signature_screen,
+ *    ani_signature_screen_contain) took; 0 if it needed none or there was no call.  ani_signature_screen_tile: the queries x references
+ *    of the merge tile of that call's last strip, 0 x 0 likewise (tools/sketch_probe.py reports both). */
 int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef,
                          const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
                          int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k,
                          ani_signeighbor_t *out /* [nQry * k] */, int32_t *count /* [nQry] */);
 int ani_signature_screen_strips(const ani_ctx *ctx);
 void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t *tileRefs);
+
+/* ---- screening under the containment estimate (no counterpart in the reference).  ani_signature_screen's
+ * estimate is a Jaccard index over the first `size` values of the union of two signatures: right when query and reference are about
+ * the same size and both complete, low for a partial genome, a plasmid or a contig against a whole one, and for a reference inside a
+ * much larger assembly.  This call divides the shared values by the part of one signature that lies where the other is complete.
+ * Everything is integer except the last step.  Q is a query signature and R a reference signature, ascending distinct lists of lengths
+ * lq and lr, as ani_sketch_signatures lays them out at `size`.
+ * 1. A signature is truncated iff its length equals `size`: the genome may have more values than the sketch holds.  A shorter
+ *    signature is the genome's whole set.
+ * 2. shared = the number of values that occur in both lists, over the whole of both: not cut at `size` union elements, unlike rule 2 of
+ *    ani_signature_pairs.
+ * 3. inQ = the number of values of Q that are <= the last value of R, if R is truncated; otherwise inQ = lq.  inR likewise with the
+ *    roles swapped.  These are the parts of each list in the hash range where the other sketch is complete.  Every shared value counts
+ *    in both: shared <= inQ <= size, shared <= inR <= size, and shared >= 1 implies both >= 1.
+ * 4. mode selects the denominator d.  ANI_CONTAIN_QUERY: d = inQ, how much of the query is in the reference (partial genomes, plasmids,
+ *    contigs).  ANI_CONTAIN_REF: d = inR, how much of the reference is in the query (references inside a large assembly).
+ *    ANI_CONTAIN_MAX: d = min(inQ, inR), symmetric in the two sets.
+ * 5. identity = 0 if shared = 0; otherwise 100.0 * pow((double) shared / (double) d, 1.0 / (double) kmerSize) in double, clamped to
+ *    [0, 100] and rounded once to float, by the library on the host.  shared = d gives exactly 100.
+ * 6. The candidates of query q are the references r with shared >= minShared and identity >= minIdentity.  Order, cut, count and unused
+ *    slots are rules 3 - 6 of ani_signature_neighbors: identity descending by bit pattern, then reference id ascending;
+ *    count[q] = min(k, candidates of q); the unused slots are {-1, 0, 0, 0.0f}; a minIdentity of -0.0 is 0.  The record is
+ *    ani_signeighbor_t{neighbor = r, shared, size = d, identity}.
+ * 7. Errors and limits are rules 4 - 6 of ani_signature_screen, and ANI_ERR_ARG for a mode outside 0 .. 2.  The checks of the scalar
+ *    arguments run before any allocation.  nQry == 0: nothing is read or written.  nRef == 0: every list is empty.
+ * 8. Memory is rule 8 of ani_signature_screen; ANI_TEST_SIG_STRIP_ROWS and ANI_TEST_SIG_SCREEN_SHAPE act on this call too.  The result
+ *    depends on no schedule, no strip height and no tile shape.
+ * ani_signature_screen_strips and ani_signature_screen_tile report this call as they report ani_signature_screen. */
+typedef enum { ANI_CONTAIN_QUERY = 0, ANI_CONTAIN_REF = 1, ANI_CONTAIN_MAX = 2 } ani_contain_mode;
+int ani_signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef,
+                                 const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
+                                 int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode,
+                                 ani_signeighbor_t *out /* [nQry * k] */, int32_t *count /* [nQry] */);
 
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut

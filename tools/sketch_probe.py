@@ -18,6 +18,12 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
                                                  route without it: ani_signature_neighbors over references + queries for the query rows
                                                  at k = 1024, cut to the references on the host; lists compared.  Every line: min .. max
                                                  of the timed calls, by the wall clock and by HIP events around the call
+    python tools/sketch_probe.py --screen --contain query|reference|max
+                                                 ani_signature_screen_contain in that mode beside
+                                                 ani_signature_screen on the same signatures, query counts and tile shapes: min .. max
+                                                 and median of the timed calls by HIP events, the merge steps of both rules replayed on
+                                                 the host (on a sample of pairs for the larger counts), steps/s, and the time per step
+                                                 of the new call over that of the existing one
 
 Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
 smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
@@ -53,6 +59,13 @@ def merge_steps(x, y, size):
     u = np.union1d(x, y)
     last = min(x[-1], y[-1]) if len(x) and len(y) else -1
     return int(min(size, np.searchsorted(u, last, side="right")))
+
+
+def contain_steps(x, y):
+    """steps of the containment walk (kernels/sigcontain.hpp): union elements taken until the end of either row, no cap"""
+    if not len(x) or not len(y):
+        return 0
+    return int(np.searchsorted(np.union1d(x, y), min(x[-1], y[-1]), side="right"))
 
 
 def count_steps(rng, sig, length, sample=20000):
@@ -201,6 +214,46 @@ def screen(e, a):
                  min(dev_of[None]) / max(dev), max(dev_of[None]) / min(dev)), flush=True)
 
 
+def contain(e, a):
+    """ani_signature_screen_contain beside ani_signature_screen: the same signatures, query counts and tile shapes as screen()"""
+    rng = np.random.default_rng(1)
+    n_ref, shape_env = 10000, "ANI_TEST_SIG_SCREEN_SHAPE"
+    ref, ref_len = synthetic_signatures(rng, n_ref)
+    qry_all, qry_len_all = synthetic_signatures(rng, 1000)
+    qry_all[0], qry_len_all[0] = ref[77], ref_len[77]                  # one query that is a reference
+    for n_qry in (1, 16, 1000):
+        if a.only and n_qry != a.only:
+            continue
+        qry, qry_len = qry_all[:n_qry], qry_len_all[:n_qry]
+        # the steps of both rules, replayed: every pair up to 20 000 of them, a sample beyond
+        pairs = n_qry * n_ref
+        if pairs <= 20000:
+            idx = [(q, r) for q in range(n_qry) for r in range(n_ref)]
+        else:
+            idx = list(zip(rng.integers(0, n_qry, 20000).tolist(), rng.integers(0, n_ref, 20000).tolist()))
+        rows = [(qry[q, :qry_len[q]].astype(np.int64), ref[r, :ref_len[r]].astype(np.int64)) for q, r in idx]
+        steps = {"screen": sum(merge_steps(x, y, SIZE) for x, y in rows) / len(idx) * pairs, "contain": sum(contain_steps(x, y) for x, y in rows) / len(idx) * pairs}
+        print("steps      nQry=%5d nRef=%d s=%d (%s): Mash merge %.3e, containment walk %.3e, ratio %.3f"
+              % (n_qry, n_ref, SIZE, "exact" if len(idx) == pairs else "sampled", steps["screen"], steps["contain"], steps["contain"] / steps["screen"]), flush=True)
+        for shape in (None, "square", "thin"):
+            os.environ.pop(shape_env, None)
+            if shape:
+                os.environ[shape_env] = shape
+            per = {}
+            for name, fn in (("screen", lambda: e.signature_screen(ref, ref_len, qry, qry_len, 16, a.k)),
+                             ("contain", lambda: e.signature_screen_contain(ref, ref_len, qry, qry_len, 16, a.k, a.contain))):
+                wall, dev = timed_events(fn, a.reps)
+                per[name] = dev
+                print("%-10s nQry=%5d nRef=%d s=%d k=%d shape %-7s tile %2d x %2d, %d strips: wall %s   HIP events %s   median %.3f ms   %.3e steps/s"
+                      % ((name + (" " + a.contain if name == "contain" else ""), n_qry, n_ref, SIZE, a.k, shape or "default") + e.signature_screen_tile()
+                         + (e.signature_screen_strips(), span(wall), span(dev), float(np.median(dev)) * 1e3, steps[name] / float(np.median(dev)))), flush=True)
+            ratio = lambda c, s: (c / steps["contain"]) / (s / steps["screen"])
+            print("           time per step, contain / screen: %.3f by the medians, %.3f .. %.3f over the spread of both"
+                  % (ratio(float(np.median(per["contain"])), float(np.median(per["screen"]))), ratio(min(per["contain"]), max(per["screen"])),
+                     ratio(max(per["contain"]), min(per["screen"]))), flush=True)
+        os.environ.pop(shape_env, None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", type=int, default=0)
@@ -209,12 +262,15 @@ def main():
     ap.add_argument("--skip-signatures", action="store_true")
     ap.add_argument("--neighbors", action="store_true")
     ap.add_argument("--screen", action="store_true")
+    ap.add_argument("--contain", choices=("query", "reference", "max"), default=None)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
+    if a.contain and not a.screen:
+        ap.error("--contain needs --screen")
     if a.neighbors or a.screen:
         import fastani_amd
-        (neighbors if a.neighbors else screen)(fastani_amd.engine(0), a)
+        (neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
         return
     import torch
     import fastani_amd
