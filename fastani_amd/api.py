@@ -18,6 +18,8 @@
                                            plasmids and contigs against whole references, or references inside a larger assembly
     Engine.signature_neighbors(sig, len, k_mer, k)  the k nearest neighbours of every genome under that estimate, streamed strip by
                                            strip, no genome ceiling (no reference counterpart)
+    Engine.signature_cluster(sig, len, k_mer, t)  greedy representative clustering (dereplication) of the genomes under that estimate
+                                           at the threshold t: genomes against representatives only, no genome ceiling
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -146,6 +148,8 @@ def _bind(lib):
                                                    vp, vp]),
         "ani_signature_screen_strips": (C.c_int, [vp]),
         "ani_signature_screen_tile": (None, [vp, vp, vp]),
+        "ani_signature_cluster": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, vp]),
+        "ani_signature_cluster_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -605,6 +609,32 @@ class Engine:
         tq, tr = C.c_int32(0), C.c_int32(0)
         self.lib.ani_signature_screen_tile(self.h, C.byref(tq), C.byref(tr))
         return tq.value, tr.value
+
+    def signature_cluster(self, sig, length, kmer_size, min_identity, min_shared=1):
+        """greedy representative clustering of the genomes under the estimate of signature_pairs(sig, length, kmer_size, min_shared):
+        genomes in id order, a genome is a representative iff no earlier representative is at identity >= min_identity, every other
+        genome a member of its nearest representative, ties by ascending id (ani_signature_cluster; the semantics are in ani_abi.h).
+        What cluster_greedy gives over the rows of signature_pairs, without the pairs: every genome is compared with the
+        representatives only, and there is no 65 536 ceiling.  -> (representative, link): int32 (n,), and NEIGHBOR_DT (n,) with the
+        representative, shared, size and identity of a member's pair, (-1, 0, 0, 0.0) for a representative."""
+        sig = np.ascontiguousarray(sig, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        if sig.ndim != 2 or length.shape != (sig.shape[0],):
+            raise ValueError("sig must be (n, size) and length (n,)")
+        n, size = sig.shape
+        representative = np.zeros(n, dtype=np.int32)
+        link = np.zeros(n, dtype=NEIGHBOR_DT)
+        self._chk(self.lib.ani_signature_cluster(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
+                                                 int(min_shared), float(min_identity), representative.ctypes.data if n else None,
+                                                 link.ctypes.data if n else None))
+        return representative, link
+
+    def signature_cluster_stats(self):
+        """(strips, representatives, cells merged, resolve steps) of the last signature_cluster call of this engine
+        (ani_signature_cluster_stats)"""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.lib.ani_signature_cluster_stats(self.h, out))
+        return tuple(int(x) for x in out)
 
 
 class FragmentSet:

@@ -5,7 +5,8 @@
 // kernels/tree.hpp), neighbour joining (ani_tree_nj, kernels/nj.hpp) and single linkage with its minimum spanning tree (ani_tree_single,
 // kernels/single.hpp); and the whole-genome sketch estimate that fills the pairs the
 // mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
-// ani_signature_pairs, kernels/sigdist.hpp).
+// ani_signature_pairs, kernels/sigdist.hpp), with its streamed consumers: neighbours, screens and the greedy clustering of
+// ani_signature_cluster (kernels/sigcluster.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -21,6 +22,7 @@
 #include "kernels/signeigh.hpp"
 #include "kernels/sigscreen.hpp"
 #include "kernels/sigcontain.hpp"
+#include "kernels/sigcluster.hpp"
 
 namespace anih {
 using namespace ani;
@@ -1635,6 +1637,135 @@ int signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t
   return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
 }
 
+// ---- greedy representative clustering under the sketch estimate (ani_signature_cluster) ----
+// Strip height at the most, by genome count: the strip's own rows x rows block is merged whether greedy clustering needs its pairs or
+// not, so the blocks together (n h cells) stay at a sixteenth of the n^2 / 2 pairs of the composition, within [256, 4096] rows: below
+// 256 the resolve workgroup's lanes idle and the launches of a strip outweigh its cells, above kSigClusterMaxStrip the covered words
+// of a strip do not fit the LDS the resolve kernel declares.
+static uint64_t sigcluster_strip_cap(uint64_t n) { return std::min<uint64_t>(std::max<uint64_t>(n / 32, 256), (uint64_t)kSigClusterMaxStrip); }
+
+// The signatures are staged and validated as for ani_signature_pairs and the identity bits of every (shared, size') come from the host.
+// First sweep, strips in id order: the strip against the representatives found before it (k_sigscreen_merge with the representatives'
+// rows as the references, then k_sigcluster_best), the strip against itself and k_sigcluster_resolve, which names the strip's
+// representatives; k_sigcluster_gather appends their rows.  Second sweep: the members of every strip against the representatives found
+// after it.  Every (genome, representative) pair is merged once, and besides them only the pairs inside a strip.  The host waits once
+// per strip of the first sweep, for the count of representatives, which sizes the next launches.  Device memory: the signatures twice
+// while they are staged and once after, the representatives' rows (room for every genome: one more copy at the most), 2 s (s + 1) bytes
+// of identities, 28 bytes per genome, and one strip of rows x max(representatives, rows) 4-byte cells.  Nothing follows nGenomes^2.
+int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
+                      int32_t *representative, ani_signeighbor_t *link)
+{
+  enum { RAW, LEN, SIG, FLAGS, TABLE, REPSIG, REPLEN, REPID, REPCNT, BEST, CELL, MEMLEN, MAT, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG;
+  const int32_t pitch = (size + 3) & ~3;
+  auto quads = [](uint64_t x) { return (x + 3) & ~(uint64_t)3; };
+  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dRepSig, *dRepId, *dRepCnt, *dCell, *dMat; int32_t *dLen, *dRepLen, *dMemLen; uint64_t *dBest;
+  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
+  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  B.b[RAW].release();
+
+  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
+  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
+  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint32_t minBits; memcpy(&minBits, &minIdentity, 4);                 // (> 0: a running best of 0 is "no edge")
+
+  TRY(B.get(REPSIG, V * (size_t)pitch * 4, (void **)&dRepSig)); TRY(B.get(REPLEN, V * 4, (void **)&dRepLen)); TRY(B.get(REPID, V * 4, (void **)&dRepId));
+  TRY(B.get(REPCNT, 64, (void **)&dRepCnt)); TRY(B.get(BEST, V * 8, (void **)&dBest)); TRY(B.get(CELL, V * 4, (void **)&dCell));
+  TRY(B.get(MEMLEN, V * 4, (void **)&dMemLen));
+  HIP_TRY(hipMemsetAsync(dBest, 0, V * 8, st)); HIP_TRY(hipMemsetAsync(dCell, 0, V * 4, st));
+  // strip height: 4 bytes per cell of a strip against every genome (all of them may be representatives) inside a share of what is free
+  // now, and the cap by genome count
+  size_t freeB = 0, totalB = 0;
+  TRY(ani_device_memory(ctx, &freeB, &totalB));
+  uint64_t h = std::min<uint64_t>((uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)quads(V))), sigcluster_strip_cap(V));
+  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
+  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, V), (uint64_t)kSigClusterMaxStrip));
+  uint64_t *stats = ctx->sigClusterStats;
+  int32_t shape[2];
+
+  // first sweep.  repAt[s]: the representatives after strip s; members[s]: its rows that are none
+  std::vector<uint32_t> repAt, members;
+  uint32_t nRep = 0;
+  for (uint64_t r0 = 0; r0 < V; r0 += h) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V), rows1 = r1 - (uint32_t)r0;
+    // (the stream is idle here: the buffer may move.  Twice the representatives, so that it moves a logarithmic number of times)
+    TRY(B.get(MAT, (size_t)rows1 * (size_t)quads(std::max<uint64_t>(std::min<uint64_t>(2 * (uint64_t)nRep, V), h)) * 4, (void **)&dMat));
+    if (nRep) {
+      const uint64_t ld = quads(nRep);
+      sigscreen_launch(st, dRepSig, dRepLen, nRep, dSig, dLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+      hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, nRep, (const uint32_t *)dRepId, minShared,
+                         (const uint32_t *)dTable, minBits, dBest, dCell);
+      stats[2] += (uint64_t)rows1 * nRep;
+    }
+    const uint64_t ld = quads(rows1);
+    sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, dSig, dLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+    hipLaunchKernelGGL(k_sigcluster_resolve, dim3(1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, rows1, nRep, minShared, (const uint32_t *)dTable,
+                       minBits, (const int32_t *)dLen, dBest, dCell, dMemLen, dRepId, dRepCnt);
+    HIP_TRY(hipGetLastError());
+    stats[2] += (uint64_t)rows1 * rows1;
+    HIP_TRY(hipMemcpyAsync(host, dRepCnt, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t found = host[0] - nRep;
+    if (found) {
+      hipLaunchKernelGGL(k_sigcluster_gather, dim3(found), dim3(kTPB), 0, st, (const uint32_t *)dSig, (const int32_t *)dLen, (const uint32_t *)dRepId, nRep, pitch,
+                         dRepSig, dRepLen);
+      HIP_TRY(hipGetLastError());
+    }
+    stats[3] += (uint64_t)found * ((rows1 + kTPB - 1) / kTPB);
+    nRep += found;
+    repAt.push_back(nRep); members.push_back(rows1 - found);
+    stats[0]++;
+  }
+  stats[1] = nRep;
+
+  // second sweep: the members of a strip against the representatives found after it (a representative's length is 0 in dMemLen)
+  uint64_t cells = 0;
+  for (size_t s = 0; s < repAt.size(); s++)
+    if (members[s]) cells = std::max<uint64_t>(cells, std::min<uint64_t>(h, V - s * h) * quads(nRep - repAt[s]));
+  HIP_TRY(hipStreamSynchronize(st));                                   // (the last gather; the buffer may move)
+  if (cells) { TRY(B.get(MAT, (size_t)cells * 4, (void **)&dMat)); }
+  for (size_t s = 0; s < repAt.size(); s++) {
+    const uint32_t later = nRep - repAt[s];
+    if (!later || !members[s]) continue;
+    const uint64_t r0 = s * h, ld = quads(later);
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V), rows1 = r1 - (uint32_t)r0;
+    sigscreen_launch(st, dRepSig + (size_t)repAt[s] * (size_t)pitch, dRepLen + repAt[s], later, dSig, dMemLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+    hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, later, (const uint32_t *)dRepId + repAt[s],
+                       minShared, (const uint32_t *)dTable, minBits, dBest, dCell);
+    HIP_TRY(hipGetLastError());
+    stats[2] += (uint64_t)rows1 * later;
+  }
+
+  // the keys back, decoded on the host; the identities are host arithmetic (ani_abi.h)
+  std::vector<uint64_t> best(V); std::vector<uint32_t> cell(V);
+  HIP_TRY(hipMemcpyAsync(best.data(), dBest, V * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(cell.data(), dCell, V * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const size_t step = 8192;
+  parallel_for((V + step - 1) / step, (uint64_t)V * 64, [&](size_t blk) {
+    for (size_t i = blk * step; i < std::min(V, (blk + 1) * step); i++) {
+      if (!best[i]) { representative[i] = (int32_t)i; link[i] = ani_signeighbor_t{-1, 0, 0, 0.0f}; continue; }
+      const int32_t rep = (int32_t)(0xffffffffu - (uint32_t)best[i]), sh = (int32_t)(cell[i] >> 16), sz = (int32_t)(cell[i] & 0xffffu);
+      representative[i] = rep;
+      link[i] = ani_signeighbor_t{rep, sh, sz, sig_identity(sh, sz, kmerSize)};
+    }
+  });
+  return ANI_OK;
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -2018,6 +2149,33 @@ void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t
 {
   if (tileQueries) *tileQueries = ctx ? ctx->sigScreenTile[0] : 0;
   if (tileRefs) *tileRefs = ctx ? ctx->sigScreenTile[1] : 0;
+}
+
+int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                          float minIdentity, int32_t *representative, ani_signeighbor_t *link)
+{
+  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
+  if (!(minIdentity > 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside (0, 100]", (double)minIdentity);
+  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the clustering takes at most 2^30", nGenomes);
+  for (uint64_t &x : ctx->sigClusterStats) x = 0;
+  if (nGenomes == 0) return ANI_OK;
+  if (!sig || !len || !representative || !link) return fail(ANI_ERR_ARG, "null argument");
+  for (int32_t g = 0; g < nGenomes; g++)
+    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return signature_cluster(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, representative, link); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4])
+{
+  if (!out) return fail(ANI_ERR_ARG, "null argument");
+  for (int i = 0; i < 4; i++) out[i] = ctx ? ctx->sigClusterStats[i] : 0;
+  return ANI_OK;
 }
 
 }  // extern "C"

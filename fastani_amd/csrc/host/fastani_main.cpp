@@ -12,7 +12,8 @@
 // than 65 536 genomes), `--sketchNeighbors K` a .neighbors file (the K nearest genomes of every genome under that estimate,
 // ani_signature_neighbors: any number of genomes), `--sketchScreen K` a .screen file (the K nearest references of every query under that
 // estimate, ani_signature_screen: the queries need not be references; with `--sketchContain query|reference|max` under the containment
-// estimate, ani_signature_screen_contain).  Sketch / Map / computeCGI run on the GPU(s)
+// estimate, ani_signature_screen_contain), `--sketchCluster T` a .sketchclusters file (greedy representative clustering under the
+// estimate, ani_signature_cluster: any number of genomes).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -79,7 +80,8 @@ struct Options {
   int sketchNeighbors = 0;                             // --sketchNeighbors K: the .neighbors file (0 = off)
   int sketchScreen = 0;                                // --sketchScreen K: the .screen file (0 = off)
   int sketchContain = -1;                              // --sketchContain MODE: .screen under the containment estimate (an ani_contain_mode; -1 = off)
-  bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0; }   // these compare the references with each other
+  float sketchCluster = 0.0f;                          // --sketchCluster T: the .sketchclusters file, greedy clustering under the estimate at >= T (0 = off)
+  bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
   bool pairStep() const { return sketchANI || (treeFill && !(tree && treeSingle)); }
@@ -101,8 +103,8 @@ struct Options {
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
-    "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [-o <value>] [-s] [-v]\n"
-    "             [--gpus <value>]\n\n"
+    "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
+    "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
     "     -r, --ref <value>  reference genome (fasta/fastq)[.gz]\n"
@@ -142,6 +144,10 @@ struct Options {
     "                 query: the share of the query's sketch found in the reference (partial genomes, plasmids, contigs); reference:\n"
     "                 the share of the reference's sketch found in the query (references inside a larger assembly); max: the larger\n"
     "                 of the two.  The fourth column of .screen is then shared/denominator [disabled by default]\n"
+    "     --sketchCluster <value>  also output greedy clusters of the genomes under that estimate at this threshold (0 < value <= 100):\n"
+    "                 dereplication, one representative per group of near-identical genomes, every genome compared with the\n"
+    "                 representatives only (.sketchclusters: genome, representative, estimate, shared/size; NA NA for a\n"
+    "                 representative); any number of genomes; the queries must be among the references [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -212,6 +218,8 @@ Options parse(int argc, char **argv)
     else if (a == "--sketchContain") { const std::string v = need(i); sketchContain = true;
       o.sketchContain = v == "query" ? ANI_CONTAIN_QUERY : v == "reference" ? ANI_CONTAIN_REF : v == "max" ? ANI_CONTAIN_MAX : -1;
       if (o.sketchContain < 0) { std::cerr << "ERROR, --sketchContain takes query or reference or max" << std::endl; exit(1); } }
+    else if (a == "--sketchCluster") { o.sketchCluster = (float)atof(need(i));
+      if (!(o.sketchCluster > 0.0f && o.sketchCluster <= 100.0f)) { std::cerr << "ERROR, --sketchCluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
@@ -601,7 +609,8 @@ void check_sketch_genomes(const Options &o)
     std::cerr << "ERROR, --sketchANI and --treeFill sketch take at most 65536 genomes, this run has " << refs.size() << std::endl; exit(1); }
   for (auto &q : o.queries)
     if (!refs.count(q)) {
-      std::cerr << "ERROR, --sketchANI" << (o.sketchNeighbors ? ", --sketchNeighbors" : "") << " and --treeFill sketch compare the reference genomes: query " << q
+      std::cerr << "ERROR, --sketchANI" << (o.sketchNeighbors ? ", --sketchNeighbors" : "") << (o.sketchCluster > 0.0f ? ", --sketchCluster" : "")
+                << " and --treeFill sketch compare the reference genomes: query " << q
                 << " is not among the references" << std::endl;
       exit(1);
     }
@@ -1616,6 +1625,29 @@ void write_neighbors(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixC
   trace("sketch neighbours written");
 }
 
+// ---- --sketchCluster T: greedy representative clustering of the .matrix genomes under the sketch estimate at >= T
+// (ani_signature_cluster on the first device, minShared = 1: every genome against the representatives only, two records per genome come
+// off the device, and there is no genome ceiling).  .sketchclusters: genomes in .matrix order: genome, representative, estimate as .sketch
+// prints it, shared/size; a representative names itself and has NA in the last two columns.
+void write_sketch_clusters(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const size_t n = mc.names.size();
+  std::vector<uint32_t> sig; std::vector<int32_t> len;
+  matrix_signatures(o, mc, sig, len);
+  std::vector<int32_t> rep(n); std::vector<ani_signeighbor_t> link(n);
+  if (ani_signature_cluster(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchCluster, rep.data(), link.data())) die("ani_signature_cluster");
+  trace("sketch clusters found");
+  BufferedFile f(o.out + ".sketchclusters");
+  for (size_t g = 0; g < n; g++) {
+    f.out << mc.names[g] << "\t" << mc.names[(size_t)rep[g]];
+    if ((size_t)rep[g] == g) f.out << "\tNA\tNA\n";
+    else f.out << "\t" << link[g].identity << "\t" << link[g].shared << "/" << link[g].size << "\n";
+  }
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".sketchclusters" << std::endl; exit(1); }
+  trace("sketch clusters written");
+}
+
 // ---- --sketchScreen K: the K nearest references of every query under the sketch estimate, at least --sketchMinANI
 // (ani_signature_screen on the first device, minShared = 1; the reference signatures are the collected table as it stands, the query
 // signatures a reference's row or the query's own).  .screen: queries in query-list order, one line per reference, nearest first, ties in
@@ -1763,13 +1795,14 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   MatrixCells mc;
-  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors) mc = matrix_cells(o, res.rows, trusted);
+  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
   const char *streamEnv = getenv("ANI_TEST_CLI_SINGLE_STREAM");
   const bool streamed = o.streamable() && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
   if ((o.sketchANI || o.treeFill) && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchNeighbors) write_neighbors(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (o.sketchCluster > 0.0f) write_sketch_clusters(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchScreen) write_screen(o, su.dev[0].ctx, ap.kmerSize);
   if (streamed) write_tree_single_streamed(o, o.out + ".newick", o.out + ".mst", su.dev[0].ctx, ap.kmerSize, mc);
   else if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)

@@ -542,6 +542,43 @@ int ani_signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int
                                  int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode,
                                  ani_signeighbor_t *out /* [nQry * k] */, int32_t *count /* [nQry] */);
 
+/* ---- greedy representative clustering of the genomes under the whole-genome sketch estimate, streamed (no counterpart in the
+ * reference).  Dereplication: one representative per group of near-identical genomes of a large collection.
+ * ani_cluster_greedy over the pairs of ani_signature_pairs in one call that compares a genome with the representatives only, about
+ * nGenomes x representatives pairs instead of nGenomes^2 / 2, keeps every pair on the device and returns two records per genome.
+ * There is no 65 536 ceiling.
+ * 1. Defined by composition.  P = the pairs ani_signature_pairs(sig, len, nGenomes, size, kmerSize, minShared) would return, were it free
+ *    of its ceiling; shared, size and identity of a pair are exactly its rules 2 and 3.
+ * 2. Edges.  {a, b} is an edge iff the pair is in P and bits(identity) >= bits(minIdentity).  Identities are non-negative floats, so the
+ *    order of their values is the order of their bit patterns.  An identity the clamp leaves at 0 is never an edge: minIdentity > 0.
+ * 3. Greedy rule.  Genomes are taken in id order, as in ani_cluster_greedy: genome i is a representative iff no representative j < i has
+ *    an edge to i; every other genome is a member.  A member goes to the adjacent representative with the largest identity, whatever
+ *    its id (a representative with a larger id than the member counts), the smallest id on a tie.
+ * 4. Outputs.  representative[i] = i for a representative, otherwise the id rule 3 chose.  link[i] = {representative[i], shared, size,
+ *    identity} of that pair for a member, the unused record {-1, 0, 0, 0.0f} for a representative.
+ * 5. Equivalence.  representative equals what ani_cluster_greedy returns over one row {refGenomeId = a, qryGenomeId = b, identity} per
+ *    pair of P at the same minIdentity, and link[i].identity equals its identityToRep[i] bit for bit for members.
+ * 6. ANI_ERR_ARG: a null pointer, nGenomes < 0, size outside [1, 4096], kmerSize outside [1, 16], minShared < 1, minIdentity outside
+ *    (0, 100] (NaN included), a len outside [0, size], a signature that does not ascend strictly inside its len.
+ * 7. ANI_ERR_LIMIT: nGenomes > 2^30.  The checks of the scalar arguments run before any allocation.
+ * 8. nGenomes == 0: ANI_OK after the scalar checks, nothing is read or written; sig, len, representative and link may then be null.
+ * 9. The result depends on no schedule, no reduction order, no strip height and no tile shape.
+ * 10. Memory.  The genomes go through the device a strip of rows at a time, twice: once in id order to find the representatives, once
+ *    for the members against the representatives found after their strip.  Device: 8 size nGenomes bytes while the signatures are
+ *    staged (half of it after), the signature rows of the representatives (at most one more copy), 2 size^2 bytes of identities, one
+ *    strip of rows x max(representatives, rows) 4-byte cells, whose height follows the free device memory and is capped by the genome
+ *    count, and 28 bytes per genome.  Nothing follows nGenomes^2.  ANI_TEST_SIG_STRIP_ROWS (tests) forces a strip height (4096 rows at
+ *    the most), ANI_TEST_SIG_SCREEN_SHAPE = square | thin the shape of the merge tile, which otherwise follows the strip height.
+ * ani_signature_cluster_stats: of the context's last ani_signature_cluster call, out[0] = its strips, out[1] = its representatives,
+ * out[2] = the cells its merge launches covered (rows x references of every launch: strip x earlier representatives, strip x strip,
+ * strip x later representatives), out[3] = its resolve steps (sweeps of 256 cells of a representative's row of a strip's own block by
+ * the one workgroup that resolves the strip: the sequential part); all 0 if there was no call or it had no genomes
+ * (tools/sketch_probe.py reports them).  ANI_ERR_ARG: out is null. */
+int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
+                          int32_t minShared, float minIdentity,
+                          int32_t *representative /* [nGenomes] */, ani_signeighbor_t *link /* [nGenomes] */);
+int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4]);   /* strips, representatives, cells merged, resolve steps of the last call */
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */

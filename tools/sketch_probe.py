@@ -24,6 +24,13 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
                                                  and median of the timed calls by HIP events, the merge steps of both rules replayed on
                                                  the host (on a sample of pairs for the larger counts), steps/s, and the time per step
                                                  of the new call over that of the existing one
+    python tools/sketch_probe.py --cluster T     ani_signature_cluster at the threshold T, at 10 000 and 90 000
+                                                 genomes in families of ten (a tenth of the genomes are representatives at any T
+                                                 between 0 and about 97), minShared 1: the call, min .. max and median by HIP events
+                                                 and by the wall clock, and its stats call (strips, representatives, cells merged,
+                                                 resolve steps); up to --compose-max genomes the composition ani_signature_pairs at
+                                                 minShared 1 + ani_cluster_greedy over its rows on the same signatures, timed the same
+                                                 way and compared with the call's result
 
 Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
 smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
@@ -254,6 +261,61 @@ def contain(e, a):
         os.environ.pop(shape_env, None)
 
 
+def family_signatures(rng, n, size=SIZE, family=10):
+    """n genomes in families of `family`: an ancestor of 1.3 size random 32-bit values, every member loses a share of them drawn from
+    0 .. 15 % and gains as many new ones; families are unrelated and share nothing.  In random order, so that the members of a family
+    lie in different strips, before and after their representative."""
+    sig = np.zeros((n, size), dtype=np.uint32)
+    length = np.zeros(n, dtype=np.int32)
+    order = rng.permutation(n)
+    m = size * 13 // 10
+    for f in range(0, n, family):
+        anc = rng.integers(0, 2 ** 32, m, dtype=np.uint64).astype(np.uint32)
+        for g in order[f:f + family]:
+            rate = rng.uniform(0.0, 0.15)
+            new = rng.integers(0, 2 ** 32, int(m * rate), dtype=np.uint64).astype(np.uint32)
+            v = np.unique(np.concatenate([anc[rng.random(m) >= rate], new]))[:size]
+            sig[g, :len(v)] = v
+            length[g] = len(v)
+    return sig, length
+
+
+def cluster(e, a):
+    from fastani_amd.api import CGI_DT
+    rng = np.random.default_rng(1)
+    for n in (10000, 90000):
+        if a.only and n != a.only:
+            continue
+        sig, length = family_signatures(rng, n)
+        got = {}
+        wall, dev = timed_events(lambda: got.__setitem__("r", e.signature_cluster(sig, length, 16, a.cluster)), a.reps)
+        rep, link = got["r"]
+        strips, reps, cells, steps = e.signature_cluster_stats()
+        own = rep == np.arange(n)
+        assert reps == int(own.sum())
+        print("cluster    n=%6d s=%d T=%g: HIP events %s median %.3f ms   wall %s   %d strips, %d representatives, %.3e cells merged (n^2/2 = %.3e), %d resolve steps"
+              "   %d members joined a later representative, estimate to the representative %.2f .. %.2f"
+              % (n, SIZE, a.cluster, span(dev), float(np.median(dev)) * 1e3, span(wall), strips, reps, cells, n * n / 2, steps, int((rep > np.arange(n)).sum()),
+                 float(link["identity"][~own].min()) if (~own).any() else 0.0, float(link["identity"][~own].max()) if (~own).any() else 0.0), flush=True)
+        if n > a.compose_max:
+            print("composition n=%6d: not run (ani_signature_pairs takes at most 65 536 genomes)" % n, flush=True)
+            continue
+        old = {}
+
+        def composition():
+            pairs = e.signature_pairs(sig, length, 16, 1)
+            rows = np.zeros(len(pairs), dtype=CGI_DT)
+            rows["refGenomeId"], rows["qryGenomeId"], rows["identity"] = pairs["a"], pairs["b"], pairs["identity"]
+            old["r"], old["rows"] = e.cluster_greedy(rows, n, a.cluster), len(pairs)
+
+        cwall, cdev = timed_events(composition, a.reps)
+        wrep, wident = old["r"]
+        same = np.array_equal(rep, wrep) and np.array_equal(link["identity"][~own].view(np.uint32), wident[~own].view(np.uint32))
+        assert same
+        print("composition n=%6d s=%d T=%g: HIP events %s median %.3f ms   wall %s   %d pair rows   result identical   call / composition by HIP events: %.3f .. %.3f"
+              % (n, SIZE, a.cluster, span(cdev), float(np.median(cdev)) * 1e3, span(cwall), old["rows"], min(dev) / max(cdev), max(dev) / min(cdev)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", type=int, default=0)
@@ -263,14 +325,15 @@ def main():
     ap.add_argument("--neighbors", action="store_true")
     ap.add_argument("--screen", action="store_true")
     ap.add_argument("--contain", choices=("query", "reference", "max"), default=None)
+    ap.add_argument("--cluster", type=float, default=0.0)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
     if a.contain and not a.screen:
         ap.error("--contain needs --screen")
-    if a.neighbors or a.screen:
+    if a.neighbors or a.screen or a.cluster:
         import fastani_amd
-        (neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
+        (cluster if a.cluster else neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
         return
     import torch
     import fastani_amd
