@@ -18,6 +18,8 @@
                                            plasmids and contigs against whole references, or references inside a larger assembly
     Engine.signature_neighbors(sig, len, k_mer, k)  the k nearest neighbours of every genome under that estimate, streamed strip by
                                            strip, no genome ceiling (no reference counterpart)
+    Engine.signature_graph(sig, len, k_mer, t)  the pairs at or above the threshold t under that estimate or the symmetric containment
+                                           estimate, filtered on the device strip by strip, no genome ceiling
     Engine.signature_cluster(sig, len, k_mer, t)  greedy representative clustering (dereplication) of the genomes under that estimate
                                            at the threshold t: genomes against representatives only, no genome ceiling
 
@@ -143,6 +145,8 @@ def _bind(lib):
         "ani_signature_pairs": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
         "ani_signature_neighbors": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
         "ani_signature_neighbors_strips": (C.c_int, [vp]),
+        "ani_signature_graph": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+        "ani_signature_graph_strips": (C.c_int, [vp]),
         "ani_signature_screen": (C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, vp]),
         "ani_signature_screen_contain": (C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                                    vp, vp]),
@@ -557,6 +561,33 @@ class Engine:
     def signature_neighbors_strips(self):
         """strips the last signature_neighbors call of this engine took (ani_signature_neighbors_strips)"""
         return int(self.lib.ani_signature_neighbors_strips(self.h))
+
+    GRAPH_ESTIMATES = {"mash": 0, "contain": 1}
+
+    def signature_graph(self, sig, length, kmer_size, min_identity=0.0, min_shared=1, estimate="mash", rows=None):
+        """the pairs a < b with a in `rows` = (begin, end) (None: all genomes) and b among all genomes that share at least min_shared
+        values and whose identity is at least min_identity (ani_signature_graph; the semantics are in ani_abi.h).  estimate "mash" (0):
+        the estimate of signature_pairs, so that at min_identity 0 over all rows the result is that of signature_pairs; "contain" (1):
+        the symmetric containment estimate of signature_screen_contain in mode "max", the size field holding the denominator.  The
+        threshold is applied on the device, a strip of rows at a time: no 65 536 ceiling.  -> SIGPAIR_DT array ordered by (a, b)."""
+        if isinstance(estimate, str):
+            if estimate not in self.GRAPH_ESTIMATES:
+                raise ValueError("estimate %r: one of %s, or 0 .. 1" % (estimate, ", ".join(sorted(self.GRAPH_ESTIMATES))))
+            estimate = self.GRAPH_ESTIMATES[estimate]
+        sig = np.ascontiguousarray(sig, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        if sig.ndim != 2 or length.shape != (sig.shape[0],):
+            raise ValueError("sig must be (n, size) and length (n,)")
+        n, size = sig.shape
+        begin, end = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+        p, m = C.c_void_p(), C.c_size_t()
+        self._chk(self.lib.ani_signature_graph(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
+                                               int(min_shared), float(min_identity), int(estimate), begin, end, C.byref(p), C.byref(m)))
+        return self._take(p, m.value, SIGPAIR_DT)
+
+    def signature_graph_strips(self):
+        """strips the last signature_graph call of this engine took (ani_signature_graph_strips)"""
+        return int(self.lib.ani_signature_graph_strips(self.h))
 
     def signature_screen(self, ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared=1, min_identity=0.0):
         """for every query signature its k nearest references under the estimate of signature_pairs, identity >= min_identity, nearest

@@ -5,8 +5,8 @@
 // kernels/tree.hpp), neighbour joining (ani_tree_nj, kernels/nj.hpp) and single linkage with its minimum spanning tree (ani_tree_single,
 // kernels/single.hpp); and the whole-genome sketch estimate that fills the pairs the
 // mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
-// ani_signature_pairs, kernels/sigdist.hpp), with its streamed consumers: neighbours, screens and the greedy clustering of
-// ani_signature_cluster (kernels/sigcluster.hpp).
+// ani_signature_pairs, kernels/sigdist.hpp), with its streamed consumers: neighbours, screens, the greedy clustering of
+// ani_signature_cluster (kernels/sigcluster.hpp) and the pair graph of ani_signature_graph (kernels/siggraph.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -23,6 +23,7 @@
 #include "kernels/sigscreen.hpp"
 #include "kernels/sigcontain.hpp"
 #include "kernels/sigcluster.hpp"
+#include "kernels/siggraph.hpp"
 
 namespace anih {
 using namespace ani;
@@ -1637,6 +1638,106 @@ int signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t
   return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
 }
 
+// ---- the pair graph under either sketch estimate, streamed (ani_signature_graph) ----
+// The signatures are staged and validated as for ani_signature_neighbors and the identity bits of every (shared, size-or-d) come from
+// the host.  The rows of the range go through the device a strip at a time: the strip's cells right of the diagonal (the triangular
+// Mash tiles of k_sigstrip_merge, or the containment walk in mode MAX with the strip as the queries and the genomes from r0 on as the
+// references, its cell pointer moved r0 columns so that both leave cell (a, b) at row a - r0, column b), the kept cells of every row
+// counted and scanned, then written as records behind the row's offset and copied back through page-locked staging.  The host does no
+// arithmetic on them.  Device memory: the signatures twice while they are staged and once after, 2 s (s + 1) bytes of identities, one
+// strip (kSigStripShare of what is free then, at 24 bytes per cell: the cell and, as if every cell were kept, its record) with 8 bytes
+// per row, 20 bytes per kept pair of the strip.  Host: 20 bytes per kept pair of the range.  Nothing follows nGenomes^2.
+// A strip holds at most kSigGraphMaxPairs cells (a forced height included), so the 32-bit sums of its kept cells are exact.
+constexpr uint64_t kSigGraphMaxPairs = 0xfffffff0ull;
+
+int signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
+                    int32_t estimate, int32_t rowBegin, int32_t rowEnd, ani_sigpair_t **rows, size_t *n)
+{
+  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, CNT, OFF, OUT, NBUF };
+  DevBufs B(NBUF);
+  hipStream_t st = ctx->stream;
+  const size_t V = (size_t)nG, R = (size_t)(rowEnd - rowBegin);
+  const int32_t pitch = (size + 3) & ~3;
+  const uint64_t ld = (V + 3) & ~(uint64_t)3;
+  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat, *dOff, *dOut; int32_t *dLen, *dCnt;
+  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
+  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
+  uint32_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
+  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
+  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
+  B.b[RAW].release();
+
+  const bool contain = estimate == ANI_GRAPH_CONTAIN_MAX;
+  const std::vector<uint32_t> table = contain ? sig_contain_table(size, kmerSize) : sig_identity_table(size, kmerSize);
+  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
+  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
+  uint32_t minBits; memcpy(&minBits, &lowest, 4);
+
+  // strip height: a cell and, as if every cell were kept, its record, inside a share of what is free now; the grid of the thin tile
+  // (one row of queries per workgroup) bounds it too, and so do the 32 bits in which device_scan sums the kept cells of a strip: a strip
+  // of at most 2^32 - 16 cells cannot wrap them, whatever is kept, so the limit check below sees every strip's true count
+  size_t freeB = 0, totalB = 0;
+  TRY(ani_device_memory(ctx, &freeB, &totalB));
+  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (24.0 * (double)ld));
+  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
+  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(h, R), 65535), kSigGraphMaxPairs / ld));
+  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat)); TRY(B.get(CNT, (size_t)h * 4, (void **)&dCnt)); TRY(B.get(OFF, (size_t)h * 4, (void **)&dOff));
+
+  const size_t piece = (size_t)1 << 20;                                // records per copy: 20 MiB of staging
+  ani_sigpair_t *stage = nullptr;
+  ani_sigpair_t *out = nullptr;
+  size_t have = 0, cap = 0;
+  struct Guard { ani_sigpair_t **p; ~Guard() { free(*p); } } guard{&out};
+  for (uint64_t r0 = (uint64_t)rowBegin; r0 < (uint64_t)rowEnd; r0 += h) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, (uint64_t)rowEnd), rows1 = r1 - (uint32_t)r0;
+    if (contain) {
+      int32_t shape[2];
+      sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, (uint32_t)(V - r0), dSig, dLen, (uint32_t)r0, r1, pitch, size, ANI_CONTAIN_MAX,
+                       dMat + r0, ld, shape);
+    }
+    else sigstrip_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
+    hipLaunchKernelGGL(k_siggraph_count, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared,
+                       (const uint32_t *)dTable, minBits, dCnt);
+    HIP_TRY(hipGetLastError());
+    ctx->sigGraphStrips++;
+    uint64_t nE = 0;
+    TRY(device_scan(ctx, dCnt, dOff, rows1, &nE, kSigGraphMaxPairs));
+    if ((uint64_t)have + nE > kSigGraphMaxPairs)                       // (before anything of the strip is written)
+      return fail(ANI_ERR_LIMIT, "more than %llu kept pairs in rows [%d, %d): split the range", (unsigned long long)kSigGraphMaxPairs, rowBegin, rowEnd);
+    if (!nE) continue;
+    if (have + (size_t)nE > cap) {
+      const size_t want = std::max<size_t>(have + (size_t)nE, cap + cap / 2);
+      ani_sigpair_t *grown = (ani_sigpair_t *)realloc(out, want * sizeof(ani_sigpair_t));
+      if (!grown) return fail(ANI_ERR_NOMEM, "host allocation of %llu pair rows failed", (unsigned long long)want);
+      out = grown; cap = want;
+    }
+    TRY(B.get(OUT, (size_t)nE * sizeof(ani_sigpair_t), (void **)&dOut));
+    hipLaunchKernelGGL(k_siggraph_write, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared,
+                       (const uint32_t *)dTable, minBits, (const uint32_t *)dOff, dOut);
+    HIP_TRY(hipGetLastError());
+    TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)nE) * sizeof(ani_sigpair_t), (void **)&stage));
+    for (size_t p0 = 0; p0 < (size_t)nE; p0 += piece) {
+      const size_t m = std::min<size_t>(piece, (size_t)nE - p0);
+      HIP_TRY(hipMemcpyAsync(stage, dOut + p0 * kSigGraphRecordWords, m * sizeof(ani_sigpair_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      memcpy(out + have + p0, stage, m * sizeof(ani_sigpair_t));
+    }
+    have += (size_t)nE;
+  }
+  *rows = out; *n = have;
+  out = nullptr;
+  return ANI_OK;
+}
+
 // ---- greedy representative clustering under the sketch estimate (ani_signature_cluster) ----
 // Strip height at the most, by genome count: the strip's own rows x rows block is merged whether greedy clustering needs its pairs or
 // not, so the blocks together (n h cells) stay at a sixteenth of the n^2 / 2 pairs of the composition, within [256, 4096] rows: below
@@ -2099,6 +2200,31 @@ int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *le
 }
 
 int ani_signature_neighbors_strips(const ani_ctx *ctx) { return ctx ? ctx->sigNeighStrips : 0; }
+
+int ani_signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                        float minIdentity, int32_t estimate, int32_t rowBegin, int32_t rowEnd, ani_sigpair_t **rows, size_t *n)
+{
+  if (!ctx || !rows || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
+  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
+  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
+  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (estimate < ANI_GRAPH_MASH || estimate > ANI_GRAPH_CONTAIN_MAX) return fail(ANI_ERR_ARG, "estimate %d outside [0, 1]", estimate);
+  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the pair graph takes at most 2^30", nGenomes);
+  if (rowBegin < 0 || rowBegin > rowEnd || rowEnd > nGenomes) return fail(ANI_ERR_ARG, "rows [%d, %d) outside [0, %d]", rowBegin, rowEnd, nGenomes);
+  ctx->sigGraphStrips = 0;
+  *rows = nullptr; *n = 0;
+  if (nGenomes <= 1 || rowBegin == rowEnd) return ANI_OK;
+  if (!sig || !len) return fail(ANI_ERR_ARG, "null argument");
+  for (int32_t g = 0; g < nGenomes; g++)
+    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try { return signature_graph(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, estimate, rowBegin, rowEnd, rows, n); }
+  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_graph_strips(const ani_ctx *ctx) { return ctx ? ctx->sigGraphStrips : 0; }
 
 // the two screen calls: the checks of ani_signature_screen's rules 4 - 6 and, with `contain`, of ani_signature_screen_contain's rule 7,
 // then the call; without `contain` it is ani_signature_screen and the mode plays no part

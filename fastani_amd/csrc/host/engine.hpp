@@ -363,6 +363,7 @@ struct ani_ctx {
   int treeSingleRounds = 0;                                                        // spanning-forest rounds of the last ani_tree_single[_sketch] (ani_tree_single_rounds)
   std::vector<uint64_t> sigStripEdges;                                             // edges kept per strip of the last ani_tree_single_sketch
   int sigNeighStrips = 0;                                                          // strips of the last ani_signature_neighbors
+  int sigGraphStrips = 0;                                                          // strips of the last ani_signature_graph
   int sigScreenStrips = 0;                                                         // strips of the last screen call (ani_signature_screen, ani_signature_screen_contain)
   int32_t sigScreenTile[2] = {0, 0};                                               // queries x references of the tile of its last strip
   uint64_t sigClusterStats[4] = {0, 0, 0, 0};                                      // strips, representatives, cells merged, resolve steps of the last ani_signature_cluster

@@ -13,7 +13,8 @@
 // ani_signature_neighbors: any number of genomes), `--sketchScreen K` a .screen file (the K nearest references of every query under that
 // estimate, ani_signature_screen: the queries need not be references; with `--sketchContain query|reference|max` under the containment
 // estimate, ani_signature_screen_contain), `--sketchCluster T` a .sketchclusters file (greedy representative clustering under the
-// estimate, ani_signature_cluster: any number of genomes).  Sketch / Map / computeCGI run on the GPU(s)
+// estimate, ani_signature_cluster: any number of genomes), `--sketchGraph T` a .sketchgraph file (the pairs at an estimate of at least
+// T, ani_signature_graph: any number of genomes, with `--sketchContain max` under the containment estimate).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
 // Ingest: files are parsed block-wise on `-t` reader threads, a slice (~1 Gbase) ahead of the GPU; a slice is
@@ -81,7 +82,8 @@ struct Options {
   int sketchScreen = 0;                                // --sketchScreen K: the .screen file (0 = off)
   int sketchContain = -1;                              // --sketchContain MODE: .screen under the containment estimate (an ani_contain_mode; -1 = off)
   float sketchCluster = 0.0f;                          // --sketchCluster T: the .sketchclusters file, greedy clustering under the estimate at >= T (0 = off)
-  bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f; }   // these compare the references with each other
+  float sketchGraph = 0.0f;                            // --sketchGraph T: the .sketchgraph file, the pairs at an estimate >= T, streamed (0 = off)
+  bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
   bool pairStep() const { return sketchANI || (treeFill && !(tree && treeSingle)); }
@@ -104,6 +106,7 @@ struct Options {
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
+    "             [--sketchGraph <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -148,6 +151,8 @@ struct Options {
     "                 dereplication, one representative per group of near-identical genomes, every genome compared with the\n"
     "                 representatives only (.sketchclusters: genome, representative, estimate, shared/size; NA NA for a\n"
     "                 representative); any number of genomes; the queries must be among the references [disabled by default]\n"
+    "     --sketchGraph <value>  also output every pair of genomes at an estimate of at least this (0 < value <= 100), as --sketchANI\n"
+    "                 prints it (.sketchgraph); any number of genomes; --sketchContain max: the containment estimate [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -221,6 +226,8 @@ Options parse(int argc, char **argv)
     else if (a == "--sketchCluster") { o.sketchCluster = (float)atof(need(i));
       if (!(o.sketchCluster > 0.0f && o.sketchCluster <= 100.0f)) { std::cerr << "ERROR, --sketchCluster takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "-o" || a == "--output") o.out = need(i);
+    else if (a == "--sketchGraph") { o.sketchGraph = (float)atof(need(i));
+      if (!(o.sketchGraph > 0.0f && o.sketchGraph <= 100.0f)) { std::cerr << "ERROR, --sketchGraph takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
     else if (a == "--saveSketch") o.saveSketch = need(i);
@@ -236,7 +243,9 @@ Options parse(int argc, char **argv)
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
   if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors && !o.sketchScreen) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
-  if (sketchContain && !o.sketchScreen) { std::cerr << "ERROR, --sketchContain needs --sketchScreen" << std::endl; exit(1); }
+  if (sketchContain && !o.sketchScreen && !(o.sketchGraph > 0.0f)) { std::cerr << "ERROR, --sketchContain needs --sketchScreen" << std::endl; exit(1); }
+  if (o.sketchGraph > 0.0f && sketchContain && o.sketchContain != ANI_CONTAIN_MAX) { std::cerr << "ERROR, --sketchGraph takes --sketchContain max only" << std::endl;
+    exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -610,7 +619,7 @@ void check_sketch_genomes(const Options &o)
   for (auto &q : o.queries)
     if (!refs.count(q)) {
       std::cerr << "ERROR, --sketchANI" << (o.sketchNeighbors ? ", --sketchNeighbors" : "") << (o.sketchCluster > 0.0f ? ", --sketchCluster" : "")
-                << " and --treeFill sketch compare the reference genomes: query " << q
+                << (o.sketchGraph > 0.0f ? ", --sketchGraph" : "") << " and --treeFill sketch compare the reference genomes: query " << q
                 << " is not among the references" << std::endl;
       exit(1);
     }
@@ -1648,6 +1657,36 @@ void write_sketch_clusters(const Options &o, ani_ctx *ctx, int kmerSize, const M
   trace("sketch clusters written");
 }
 
+// ---- --sketchGraph T: every pair of .matrix genomes whose sketch estimate is at least T (ani_signature_graph on the first device,
+// minShared = 1: the threshold is applied on the device, the pairs below it never exist on the host, and there is no genome ceiling).
+// .sketchgraph: one line per pair in (a, b) order of the .matrix numbering, printed as .sketch prints it: genome, genome, estimate,
+// shared/size.  With --sketchContain max the estimate is the symmetric containment one and the last column shared/denominator.  The
+// file is written a range of rows at a time, max(1, 2^26 / genomes) of them (ANI_TEST_CLI_GRAPH_ROWS forces a height, for tests), so
+// that the host never holds more than about 1.3 GB of records; the file does not depend on the height.
+void write_sketch_graph(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
+{
+  const size_t n = mc.names.size();
+  std::vector<uint32_t> sig; std::vector<int32_t> len;
+  matrix_signatures(o, mc, sig, len);
+  size_t height = std::max<size_t>(1, ((size_t)1 << 26) / std::max<size_t>(n, 1));
+  if (const char *ev = getenv("ANI_TEST_CLI_GRAPH_ROWS")) { const long long v = atoll(ev); if (v >= 1) height = (size_t)v; }
+  const int32_t estimate = o.sketchContain == ANI_CONTAIN_MAX ? ANI_GRAPH_CONTAIN_MAX : ANI_GRAPH_MASH;
+  BufferedFile f(o.out + ".sketchgraph");
+  for (size_t r0 = 0; r0 < n; r0 += height) {
+    const size_t r1 = std::min(n, r0 + height);
+    ani_sigpair_t *rows = nullptr; size_t nr = 0;
+    if (ani_signature_graph(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchGraph, estimate, (int32_t)r0, (int32_t)r1, &rows, &nr))
+      die("ani_signature_graph");
+    for (size_t i = 0; i < nr; i++)
+      f.out << mc.names[(size_t)rows[i].a] << "\t" << mc.names[(size_t)rows[i].b] << "\t" << rows[i].identity << "\t" << rows[i].shared << "/" << rows[i].size << "\n";
+    ani_free(rows);
+  }
+  trace("sketch graph found");
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << o.out << ".sketchgraph" << std::endl; exit(1); }
+  trace("sketch graph written");
+}
+
 // ---- --sketchScreen K: the K nearest references of every query under the sketch estimate, at least --sketchMinANI
 // (ani_signature_screen on the first device, minShared = 1; the reference signatures are the collected table as it stands, the query
 // signatures a reference's row or the query's own).  .screen: queries in query-list order, one line per reference, nearest first, ties in
@@ -1795,7 +1834,7 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   MatrixCells mc;
-  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f) mc = matrix_cells(o, res.rows, trusted);
+  if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
   const char *streamEnv = getenv("ANI_TEST_CLI_SINGLE_STREAM");
@@ -1803,6 +1842,7 @@ int main(int argc, char **argv)
   if ((o.sketchANI || o.treeFill) && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchNeighbors) write_neighbors(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchCluster > 0.0f) write_sketch_clusters(o, su.dev[0].ctx, ap.kmerSize, mc);
+  if (o.sketchGraph > 0.0f) write_sketch_graph(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchScreen) write_screen(o, su.dev[0].ctx, ap.kmerSize);
   if (streamed) write_tree_single_streamed(o, o.out + ".newick", o.out + ".mst", su.dev[0].ctx, ap.kmerSize, mc);
   else if (o.tree && o.treeNj) write_tree_nj(o.out + ".newick", su.dev[0].ctx, mc, fill);      // (all before write_matrix, which sorts the cells in place)

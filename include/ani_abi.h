@@ -579,6 +579,41 @@ int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len,
                           int32_t *representative /* [nGenomes] */, ani_signeighbor_t *link /* [nGenomes] */);
 int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4]);   /* strips, representatives, cells merged, resolve steps of the last call */
 
+/* ---- the pair graph of the genomes under either whole-genome sketch estimate, streamed (no counterpart in the reference; DESIGN.md
+ * section 2.21).  The pair list of ani_signature_pairs, filtered on the device by an identity threshold and made a strip of rows at a
+ * time: what clustering and graph tools take as their input.  There is no 65 536 ceiling, and containment is available for all pairs.
+ * 1. ANI_GRAPH_MASH: shared, size and identity of a pair (a, b), a < b, are exactly rules 2 and 3 of ani_signature_pairs, were it free
+ *    of its ceiling.
+ * 2. ANI_GRAPH_CONTAIN_MAX: Q is the signature of a and R the signature of b; shared, inQ, inR, d = min(inQ, inR) and identity are
+ *    exactly rules 1 - 5 of ani_signature_screen_contain in mode ANI_CONTAIN_MAX.  This is symmetric, so which genome is Q does not
+ *    matter.  The record's `size` field holds d.
+ * 3. A pair is kept iff shared >= minShared and bits(identity) >= bits(minIdentity).  Identities are non-negative floats, so the order
+ *    of their values is the order of their bit patterns; a minIdentity of -0.0 is 0.  At minIdentity = 0 a pair that the clamp leaves at
+ *    identity 0 is kept: at ANI_GRAPH_MASH, minIdentity 0 and the full range the call returns exactly the records of ani_signature_pairs.
+ * 4. *rows holds the kept pairs with rowBegin <= a < rowEnd and b > a, b over all of (a, nGenomes), ordered by (a, b).  The identity is
+ *    the float the host arithmetic of the defining call yields, bit for bit.  ani_free releases *rows.  Row ranges are independent, and
+ *    the concatenation of the results of a split range is the result of the whole range.
+ * 5. ANI_ERR_ARG: a null pointer, nGenomes < 0, size outside [1, 4096], kmerSize outside [1, 16], minShared < 1, minIdentity outside
+ *    [0, 100] (NaN included), estimate outside 0 .. 1, not 0 <= rowBegin <= rowEnd <= nGenomes, a len outside [0, size], a signature
+ *    that does not ascend strictly inside its len.
+ * 6. ANI_ERR_LIMIT: nGenomes > 2^30, or more than 2^32 - 16 kept pairs in the range: the caller splits the range.  The checks of the
+ *    scalar arguments run before any allocation.
+ * 7. nGenomes <= 1 or rowBegin == rowEnd: ANI_OK after the scalar checks, *rows = NULL and *n = 0; nothing else is read, and sig and len
+ *    may then be null.  A range without a kept pair also yields *rows = NULL and *n = 0.
+ * 8. The result depends on no schedule, no reduction order and no strip height.
+ * 9. Memory.  The rows of the range go through the device a strip at a time.  Device: 8 size nGenomes bytes while the signatures are
+ *    staged (half of it after), as ani_signature_neighbors stages them, 2 size^2 bytes of identity bits, one strip of rows x nGenomes
+ *    4-byte cells, whose height follows the free device memory, 4 bytes per row of a strip for each of its counts and offsets, and 20
+ *    bytes per kept pair of a strip.  Host: 20 bytes per kept pair of the range.  Nothing follows nGenomes^2.  ANI_TEST_SIG_STRIP_ROWS
+ *    (tests) forces a strip height.
+ * ani_signature_graph_strips: the strips the context's last ani_signature_graph call took; 0 if it needed none or there was no call
+ * (tools/sketch_probe.py reports it). */
+typedef enum { ANI_GRAPH_MASH = 0, ANI_GRAPH_CONTAIN_MAX = 1 } ani_graph_estimate;
+int ani_signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
+                        int32_t minShared, float minIdentity, int32_t estimate, int32_t rowBegin, int32_t rowEnd,
+                        ani_sigpair_t **rows, size_t *n);
+int ani_signature_graph_strips(const ani_ctx *ctx);
+
 /* ---- synthetic genomes (benchmark input generator; DESIGN.md §Synthetic data) ----
  * Writes nGenomes genomes of genomeLen bases, 2-bit packed, genome i at word offset i*ceil(genomeLen/16) of devOut
  * (device memory, caller-allocated).  `variant` re-draws the substitutions with the cluster ancestors kept (0 = base set). */

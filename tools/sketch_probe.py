@@ -31,6 +31,14 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
                                                  resolve steps); up to --compose-max genomes the composition ani_signature_pairs at
                                                  minShared 1 + ani_cluster_greedy over its rows on the same signatures, timed the same
                                                  way and compared with the call's result
+    python tools/sketch_probe.py --graph T [--contain max]
+                                                 ani_signature_graph at the threshold T, at 10 000 and 90 000
+                                                 genomes in families of ten, minShared 1, all rows in one call, under the Mash estimate
+                                                 or with --contain max the containment estimate: min .. max and median by HIP events and
+                                                 by the wall clock, its strips and its kept pairs; under the Mash estimate and up to
+                                                 --compose-max genomes the composition ani_signature_pairs at minShared 1 + a numpy
+                                                 filter by identity bits on the same signatures in the same process, timed the same way
+                                                 and compared with the call's records
 
 Signatures for the pair call: every genome draws its values from a universe of 6 000 with a density of its own and keeps the 1 000
 smallest, so pairs stop anywhere between a few hundred and the full 1 000 union elements.  Merge steps are counted by replaying the
@@ -316,6 +324,36 @@ def cluster(e, a):
               % (n, SIZE, a.cluster, span(cdev), float(np.median(cdev)) * 1e3, span(cwall), old["rows"], min(dev) / max(cdev), max(dev) / min(cdev)), flush=True)
 
 
+def graph(e, a):
+    rng = np.random.default_rng(1)
+    estimate = "contain" if a.contain else "mash"
+    low = np.float32(a.graph).view(np.uint32)
+    for n in (10000, 90000):
+        if a.only and n != a.only:
+            continue
+        sig, length = family_signatures(rng, n)
+        got = {}
+        wall, dev = timed_events(lambda: got.__setitem__("r", e.signature_graph(sig, length, 16, a.graph, 1, estimate)), a.reps)
+        print("graph      n=%6d s=%d T=%g %s: HIP events %s median %.3f ms   wall %s median %.3f ms   %d strips, %d kept pairs"
+              % (n, SIZE, a.graph, estimate, span(dev), float(np.median(dev)) * 1e3, span(wall), float(np.median(wall)) * 1e3, e.signature_graph_strips(), len(got["r"])),
+              flush=True)
+        if estimate != "mash" or n > a.compose_max:
+            print("composition n=%6d: not run (%s)" % (n, "ani_signature_pairs knows the Mash estimate only" if estimate != "mash"
+                                                      else "ani_signature_pairs takes at most 65 536 genomes"), flush=True)
+            continue
+        old = {}
+
+        def composition():
+            pairs = e.signature_pairs(sig, length, 16, 1)
+            old["r"], old["rows"] = pairs[pairs["identity"].view(np.uint32) >= low], len(pairs)
+
+        cwall, cdev = timed_events(composition, a.reps)
+        assert np.array_equal(got["r"], old["r"])
+        print("composition n=%6d s=%d T=%g: HIP events %s median %.3f ms   wall %s median %.3f ms   %d pair rows   records identical   call / composition by the wall clock: "
+              "%.3f .. %.3f" % (n, SIZE, a.graph, span(cdev), float(np.median(cdev)) * 1e3, span(cwall), float(np.median(cwall)) * 1e3, old["rows"],
+                                min(wall) / max(cwall), max(wall) / min(cwall)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", type=int, default=0)
@@ -326,14 +364,17 @@ def main():
     ap.add_argument("--screen", action="store_true")
     ap.add_argument("--contain", choices=("query", "reference", "max"), default=None)
     ap.add_argument("--cluster", type=float, default=0.0)
+    ap.add_argument("--graph", type=float, default=0.0)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
-    if a.contain and not a.screen:
-        ap.error("--contain needs --screen")
-    if a.neighbors or a.screen or a.cluster:
+    if a.contain and not a.screen and not a.graph:
+        ap.error("--contain needs --screen or --graph")
+    if a.graph and a.contain not in (None, "max"):
+        ap.error("--graph takes --contain max only")
+    if a.neighbors or a.screen or a.cluster or a.graph:
         import fastani_amd
-        (cluster if a.cluster else neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
+        (graph if a.graph else cluster if a.cluster else neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
         return
     import torch
     import fastani_amd
