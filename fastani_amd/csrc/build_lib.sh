@@ -15,7 +15,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 LLVM=${LLVM_BIN:-/opt/rocm/lib/llvm/bin}
 OUT=${1:-$HERE/libfastani_amd.so}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC ${ANI_EXTRA_FLAGS:-}"
-UNITS="engine_core engine_ingest engine_sketch engine_index engine_map engine_l2 sort_device"
+UNITS="engine_core engine_ingest engine_sketch engine_index engine_map engine_l2 sort_device prim_check"
 # per-unit flags: the L2 codes / simulation kernels with the max-ILP scheduler (engine_l2.hip says why); ANI_L2_UNIT_FLAGS="" builds them like the rest
 unit_flags() { if [ "$1" = "engine_l2" ]; then echo "${ANI_L2_UNIT_FLAGS--mllvm -amdgpu-sched-strategy=max-ilp}"; fi; }
 T=$(mktemp -d)

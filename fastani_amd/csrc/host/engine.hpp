@@ -7,6 +7,7 @@
 // engine_map.hip     L1 + L2 + identity + reducer (≙ Map::mapQuery ... cgi::computeCGI)              (computeMap.hpp:112-545, computeCoreIdentity.hpp:166-298)
 //   engine_l2.hip      the launches of k_l2_codes / k_l2_sim (a unit of its own for its compiler flags: build_lib.sh)
 //   sort_device.hip    the radix sort
+//   prim_check.hip     test infrastructure: the primitives of kernels/common.hpp and the prefix sum, callable on their own
 // Kernels live in kernels/*.hpp (internal linkage: a unit compiles the ones it launches).  Nothing here crosses the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +51,13 @@ extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN,
                               uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint64_t *tmpV, uint32_t *sHash, uint64_t *sSW,
                               void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream);
 extern "C" int ani_sort_check(void *tmp, hipStream_t stream);
+
+// TEST INFRASTRUCTURE (prim_check.hip; not part of include/ani_abi.h, no product code calls them): the workgroup primitives of
+// kernels/common.hpp run by small check kernels, one workgroup per slot of `in` / `out` (the file's header has the table of ops), and
+// anih::device_scan on the context's stream.  tests/test_primitives.py holds them to numpy.
+struct ani_ctx;
+extern "C" int ani_prim_check(int op, const void *in, void *out, const int32_t *sizes, int blocks, int cap, int threads, hipStream_t stream);
+extern "C" int ani_prim_device_scan(ani_ctx *ctx, const int32_t *in, uint32_t *out, uint32_t n, uint64_t *total, uint64_t limit);
 
 namespace ani { struct TableSlot; }
 

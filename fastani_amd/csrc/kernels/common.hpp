@@ -159,7 +159,8 @@ __device__ __forceinline__ int wave_incl_scan(int v)
 
 // The same scan over the DPP data path (gfx9 wave64: row_shr 1 / 2 / 4 / 8 inside the rows of 16 lanes, then row_bcast:15 into rows 1 and
 // 3, row_bcast:31 into rows 2 and 3): six v_add_u32_dpp instead of six ds_bpermute round trips with their selects.  Lanes without a
-// source (bound_ctrl off, `old` = 0) add nothing.  Checked against wave_incl_scan on the hardware by tools/ubench/lanexor.hip.
+// source (bound_ctrl off, `old` = 0) add nothing.  Checked against wave_incl_scan on the hardware by tools/ubench/lanexor.hip, and held to
+// np.cumsum by tests/test_primitives.py (test_gpu_wave_scans).
 __device__ __forceinline__ int wave_incl_scan_dpp(int v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -350,7 +351,8 @@ __device__ inline void block_bitonic_sort(K *a, int n2)
 // (lane_xor below; no LDS bandwidth, no bank conflicts, no barrier); only strides that pair two WAVES go through LDS (3 of the 55
 // stages at 1024 keys in four waves).
 // ---------------------------------------------------------------------------------------------
-// value of lane ^ M for M = 1, 2, 4, 8, 16, 32.  (Checked lane by lane on an MI355X: tools/ubench/lanexor.hip.)
+// value of lane ^ M for M = 1, 2, 4, 8, 16, 32.  (Checked lane by lane on an MI355X: tools/ubench/lanexor.hip, and in every wave of a
+// workgroup, 32 and 64 bit, by tests/test_primitives.py: test_gpu_lane_xor.)
 template <int M> __device__ __forceinline__ uint32_t lane_xor(uint32_t x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
