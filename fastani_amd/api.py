@@ -22,6 +22,8 @@
                                            estimate, filtered on the device strip by strip, no genome ceiling
     Engine.signature_cluster(sig, len, k_mer, t)  greedy representative clustering (dereplication) of the genomes under that estimate
                                            at the threshold t: genomes against representatives only, no genome ceiling
+    Engine.signature_cluster_contain(sig, len, k_mer, t)  the same under the symmetric containment estimate: partial genomes (MAGs of
+                                           unequal completeness) join the genome they are parts of
 
 Everything here is plumbing: numpy arrays in, numpy record arrays out.  All compute happens in
 libfastani_amd.so (hand-written HIP kernels, gfx950); there is no Python or CPU fallback.
@@ -153,6 +155,7 @@ def _bind(lib):
         "ani_signature_screen_strips": (C.c_int, [vp]),
         "ani_signature_screen_tile": (None, [vp, vp, vp]),
         "ani_signature_cluster": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, vp]),
+        "ani_signature_cluster_contain": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, vp]),
         "ani_signature_cluster_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
@@ -604,11 +607,15 @@ class Engine:
         (0): how much of the query is in the reference, for partial genomes, plasmids and contigs; "reference" (1): how much of the
         reference is in the query, for references inside a larger assembly; "max" (2): the larger of the two, symmetric.
         -> (neighbors, count) as signature_screen; the size field of a record is the denominator."""
+        return self._screen(ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, self._contain_mode(mode))
+
+    def _contain_mode(self, mode):
+        """a containment mode by name or number -> its number"""
         if isinstance(mode, str):
             if mode not in self.CONTAIN_MODES:
                 raise ValueError("mode %r: one of %s, or 0 .. 2" % (mode, ", ".join(sorted(self.CONTAIN_MODES))))
             mode = self.CONTAIN_MODES[mode]
-        return self._screen(ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, int(mode))
+        return int(mode)
 
     def _screen(self, ref_sig, ref_length, qry_sig, qry_length, kmer_size, k, min_shared, min_identity, mode):
         """the two screen calls: mode None is ani_signature_screen, 0 .. 2 ani_signature_screen_contain"""
@@ -648,6 +655,18 @@ class Engine:
         What cluster_greedy gives over the rows of signature_pairs, without the pairs: every genome is compared with the
         representatives only, and there is no 65 536 ceiling.  -> (representative, link): int32 (n,), and NEIGHBOR_DT (n,) with the
         representative, shared, size and identity of a member's pair, (-1, 0, 0, 0.0) for a representative."""
+        return self._cluster(sig, length, kmer_size, min_identity, min_shared, None)
+
+    def signature_cluster_contain(self, sig, length, kmer_size, min_identity, mode="max", min_shared=1):
+        """signature_cluster under the containment estimate of signature_screen_contain (ani_signature_cluster_contain; the semantics
+        are in ani_abi.h): a pair is judged by the share of the smaller genome, so that partial genomes, such as metagenome bins of
+        unequal completeness, join the genome they are parts of.  mode must be "max" (2): the greedy rule needs a symmetric
+        estimate, and the library refuses the other two.  -> (representative, link) as signature_cluster; the size field of a link is
+        the denominator.  What cluster_greedy gives over the rows of signature_graph(estimate="contain", min_identity=0)."""
+        return self._cluster(sig, length, kmer_size, min_identity, min_shared, self._contain_mode(mode))
+
+    def _cluster(self, sig, length, kmer_size, min_identity, min_shared, mode):
+        """the two cluster calls: mode None is ani_signature_cluster, otherwise ani_signature_cluster_contain"""
         sig = np.ascontiguousarray(sig, dtype=np.uint32)
         length = np.ascontiguousarray(length, dtype=np.int32)
         if sig.ndim != 2 or length.shape != (sig.shape[0],):
@@ -655,14 +674,18 @@ class Engine:
         n, size = sig.shape
         representative = np.zeros(n, dtype=np.int32)
         link = np.zeros(n, dtype=NEIGHBOR_DT)
-        self._chk(self.lib.ani_signature_cluster(self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size),
-                                                 int(min_shared), float(min_identity), representative.ctypes.data if n else None,
-                                                 link.ctypes.data if n else None))
+        head = (self.h, sig.ctypes.data if n else None, length.ctypes.data if n else None, n, size, int(kmer_size), int(min_shared), float(min_identity))
+        tail = (representative.ctypes.data if n else None, link.ctypes.data if n else None)
+        if mode is None:
+            self._chk(self.lib.ani_signature_cluster(*head, *tail))
+        else:
+            self._chk(self.lib.ani_signature_cluster_contain(*head, mode, *tail))
         return representative, link
 
     def signature_cluster_stats(self):
-        """(strips, representatives, cells merged, resolve steps) of the last signature_cluster call of this engine
-        (ani_signature_cluster_stats)"""
+        """(strips, representatives, cells walked, resolve steps) of the last signature_cluster or signature_cluster_contain call of
+        this engine (ani_signature_cluster_stats); a strip's own block counts rows (rows - 1) / 2 cells where it is made from its
+        upper triangle"""
         out = (C.c_uint64 * 4)()
         self._chk(self.lib.ani_signature_cluster_stats(self.h, out))
         return tuple(int(x) for x in out)

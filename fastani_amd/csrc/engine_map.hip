@@ -6,7 +6,7 @@
 // kernels/single.hpp); and the whole-genome sketch estimate that fills the pairs the
 // mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
 // ani_signature_pairs, kernels/sigdist.hpp), with its streamed consumers: neighbours, screens, the greedy clustering of
-// ani_signature_cluster (kernels/sigcluster.hpp) and the pair graph of ani_signature_graph (kernels/siggraph.hpp).
+// ani_signature_cluster and ani_signature_cluster_contain (kernels/sigcluster.hpp) and the pair graph of ani_signature_graph (kernels/siggraph.hpp).
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -1408,8 +1408,18 @@ static std::vector<uint32_t> sig_identity_table(int32_t size, int32_t kmerSize)
   return table;
 }
 
-// bits(identity) of every (shared, d) with 1 <= shared <= d <= size under the containment estimate (ani_signature_screen_contain, rule 5),
-// in the same triangular layout
+// identity of a pair under the containment estimate from its exact integers (ani_signature_screen_contain, rule 5): one double
+// expression, rounded once
+static inline float sig_contain_identity(int32_t shared, int32_t d, int32_t kmerSize)
+{
+  if (shared == 0) return 0.0f;
+  double id = 100.0 * pow((double)shared / (double)d, 1.0 / (double)kmerSize);
+  if (id < 0.0) id = 0.0;
+  if (id > 100.0) id = 100.0;
+  return (float)id;
+}
+
+// bits(identity) of every (shared, d) with 1 <= shared <= d <= size under the containment estimate, in the same triangular layout
 static std::vector<uint32_t> sig_contain_table(int32_t size, int32_t kmerSize)
 {
   const size_t S = (size_t)size;
@@ -1417,10 +1427,7 @@ static std::vector<uint32_t> sig_contain_table(int32_t size, int32_t kmerSize)
   parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
     const int32_t d = (int32_t)i + 1;
     for (int32_t sh = 1; sh <= d; sh++) {
-      double id = 100.0 * pow((double)sh / (double)d, 1.0 / (double)kmerSize);
-      if (id < 0.0) id = 0.0;
-      if (id > 100.0) id = 100.0;
-      const float w = (float)id;
+      const float w = sig_contain_identity(sh, d, kmerSize);
       memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)d)], &w, 4);
     }
   });
@@ -1745,6 +1752,18 @@ int signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32
 // of a strip do not fit the LDS the resolve kernel declares.
 static uint64_t sigcluster_strip_cap(uint64_t n) { return std::min<uint64_t>(std::max<uint64_t>(n / 32, 256), (uint64_t)kSigClusterMaxStrip); }
 
+// The strip's own rows x rows block under the containment estimate in mode MAX, from its upper triangle (k_sigcontain_tri, DESIGN.md
+// section 2.22): the square tile of the row pitch at every strip height.  A strip lower than the tile is one diagonal tile, which stages
+// the strip's rows once, so the thin tile of sigscreen_launch has nothing to save here and ANI_TEST_SIG_SCREEN_SHAPE does not act.
+static void sigcontain_tri_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t h, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld)
+{
+  auto tiles = [&](uint32_t t) { const uint32_t n = (h + t - 1) / t; return dim3(n * (n + 1) / 2); };
+  if (pitch <= 256) hipLaunchKernelGGL((k_sigcontain_tri<16, 8192 + kSigContainPad>), tiles(16), dim3(256), 0, st, sig, len, h, pitch, size, mat, ld);
+  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigcontain_tri<16, kSigTileWords + kSigContainPad>), tiles(16), dim3(256), 0, st, sig, len, h, pitch, size, mat, ld);
+  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigcontain_tri<8, kSigTileWords + kSigContainPad>), tiles(8), dim3(64), 0, st, sig, len, h, pitch, size, mat, ld);
+  else hipLaunchKernelGGL((k_sigcontain_tri<4, kSigTileWords + kSigContainPad>), tiles(4), dim3(64), 0, st, sig, len, h, pitch, size, mat, ld);
+}
+
 // The signatures are staged and validated as for ani_signature_pairs and the identity bits of every (shared, size') come from the host.
 // First sweep, strips in id order: the strip against the representatives found before it (k_sigscreen_merge with the representatives'
 // rows as the references, then k_sigcluster_best), the strip against itself and k_sigcluster_resolve, which names the strip's
@@ -1753,8 +1772,13 @@ static uint64_t sigcluster_strip_cap(uint64_t n) { return std::min<uint64_t>(std
 // per strip of the first sweep, for the count of representatives, which sizes the next launches.  Device memory: the signatures twice
 // while they are staged and once after, the representatives' rows (room for every genome: one more copy at the most), 2 s (s + 1) bytes
 // of identities, 28 bytes per genome, and one strip of rows x max(representatives, rows) 4-byte cells.  Nothing follows nGenomes^2.
-int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
-                      int32_t *representative, ani_signeighbor_t *link)
+// Shared by the two estimates: mode < 0 is ani_signature_cluster (the Mash merge, sig_identity_table); mode ANI_CONTAIN_MAX is
+// ani_signature_cluster_contain: the containment walk in the rectangular launches, sig_contain_table, and the
+// strip's own block from its upper triangle, whose cells are symmetric in that mode, unless ANI_TEST_SIG_CLUSTER_TRI = 0 (tests,
+// tools/sketch_probe.py) sends it through the full rows x rows launch as well.  stats[2] counts the cells walked: rows (rows - 1) / 2 for
+// a triangular launch.
+static int cluster_run(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
+                       int32_t mode, int32_t *representative, ani_signeighbor_t *link)
 {
   enum { RAW, LEN, SIG, FLAGS, TABLE, REPSIG, REPLEN, REPID, REPCNT, BEST, CELL, MEMLEN, MAT, NBUF };
   DevBufs B(NBUF);
@@ -1777,11 +1801,13 @@ int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int
   if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
   B.b[RAW].release();
 
-  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
+  const std::vector<uint32_t> table = mode < 0 ? sig_identity_table(size, kmerSize) : sig_contain_table(size, kmerSize);
   TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
   HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
   uint32_t minBits; memcpy(&minBits, &minIdentity, 4);                 // (> 0: a running best of 0 is "no edge")
+  bool tri = mode >= 0;
+  if (const char *ev = getenv("ANI_TEST_SIG_CLUSTER_TRI")) { if (!strcmp(ev, "0")) tri = false; }
 
   TRY(B.get(REPSIG, V * (size_t)pitch * 4, (void **)&dRepSig)); TRY(B.get(REPLEN, V * 4, (void **)&dRepLen)); TRY(B.get(REPID, V * 4, (void **)&dRepId));
   TRY(B.get(REPCNT, 64, (void **)&dRepCnt)); TRY(B.get(BEST, V * 8, (void **)&dBest)); TRY(B.get(CELL, V * 4, (void **)&dCell));
@@ -1806,17 +1832,18 @@ int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int
     TRY(B.get(MAT, (size_t)rows1 * (size_t)quads(std::max<uint64_t>(std::min<uint64_t>(2 * (uint64_t)nRep, V), h)) * 4, (void **)&dMat));
     if (nRep) {
       const uint64_t ld = quads(nRep);
-      sigscreen_launch(st, dRepSig, dRepLen, nRep, dSig, dLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+      sigscreen_launch(st, dRepSig, dRepLen, nRep, dSig, dLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
       hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, nRep, (const uint32_t *)dRepId, minShared,
                          (const uint32_t *)dTable, minBits, dBest, dCell);
       stats[2] += (uint64_t)rows1 * nRep;
     }
     const uint64_t ld = quads(rows1);
-    sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, dSig, dLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+    if (tri) sigcontain_tri_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, pitch, size, dMat, ld);
+    else sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, dSig, dLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
     hipLaunchKernelGGL(k_sigcluster_resolve, dim3(1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, rows1, nRep, minShared, (const uint32_t *)dTable,
                        minBits, (const int32_t *)dLen, dBest, dCell, dMemLen, dRepId, dRepCnt);
     HIP_TRY(hipGetLastError());
-    stats[2] += (uint64_t)rows1 * rows1;
+    stats[2] += tri ? (uint64_t)rows1 * (rows1 - 1) / 2 : (uint64_t)rows1 * rows1;
     HIP_TRY(hipMemcpyAsync(host, dRepCnt, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t found = host[0] - nRep;
@@ -1843,7 +1870,7 @@ int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int
     if (!later || !members[s]) continue;
     const uint64_t r0 = s * h, ld = quads(later);
     const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V), rows1 = r1 - (uint32_t)r0;
-    sigscreen_launch(st, dRepSig + (size_t)repAt[s] * (size_t)pitch, dRepLen + repAt[s], later, dSig, dMemLen, (uint32_t)r0, r1, pitch, size, -1, dMat, ld, shape);
+    sigscreen_launch(st, dRepSig + (size_t)repAt[s] * (size_t)pitch, dRepLen + repAt[s], later, dSig, dMemLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
     hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, later, (const uint32_t *)dRepId + repAt[s],
                        minShared, (const uint32_t *)dTable, minBits, dBest, dCell);
     HIP_TRY(hipGetLastError());
@@ -1861,10 +1888,23 @@ int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int
       if (!best[i]) { representative[i] = (int32_t)i; link[i] = ani_signeighbor_t{-1, 0, 0, 0.0f}; continue; }
       const int32_t rep = (int32_t)(0xffffffffu - (uint32_t)best[i]), sh = (int32_t)(cell[i] >> 16), sz = (int32_t)(cell[i] & 0xffffu);
       representative[i] = rep;
-      link[i] = ani_signeighbor_t{rep, sh, sz, sig_identity(sh, sz, kmerSize)};
+      link[i] = ani_signeighbor_t{rep, sh, sz, mode < 0 ? sig_identity(sh, sz, kmerSize) : sig_contain_identity(sh, sz, kmerSize)};
     }
   });
   return ANI_OK;
+}
+
+int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
+                      int32_t *representative, ani_signeighbor_t *link)
+{
+  return cluster_run(ctx, sig, len, nG, size, kmerSize, minShared, minIdentity, -1, representative, link);
+}
+
+// ---- the same under the containment estimate (ani_signature_cluster_contain) ----
+int signature_cluster_contain(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared,
+                              float minIdentity, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
+{
+  return cluster_run(ctx, sig, len, nG, size, kmerSize, minShared, minIdentity, mode, representative, link);
 }
 
 }  // namespace anih
@@ -2277,8 +2317,10 @@ void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t
   if (tileRefs) *tileRefs = ctx ? ctx->sigScreenTile[1] : 0;
 }
 
-int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                          float minIdentity, int32_t *representative, ani_signeighbor_t *link)
+// the two cluster calls: the checks of ani_signature_cluster's rules 6 - 8 and, with `contain`, of the mode, then the call; without
+// `contain` it is ani_signature_cluster and the mode plays no part
+static int cluster_entry(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                         float minIdentity, bool contain, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
 {
   if (!ctx) return fail(ANI_ERR_ARG, "null argument");
   if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
@@ -2286,6 +2328,9 @@ int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len,
   if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
   if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
   if (!(minIdentity > 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside (0, 100]", (double)minIdentity);
+  if (contain && (mode < ANI_CONTAIN_QUERY || mode > ANI_CONTAIN_MAX)) return fail(ANI_ERR_ARG, "containment mode %d outside [0, 2]", mode);
+  if (contain && mode != ANI_CONTAIN_MAX)
+    return fail(ANI_ERR_ARG, "containment mode %d: the greedy rule needs a symmetric estimate, ANI_CONTAIN_MAX", mode);
   if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the clustering takes at most 2^30", nGenomes);
   for (uint64_t &x : ctx->sigClusterStats) x = 0;
   if (nGenomes == 0) return ANI_OK;
@@ -2293,8 +2338,23 @@ int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len,
   for (int32_t g = 0; g < nGenomes; g++)
     if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
   HIP_TRY(hipSetDevice(ctx->device));
-  try { return signature_cluster(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, representative, link); }
+  try {
+    if (contain) return signature_cluster_contain(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, mode, representative, link);
+    return signature_cluster(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, representative, link);
+  }
   catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                          float minIdentity, int32_t *representative, ani_signeighbor_t *link)
+{
+  return cluster_entry(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, false, -1, representative, link);
+}
+
+int ani_signature_cluster_contain(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
+                                  float minIdentity, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
+{
+  return cluster_entry(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, true, mode, representative, link);
 }
 
 int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4])

@@ -374,7 +374,7 @@ struct ani_ctx {
   int sigGraphStrips = 0;                                                          // strips of the last ani_signature_graph
   int sigScreenStrips = 0;                                                         // strips of the last screen call (ani_signature_screen, ani_signature_screen_contain)
   int32_t sigScreenTile[2] = {0, 0};                                               // queries x references of the tile of its last strip
-  uint64_t sigClusterStats[4] = {0, 0, 0, 0};                                      // strips, representatives, cells merged, resolve steps of the last ani_signature_cluster
+  uint64_t sigClusterStats[4] = {0, 0, 0, 0};                                      // strips, representatives, cells walked, resolve steps of the last cluster call (ani_signature_cluster, ani_signature_cluster_contain)
   // minimizers per index chunk (env ANI_MAX_INDEX_MINIMIZERS); indices are 32 bit
   uint64_t maxIndexMinimizers = 1700000000ull;
   // (engine_map.hip checks them against kernels/l1.hpp)           // env ANI_TEST_L1_FILTER_MIN / ANI_TEST_L1_LDS_MAX, read by ani_init (tests: per engine, not

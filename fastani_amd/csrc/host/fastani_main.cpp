@@ -13,7 +13,8 @@
 // ani_signature_neighbors: any number of genomes), `--sketchScreen K` a .screen file (the K nearest references of every query under that
 // estimate, ani_signature_screen: the queries need not be references; with `--sketchContain query|reference|max` under the containment
 // estimate, ani_signature_screen_contain), `--sketchCluster T` a .sketchclusters file (greedy representative clustering under the
-// estimate, ani_signature_cluster: any number of genomes), `--sketchGraph T` a .sketchgraph file (the pairs at an estimate of at least
+// estimate, ani_signature_cluster: any number of genomes; with `--sketchContain max` under the containment estimate,
+// ani_signature_cluster_contain, for partial genomes), `--sketchGraph T` a .sketchgraph file (the pairs at an estimate of at least
 // T, ani_signature_graph: any number of genomes, with `--sketchContain max` under the containment estimate).  Sketch / Map / computeCGI run on the GPU(s)
 // through the C-ABI; this file is host-side text I/O and orchestration only.
 //
@@ -80,7 +81,7 @@ struct Options {
   int sketchSize = 1000; float sketchMinANI = 70.0f;   // --sketchSize, --sketchMinANI
   int sketchNeighbors = 0;                             // --sketchNeighbors K: the .neighbors file (0 = off)
   int sketchScreen = 0;                                // --sketchScreen K: the .screen file (0 = off)
-  int sketchContain = -1;                              // --sketchContain MODE: .screen under the containment estimate (an ani_contain_mode; -1 = off)
+  int sketchContain = -1;                              // --sketchContain MODE: .screen, .sketchgraph and .sketchclusters under the containment estimate (an ani_contain_mode; -1 = off)
   float sketchCluster = 0.0f;                          // --sketchCluster T: the .sketchclusters file, greedy clustering under the estimate at >= T (0 = off)
   float sketchGraph = 0.0f;                            // --sketchGraph T: the .sketchgraph file, the pairs at an estimate >= T, streamed (0 = off)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
@@ -146,11 +147,14 @@ struct Options {
     "     --sketchContain <value>  with --sketchScreen: the containment estimate instead, for inputs of unequal size or completeness.\n"
     "                 query: the share of the query's sketch found in the reference (partial genomes, plasmids, contigs); reference:\n"
     "                 the share of the reference's sketch found in the query (references inside a larger assembly); max: the larger\n"
-    "                 of the two.  The fourth column of .screen is then shared/denominator [disabled by default]\n"
+    "                 of the two.  The fourth column of .screen is then shared/denominator.  With --sketchGraph or --sketchCluster:\n"
+    "                 max only; it applies to each of the three that is given [disabled by default]\n"
     "     --sketchCluster <value>  also output greedy clusters of the genomes under that estimate at this threshold (0 < value <= 100):\n"
     "                 dereplication, one representative per group of near-identical genomes, every genome compared with the\n"
     "                 representatives only (.sketchclusters: genome, representative, estimate, shared/size; NA NA for a\n"
-    "                 representative); any number of genomes; the queries must be among the references [disabled by default]\n"
+    "                 representative); any number of genomes; the queries must be among the references; --sketchContain max: the\n"
+    "                 containment estimate, so that partial genomes join the genome they are parts of, the fourth column\n"
+    "                 shared/denominator [disabled by default]\n"
     "     --sketchGraph <value>  also output every pair of genomes at an estimate of at least this (0 < value <= 100), as --sketchANI\n"
     "                 prints it (.sketchgraph); any number of genomes; --sketchContain max: the containment estimate [disabled by default]\n"
     "     -o, --output <value>  output file name\n"
@@ -243,8 +247,10 @@ Options parse(int argc, char **argv)
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
   if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors && !o.sketchScreen) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
-  if (sketchContain && !o.sketchScreen && !(o.sketchGraph > 0.0f)) { std::cerr << "ERROR, --sketchContain needs --sketchScreen" << std::endl; exit(1); }
+  if (sketchContain && !o.sketchScreen && !(o.sketchGraph > 0.0f) && !(o.sketchCluster > 0.0f)) { std::cerr << "ERROR, --sketchContain needs --sketchScreen" << std::endl; exit(1); }
   if (o.sketchGraph > 0.0f && sketchContain && o.sketchContain != ANI_CONTAIN_MAX) { std::cerr << "ERROR, --sketchGraph takes --sketchContain max only" << std::endl;
+    exit(1); }
+  if (o.sketchCluster > 0.0f && sketchContain && o.sketchContain != ANI_CONTAIN_MAX) { std::cerr << "ERROR, --sketchCluster takes --sketchContain max only" << std::endl;
     exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
@@ -1637,14 +1643,19 @@ void write_neighbors(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixC
 // ---- --sketchCluster T: greedy representative clustering of the .matrix genomes under the sketch estimate at >= T
 // (ani_signature_cluster on the first device, minShared = 1: every genome against the representatives only, two records per genome come
 // off the device, and there is no genome ceiling).  .sketchclusters: genomes in .matrix order: genome, representative, estimate as .sketch
-// prints it, shared/size; a representative names itself and has NA in the last two columns.
+// prints it, shared/size; a representative names itself and has NA in the last two columns.  With --sketchContain max the call is
+// ani_signature_cluster_contain, the estimate the symmetric containment one and the last column shared/denominator.
 void write_sketch_clusters(const Options &o, ani_ctx *ctx, int kmerSize, const MatrixCells &mc)
 {
   const size_t n = mc.names.size();
   std::vector<uint32_t> sig; std::vector<int32_t> len;
   matrix_signatures(o, mc, sig, len);
   std::vector<int32_t> rep(n); std::vector<ani_signeighbor_t> link(n);
-  if (ani_signature_cluster(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchCluster, rep.data(), link.data())) die("ani_signature_cluster");
+  if (o.sketchContain >= 0) {
+    if (ani_signature_cluster_contain(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchCluster, o.sketchContain, rep.data(), link.data()))
+      die("ani_signature_cluster_contain");
+  }
+  else if (ani_signature_cluster(ctx, sig.data(), len.data(), (int32_t)n, g_sigs.size, kmerSize, 1, o.sketchCluster, rep.data(), link.data())) die("ani_signature_cluster");
   trace("sketch clusters found");
   BufferedFile f(o.out + ".sketchclusters");
   for (size_t g = 0; g < n; g++) {

@@ -16,6 +16,11 @@
 // identities, the smallest id (ani_abi.h, rule 3).  A maximum over a set, so no order of strips, tiles or lanes shows in it.  The slot
 // of a genome has one writer in every kernel (lane 0 of the row's workgroup in k_sigcluster_best, lane g mod 256 in
 // k_sigcluster_resolve), and kernels follow each other on one stream: no atomics.
+//
+// ani_signature_cluster_contain runs the same three kernels over other cells: shared << 16 | d of the containment
+// walk in mode MAX (sigcontain.hpp), with the host's table of that estimate.  The kernels read a cell through the table only, and
+// shared <= d <= size there as well, so nothing in them knows the estimate.  The strip's own block then comes from k_sigcontain_tri,
+// which writes both cells of a pair and 0 on the diagonal; k_sigcluster_resolve skips the diagonal either way.
 #pragma once
 #include "../../../include/ani_abi.h"
 #include "common.hpp"

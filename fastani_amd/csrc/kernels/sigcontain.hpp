@@ -6,6 +6,8 @@
 //   k_sigcontain_merge  one tile of TQ queries x TR references per workgroup, one walk per lane; cell (q - q0, r) of a (q1 - q0) x ld
 //                       strip, shared << 16 | d, d the denominator of the mode (ani_abi.h rules 2 - 4)
 //   (k_sigscreen_select of sigscreen.hpp, unchanged: shared <= d <= size, so the cell and the triangular table fit as they are)
+//   k_sigcontain_tri    the rows x rows block of a strip against itself in mode MAX, from its upper triangle alone: one walk per pair,
+//                       both cells written (ani_signature_cluster_contain)
 //
 // The walk.  Q and R ascend strictly; one step looks at the heads x = Q[pa], y = R[pb], the smaller advances, both on a tie, which is a
 // shared value.  Unlike sig_merge_rows there is no cap at `size` union elements: the walk ends when either row ends, after at most
@@ -108,6 +110,50 @@ static __global__ __launch_bounds__(TQ * TR >= kWave ? TQ * TR : kWave) void k_s
   if (kStageRefs) v = sig_contain_rows(tile + i * ldsPitch, tileLen[i], tile + (TQ + j) * ldsPitch, tileLen[TQ + j], size, mode);
   else v = sig_contain_stream(tile + i * ldsPitch, tileLen[i], (const uint4 *)(refSig + b * (uint32_t)pitch), refLen[b], size, mode);
   mat[(a - q0) * ld + b] = v;
+}
+
+// The h x h block of the rows [0, h) of sig against themselves in mode ANI_CONTAIN_MAX, where cell (i, j) equals cell (j, i): `shared` is
+// symmetric, and d = min(inQ, inR) with the roles swapped.  Only the tiles on or above the diagonal are launched, as a linear grid of
+// n (n + 1) / 2 workgroups, n = ceil(h / T): workgroup t is tile (ty <= tx) with t = tx (tx + 1) / 2 + ty, so tx is the largest integer
+// with tx (tx + 1) / 2 <= t (a float square root, then exact integer steps: 8 t + 1 < 2^24 for every h the callers have).  A tile right
+// of the diagonal stages 2 T rows and lane (i, j) walks its pair once; a tile on the diagonal stages its T rows once, and only the
+// lanes with j > i walk.  Either way the lane writes cell (a, b) and its mirror (b, a), the latter strided by ld.  The diagonal cells
+// are written as 0: k_sigcluster_resolve skips them, and no cell of the block is left as it was.  Rows at or beyond h have length 0 and
+// no cell.  WORDS >= 2 T (pitch + 4), as for the square tile of k_sigcontain_merge, whose LDS pitch this keeps.
+template <int T, int WORDS>
+static __global__ __launch_bounds__(T * T >= kWave ? T * T : kWave) void k_sigcontain_tri(const uint32_t *__restrict__ sig, const int32_t *__restrict__ len,
+    uint32_t h, int32_t pitch, int32_t size, uint32_t *__restrict__ mat, uint64_t ld)
+{
+  static_assert(2 * T * 4 <= kSigContainPad, "the pad holds 4 words per row");
+  __shared__ uint32_t tile[WORDS];
+  __shared__ int32_t tileLen[2 * T];
+  const uint32_t t = blockIdx.x;
+  uint32_t tx = (uint32_t)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while (tx * (tx + 1) / 2 > t) tx--;
+  while ((tx + 1) * (tx + 2) / 2 <= t) tx++;
+  const uint32_t ty = t - tx * (tx + 1) / 2;
+  const bool diag = ty == tx;
+  const uint32_t tid = threadIdx.x, nt = blockDim.x;
+  const uint32_t ldsPitch = (uint32_t)pitch + (((pitch >> 2) & 1) == 0 ? 4u : 0u);
+  const uint32_t quads = ldsPitch / 4;
+  const uint32_t rows = diag ? (uint32_t)T : 2u * T, colRow0 = diag ? 0u : (uint32_t)T;       // a diagonal tile's columns are its rows
+  uint4 *tile4 = (uint4 *)tile;
+  for (uint32_t r = 0; r < rows; r++) {
+    const uint32_t g = r < (uint32_t)T ? ty * T + r : tx * T + (r - T);
+    const int32_t l = g < h ? len[g] : 0;
+    if (tid == 0) tileLen[r] = l;
+    const uint4 *src = (const uint4 *)(sig + (uint64_t)g * (uint32_t)pitch);
+    for (uint32_t q = tid; q < ((uint32_t)l + 3) / 4; q += nt) tile4[r * quads + q] = src[q];
+  }
+  block_barrier();
+  if (tid >= (uint32_t)(T * T)) return;
+  const uint32_t i = tid / T, j = tid % T;
+  const uint64_t a = (uint64_t)ty * T + i, b = (uint64_t)tx * T + j;
+  if (a >= h || b >= h || b < a) return;               // (b < a: left of the diagonal in a diagonal tile, the mirror of a lane that walks)
+  if (a == b) { mat[a * ld + a] = 0u; return; }
+  const uint32_t v = sig_contain_rows(tile + i * ldsPitch, tileLen[i], tile + (colRow0 + j) * ldsPitch, tileLen[colRow0 + j], size, ANI_CONTAIN_MAX);
+  mat[a * ld + b] = v;
+  mat[b * ld + a] = v;
 }
 
 }  // namespace ani

@@ -577,7 +577,35 @@ int ani_signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int
 int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
                           int32_t minShared, float minIdentity,
                           int32_t *representative /* [nGenomes] */, ani_signeighbor_t *link /* [nGenomes] */);
-int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4]);   /* strips, representatives, cells merged, resolve steps of the last call */
+int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4]);   /* strips, representatives, cells walked, resolve steps of the last call */
+
+/* ---- greedy representative clustering under the containment estimate, streamed (no counterpart in the reference; DESIGN.md section
+ * 2.22).  ani_signature_cluster's estimate is a Jaccard index, which reads low for a genome that is partly there: a bin that holds half
+ * of a genome shares half of the genome's sketch, shared / size = 1 / 2, which reads 97.5 % at kmerSize 16 (96.5 % for a bin that holds
+ * 40 %), and becomes a representative of its own at a threshold of 99.  This call clusters by the share of the smaller genome
+ * instead, so that metagenome-assembled genomes of unequal completeness join the genome they are parts of.  The rules are
+ * ani_signature_cluster's with another pair.
+ * 1. The pair.  For a < b, Q is the signature of a and R the signature of b; shared, inQ, inR, d and identity are exactly rules 1 - 5 of
+ *    ani_signature_screen_contain, and so rule 2 of ani_signature_graph: shared over the whole of both lists, d = min(inQ, inR).
+ * 2. mode must be ANI_CONTAIN_MAX.  The greedy rule asks whether {a, b} is an edge, not whether a is in b, so it needs an estimate that
+ *    is symmetric in the two genomes; ANI_CONTAIN_QUERY and ANI_CONTAIN_REF are ANI_ERR_ARG with a message that says so, and so is
+ *    every value outside 0 .. 2.  The argument exists so that the signature stays if a directed rule is defined later.
+ * 3. Edges.  {a, b} is an edge iff shared >= minShared and bits(identity) >= bits(minIdentity).
+ * 4. The greedy rule, the outputs, the errors, the limits, the nGenomes == 0 case and the independence of schedule, reduction order,
+ *    strip height and tile shape are rules 3, 4 and 6 - 9 of ani_signature_cluster; minIdentity lies in (0, 100].  link[i] of a member
+ *    is {representative[i], shared, d, identity} of that pair.
+ * 5. Equivalence.  representative equals what ani_cluster_greedy returns over one row {refGenomeId = a, qryGenomeId = b, identity} per
+ *    record with shared >= minShared of ani_signature_graph(sig, len, nGenomes, size, kmerSize, minShared, 0, ANI_GRAPH_CONTAIN_MAX, 0,
+ *    nGenomes), at the same minIdentity, and link[i].identity equals its identityToRep[i] bit for bit for members.
+ * 6. Memory is rule 10 of ani_signature_cluster; ANI_TEST_SIG_STRIP_ROWS acts on this call too, and ANI_TEST_SIG_SCREEN_SHAPE on its
+ *    rectangular launches.  In mode MAX cell (a, b) equals cell (b, a), so a strip's own rows x rows block is made from its upper
+ *    triangle, one walk per pair.  ANI_TEST_SIG_CLUSTER_TRI = 0 (tests, tools/sketch_probe.py) walks the full block instead; the result
+ *    does not depend on it.
+ * ani_signature_cluster_stats reports the context's last call of either kind.  out[2] counts the cells a launch walked: rows x
+ * references of a rectangular launch, and rows (rows - 1) / 2, not rows^2, of a triangular launch over the rows of a strip. */
+int ani_signature_cluster_contain(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize,
+                                  int32_t minShared, float minIdentity, int32_t mode,
+                                  int32_t *representative /* [nGenomes] */, ani_signeighbor_t *link /* [nGenomes] */);
 
 /* ---- the pair graph of the genomes under either whole-genome sketch estimate, streamed (no counterpart in the reference; DESIGN.md
  * section 2.21).  The pair list of ani_signature_pairs, filtered on the device by an identity threshold and made a strip of rows at a

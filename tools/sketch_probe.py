@@ -31,6 +31,12 @@ clock around them includes uploads, kernels and read-back (for the pairs: the ho
                                                  resolve steps); up to --compose-max genomes the composition ani_signature_pairs at
                                                  minShared 1 + ani_cluster_greedy over its rows on the same signatures, timed the same
                                                  way and compared with the call's result
+    python tools/sketch_probe.py --cluster T --contain max
+                                                 ani_signature_cluster_contain on the same genomes: the call,
+                                                 the same call with ANI_TEST_SIG_CLUSTER_TRI=0 (every strip's own block walked in
+                                                 full instead of from its upper triangle) and ani_signature_cluster under the Mash
+                                                 estimate, taken in turns; min .. max and median of each by HIP events and by the wall
+                                                 clock, the stats call of each, and the results of the first two compared
     python tools/sketch_probe.py --graph T [--contain max]
                                                  ani_signature_graph at the threshold T, at 10 000 and 90 000
                                                  genomes in families of ten, minShared 1, all rows in one call, under the Mash estimate
@@ -324,6 +330,60 @@ def cluster(e, a):
               % (n, SIZE, a.cluster, span(cdev), float(np.median(cdev)) * 1e3, span(cwall), old["rows"], min(dev) / max(cdev), max(dev) / min(cdev)), flush=True)
 
 
+def cluster_contain(e, a):
+    """ani_signature_cluster_contain beside itself without the triangular block and beside ani_signature_cluster: the genomes of
+    cluster(), the three calls in turns so that a drift of the machine meets all of them"""
+    rng = np.random.default_rng(1)
+    tri_env = "ANI_TEST_SIG_CLUSTER_TRI"
+    calls = (("contain", None, lambda sig, length: e.signature_cluster_contain(sig, length, 16, a.cluster, a.contain)),
+             ("contain, full blocks", "0", lambda sig, length: e.signature_cluster_contain(sig, length, 16, a.cluster, a.contain)),
+             ("mash", None, lambda sig, length: e.signature_cluster(sig, length, 16, a.cluster)))
+    for n in (10000, 90000):
+        if a.only and n != a.only:
+            continue
+        sig, length = family_signatures(rng, n)
+        wall, dev, got, stats = ({name: [] for name, _, _ in calls} for _ in range(4))
+        for turn in range(a.reps + 1):                                 # (the first turn warms up)
+            for name, tri, fn in calls:
+                os.environ.pop(tri_env, None)
+                if tri is not None:
+                    os.environ[tri_env] = tri
+                w, d = timed_once(lambda: got.__setitem__(name, fn(sig, length)))
+                stats[name] = e.signature_cluster_stats()
+                if turn:
+                    wall[name] += w
+                    dev[name] += d
+        os.environ.pop(tri_env, None)
+        for i in (0, 1):
+            assert np.array_equal(got["contain"][i], got["contain, full blocks"][i])
+        for name, _, _ in calls:
+            rep, link = got[name]
+            own = rep == np.arange(n)
+            strips, reps, cells, steps = stats[name]
+            assert reps == int(own.sum())
+            print("cluster    n=%6d s=%d T=%g %-20s: HIP events %s median %.3f ms   wall %s median %.3f ms   %d strips, %d representatives, %.3e cells walked, "
+                  "%d resolve steps   %d members joined a later representative"
+                  % (n, SIZE, a.cluster, name, span(dev[name]), float(np.median(dev[name])) * 1e3, span(wall[name]), float(np.median(wall[name])) * 1e3, strips, reps,
+                     cells, steps, int((rep > np.arange(n)).sum())), flush=True)
+        m = {name: float(np.median(dev[name])) for name, _, _ in calls}
+        print("           n=%6d: results of the two containment calls identical; by the medians of the HIP events, contain / contain with full blocks %.3f, "
+              "contain / mash %.3f" % (n, m["contain"] / m["contain, full blocks"], m["contain"] / m["mash"]), flush=True)
+
+
+def timed_once(fn):
+    """one call of timed_events without its warm-up"""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    t0 = time.perf_counter()
+    fn()
+    wall = time.perf_counter() - t0
+    e1.record()
+    e1.synchronize()
+    return [wall], [e0.elapsed_time(e1) / 1e3]
+
+
 def graph(e, a):
     rng = np.random.default_rng(1)
     estimate = "contain" if a.contain else "mash"
@@ -368,13 +428,15 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--compose-max", type=int, default=10000)
     a = ap.parse_args()
-    if a.contain and not a.screen and not a.graph:
-        ap.error("--contain needs --screen or --graph")
+    if a.contain and not a.screen and not a.graph and not a.cluster:
+        ap.error("--contain needs --screen, --graph or --cluster")
     if a.graph and a.contain not in (None, "max"):
         ap.error("--graph takes --contain max only")
+    if a.cluster and a.contain not in (None, "max"):
+        ap.error("--cluster takes --contain max only")
     if a.neighbors or a.screen or a.cluster or a.graph:
         import fastani_amd
-        (graph if a.graph else cluster if a.cluster else neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
+        (graph if a.graph else cluster_contain if a.cluster and a.contain else cluster if a.cluster else neighbors if a.neighbors else contain if a.contain else screen)(fastani_amd.engine(0), a)
         return
     import torch
     import fastani_amd
