@@ -1986,12 +1986,13 @@ int ani_map_query(ani_ctx *ctx, const ani_sketch *skc, const ani_seq_batch_t *qu
   return to_host_malloc(maps, out, n);
 }
 
-int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *mappings, size_t n, uint64_t totalQueryFragments, int32_t queryFileNo,
-                    ani_cgi_t **out, size_t *m)
+// The reducer over a foreign mapping list: ani_compute_cgi (one query genome, queryFragStart == nullptr) and the test entry point
+// ani_reduce_check (nQuery query genomes in one table: the mappings of query q are those with querySeqId in [queryFragStart[q],
+// queryFragStart[q + 1]), and its fragments carry fragGenome = fs.genomeBase + q).  fs.genomeFragments and fs.genomeBase are the
+// caller's.  The rows keep the sketch's own reference ids, whatever ani_sketch_set_ref_id_base says.
+static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t *mappings, size_t n, const int32_t *queryFragStart, int32_t nQuery,
+                               FragSet &fs, int32_t firstQueryId, RowBuf *rows)
 {
-  if (!ctx || !skc || !out || !m || (n && !mappings)) return fail(ANI_ERR_ARG, "null argument");
-  ani_sketch *sk = const_cast<ani_sketch *>(skc);
-  HIP_TRY(hipSetDevice(ctx->device));
   if (n > 0x7ffffff0ull) return fail(ANI_ERR_LIMIT, "too many mappings");
   // The device reducer expects the mappings of one (fragment, reference genome) next to each other, which is how Map reports
   // them (fragment, then reference position); only input that is not in that order is sorted (on the device, by
@@ -2001,8 +2002,11 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *ma
     const ani_mapping_t &a = mappings[i];
     if (a.refSeqId < 0 || a.refSeqId >= sk->nContigs) return fail(ANI_ERR_ARG, "mapping %zu refers to contig %d outside the sketch", i, a.refSeqId);
     if (a.refStartPos < 0 || a.refStartPos > sk->contigLen[a.refSeqId]) return fail(ANI_ERR_ARG, "mapping %zu has refStartPos outside its contig", i);
-    if (a.nucIdentity <= 0.0f) return fail(ANI_ERR_ARG, "mapping %zu has non-positive identity", i);
+    // the identity bits go through an unsigned atomicMax and a float sum: (0, 100] only, written so that NaN fails
+    if (!(a.nucIdentity > 0.0f && a.nucIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "mapping %zu has an identity outside (0, 100]", i);
     if (a.querySeqId < 0) return fail(ANI_ERR_ARG, "mapping %zu has a negative querySeqId", i);
+    if (queryFragStart && a.querySeqId >= queryFragStart[nQuery]) return fail(ANI_ERR_ARG, "mapping %zu has querySeqId %d outside the %d fragments of the queries",
+        i, a.querySeqId, queryFragStart[nQuery]);
     if (i && (mappings[i - 1].querySeqId > a.querySeqId || (mappings[i - 1].querySeqId == a.querySeqId
         && mappings[i - 1].refSeqId > a.refSeqId))) ordered = false;
   }
@@ -2024,15 +2028,19 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *ma
     HIP_TRY(hipMemcpyAsync(ord.data(), ctx->keepOff.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-  // compress querySeqId -> dense fragment index (all of one genome); split the candidate list by index chunk
-  FragSet fs; fs.genomeFragments.assign(1, (int32_t)totalQueryFragments);
+  // compress querySeqId -> dense fragment index (ascending, so the fragments of a query are consecutive); split the candidate list by
+  // index chunk
   const size_t nCh = sk->chunks.size();
   std::vector<std::vector<int32_t>> cFrag(nCh), cSeq(nCh), cStart(nCh); std::vector<std::vector<uint32_t>> cBits(nCh);
-  int32_t lastQ = -1, f = -1;
+  std::vector<int32_t> fragQ;                        // several queries: fragment -> fs.genomeBase + its query
+  int32_t lastQ = -1, f = -1, q = 0;
   size_t chunkOfSeqHint = 0;
   for (size_t i = 0; i < n; i++) {
     const ani_mapping_t &a = mappings[ordered ? i : ord[i]];
-    if (a.querySeqId != lastQ || f < 0) { f++; lastQ = a.querySeqId; }
+    if (a.querySeqId != lastQ || f < 0) {
+      f++; lastQ = a.querySeqId;
+      if (queryFragStart) { while (a.querySeqId >= queryFragStart[q + 1]) q++; fragQ.push_back(fs.genomeBase + q); }
+    }
     size_t c = chunkOfSeqHint;
     while (c + 1 < nCh && a.refSeqId >= sk->chunks[c]->c0 + sk->chunks[c]->nContigs) c++;
     while (c > 0 && a.refSeqId < sk->chunks[c]->c0) c--;
@@ -2043,8 +2051,11 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *ma
   fs.nFrag = f + 1;
   const size_t nF = (size_t)(f + 1);
   TRY(ctx->fragGenome.ensure((nF ? nF : 1) * 4));
-  if (nF) HIP_TRY(hipMemsetAsync(ctx->fragGenome.p, 0, nF * 4, ctx->stream));
-  fs.fragGenome = ctx->fragGenome.as<int32_t>(); fs.genomeBase = 0;
+  if (nF && queryFragStart) {
+    HIP_TRY(hipMemcpyAsync(ctx->fragGenome.p, fragQ.data(), nF * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  } else if (nF) HIP_TRY(hipMemsetAsync(ctx->fragGenome.p, 0, nF * 4, ctx->stream));
+  fs.fragGenome = ctx->fragGenome.as<int32_t>();
   for (size_t c = 0; c < nCh; c++) {
     const size_t nc = cFrag[c].size();
     if (nc) {
@@ -2054,11 +2065,52 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *ma
       HIP_TRY(hipMemcpyAsync(ctx->refStart.p, cStart[c].data(), nc * 4, hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(hipMemcpyAsync(ctx->idBits.p, cBits[c].data(), nc * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-    TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, 1));
+    TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
+  const size_t m0 = rows->n;
+  TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
+  if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
+  return ANI_OK;
+}
+
+int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *mappings, size_t n, uint64_t totalQueryFragments, int32_t queryFileNo,
+                    ani_cgi_t **out, size_t *m)
+{
+  if (!ctx || !skc || !out || !m || (n && !mappings)) return fail(ANI_ERR_ARG, "null argument");
+  ani_sketch *sk = const_cast<ani_sketch *>(skc);
+  HIP_TRY(hipSetDevice(ctx->device));
+  FragSet fs; fs.genomeFragments.assign(1, (int32_t)totalQueryFragments); fs.genomeBase = 0;
   RowBuf rows;
-  TRY(collect_rows(ctx, sk, fs, 1, queryFileNo, &rows));
+  TRY(reduce_mapping_list(ctx, sk, mappings, n, nullptr, 1, fs, queryFileNo, &rows));
+  *m = rows.n; *out = rows.release();
+  if (!*out) return fail(ANI_ERR_NOMEM, "host allocation failed");
+  return ANI_OK;
+}
+
+// TEST INFRASTRUCTURE (declared in host/engine.hpp, not part of include/ani_abi.h, no product code calls it): the reducer in the shape
+// the fused path gives it - several query genomes in one bin table, fragGenome values above a non-zero FragSet::genomeBase, the
+// pair grid's partial last block - over a synthetic mapping list.  The mappings of query q are those with querySeqId in
+// [queryFragStart[q], queryFragStart[q + 1]); the result is the concatenation over q of ani_compute_cgi(mappings of q,
+// totalQueryFragments = queryFragStart[q + 1] - queryFragStart[q], queryFileNo = firstQueryId + q).  One reduce_stage per index chunk
+// with nQuery and one collect_rows, as map_fragset runs them.  Validates like ani_compute_cgi; a querySeqId outside
+// [0, queryFragStart[nQuery]) is ANI_ERR_ARG too.  tests/test_reducer.py holds it to the oracle.
+int ani_reduce_check(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *mappings, size_t n, const int32_t *queryFragStart, int32_t nQuery,
+                     int32_t genomeBase, int32_t firstQueryId, ani_cgi_t **out, size_t *m)
+{
+  if (!ctx || !skc || !out || !m || !queryFragStart || (n && !mappings)) return fail(ANI_ERR_ARG, "null argument");
+  if (nQuery < 0 || nQuery > 65536) return fail(ANI_ERR_ARG, "ani_reduce_check: %d queries", nQuery);
+  if (genomeBase < 0 || genomeBase > 0x7fffffff - nQuery) return fail(ANI_ERR_ARG, "ani_reduce_check: genomeBase %d", genomeBase);
+  if (queryFragStart[0] != 0) return fail(ANI_ERR_ARG, "ani_reduce_check: queryFragStart[0] is not 0");
+  ani_sketch *sk = const_cast<ani_sketch *>(skc);
+  HIP_TRY(hipSetDevice(ctx->device));
+  FragSet fs; fs.genomeBase = genomeBase;
+  for (int32_t q = 0; q < nQuery; q++) {
+    if (queryFragStart[q + 1] < queryFragStart[q]) return fail(ANI_ERR_ARG, "ani_reduce_check: queryFragStart is not ascending at %d", q);
+    fs.genomeFragments.push_back(queryFragStart[q + 1] - queryFragStart[q]);
+  }
+  RowBuf rows;
+  TRY(reduce_mapping_list(ctx, sk, mappings, n, queryFragStart, nQuery, fs, firstQueryId, &rows));
   *m = rows.n; *out = rows.release();
   if (!*out) return fail(ANI_ERR_NOMEM, "host allocation failed");
   return ANI_OK;

@@ -58,6 +58,14 @@ extern "C" int ani_sort_check(void *tmp, hipStream_t stream);
 struct ani_ctx;
 extern "C" int ani_prim_check(int op, const void *in, void *out, const int32_t *sizes, int blocks, int cap, int threads, hipStream_t stream);
 extern "C" int ani_prim_device_scan(ani_ctx *ctx, const int32_t *in, uint32_t *out, uint32_t n, uint64_t *total, uint64_t limit);
+// TEST INFRASTRUCTURE (engine_map.hip, beside ani_compute_cgi, whose front half it shares; not part of include/ani_abi.h, no product
+// code calls it): the reducer's own reduce_stage / collect_rows over a synthetic mapping list in the shape of the fused path — nQuery
+// query genomes in one bin table (query q owns the querySeqIds [queryFragStart[q], queryFragStart[q + 1]), queryFragStart[0] = 0),
+// fragGenome = genomeBase + q with FragSet::genomeBase = genomeBase.  Result: the rows of ani_compute_cgi(mappings of q,
+// queryFragStart[q + 1] - queryFragStart[q], firstQueryId + q) for q = 0 .. nQuery - 1, one after the other.  tests/test_reducer.py
+// holds it to the oracle.
+extern "C" int ani_reduce_check(ani_ctx *ctx, const ani_sketch *sk, const ani_mapping_t *mappings, size_t n, const int32_t *queryFragStart,
+                                int32_t nQuery, int32_t genomeBase, int32_t firstQueryId, ani_cgi_t **out, size_t *m);
 
 namespace ani { struct TableSlot; }
 

@@ -300,7 +300,16 @@ int ani_fragset_unpack(ani_ctx *ctx, const void *devBuf, size_t bytes, ani_frags
 int ani_fragset_unpack_merged(ani_ctx *ctx, const void *devBuf, size_t slotBytes, int32_t nSlots, const int32_t *slotQueryBase,
                               ani_fragset **out);
 
-/* ---- reducer: replaces cgi::computeCGI (computeCoreIdentity.hpp:166-298) for one query genome ---- */
+/* ---- reducer: replaces cgi::computeCGI (computeCoreIdentity.hpp:166-298) for one query genome ----
+ * The mappings may come in any order (a list that is not ordered by (querySeqId, refSeqId) is sorted on the device); querySeqId values
+ * need not be dense.  Rows: refGenomeId ascending, the sketch's own ids (ani_sketch_set_ref_id_base does not apply), qryGenomeId =
+ * queryFileNo, totalQueryFragments as given; n = 0 gives no rows.  ANI_ERR_ARG, with nothing reduced, for a mapping with
+ *   - refSeqId outside [0, contigs of the sketch),
+ *   - refStartPos outside [0, length of that contig] (the length itself is accepted: it falls into the contig's last bin),
+ *   - nucIdentity outside (0, 100]: zero, -0.0, negative, above 100, +inf or NaN (the reducer orders identities by their bit
+ *     patterns and sums them, so a NaN would displace every valid identity of its bin and poison the row),
+ *   - a negative querySeqId;
+ * ANI_ERR_LIMIT for 2^31 - 16 mappings or more. */
 int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *sk, const ani_mapping_t *mappings, size_t n,
                     uint64_t totalQueryFragments, int32_t queryFileNo, ani_cgi_t **out, size_t *m);
 
