@@ -41,6 +41,7 @@ CGI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("countSeq", 
                    ("totalQueryFragments", "<i4"), ("identity", "<f4")])
 SIGPAIR_DT = np.dtype([("a", "<i4"), ("b", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
 NEIGHBOR_DT = np.dtype([("neighbor", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
+BINPROFILE_DT = np.dtype([("count", "<u4"), ("minIdentity", "<f4"), ("maxIdentity", "<f4"), ("reserved", "<u4"), ("sum", "<u8")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -134,6 +135,10 @@ def _bind(lib):
         "ani_sketch_residency": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "ani_sketch_set_ref_id_base": (C.c_int, [vp, C.c_int32]),
         "ani_map_cgi_batch": (C.c_int, [vp, vp, C.POINTER(SeqBatch), C.c_int32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_profile_begin": (C.c_int, [vp, C.c_float, C.c_int32]),
+        "ani_sketch_profile_bins": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "ani_sketch_profile_read": (C.c_int, [vp, vp, vp]),
+        "ani_sketch_profile_end": (C.c_int, [vp]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
@@ -906,6 +911,37 @@ class Sketch:
     def set_ref_id_base(self, base):
         """this sketch is a shard / block of a larger set: CGI rows of the batch entry points report refGenomeId + base"""
         self.e._chk(self.e.lib.ani_sketch_set_ref_id_base(self.h, int(base)))
+
+    def profile_begin(self, min_identity=0.0, min_fragments=1):
+        """start (or reset) the per-bin conservation profile: every mapping call that reduces against this sketch adds its query genomes
+        whose row has countSeq >= min_fragments and identity >= min_identity (ani_sketch_profile_begin)"""
+        self.e._chk(self.e.lib.ani_sketch_profile_begin(self.h, float(min_identity), int(min_fragments)))
+
+    def profile_bins(self):
+        n = C.c_uint64()
+        self.e._chk(self.e.lib.ani_sketch_profile_bins(self.h, C.byref(n)))
+        return n.value
+
+    def profile_read(self):
+        """-> (bins BINPROFILE_DT[nBins] in set-global bin order, queries uint32[nGenomes]); does not reset"""
+        bins = np.zeros(self.profile_bins(), dtype=BINPROFILE_DT)
+        queries = np.zeros(self._counts()[1], dtype=np.uint32)
+        self.e._chk(self.e.lib.ani_sketch_profile_read(self.h, bins.ctypes.data if len(bins) else None, queries.ctypes.data if len(queries) else None))
+        return bins, queries
+
+    def profile_end(self):
+        self.e._chk(self.e.lib.ani_sketch_profile_end(self.h))
+
+    def profile_layout(self):
+        """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and
+        genome; contig c has contigLen[c] // (fragLen - 20) + 1 bins"""
+        n_contigs, n_genomes = self._counts()
+        a, b = C.c_void_p(), C.c_void_p()
+        self.e._chk(self.e.lib.ani_sketch_tables(self.h, C.byref(a), C.byref(b)))
+        clen = np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_int32)), (n_contigs,)).astype(np.int64) if n_contigs else np.zeros(0, dtype=np.int64)
+        gcs = np.ctypeslib.as_array(C.cast(b, C.POINTER(C.c_int32)), (n_genomes + 1,)).astype(np.int64)
+        contig_bin_start = np.concatenate([[0], np.cumsum(clen // (self.params.fragLen - 20) + 1)]).astype(np.int64)
+        return contig_bin_start, contig_bin_start[gcs]
 
     def residency(self):
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()

@@ -16,10 +16,17 @@ void free_chunk_index(IndexChunk *ch)
   for (void **q : ptrs) if (*q) { pool_free(*q); *q = nullptr; }
   ch->resident = false; ch->nDup = 0;
 }
+// the accumulators of the conservation profile (ani_sketch_profile_begin)
+void free_chunk_profile(IndexChunk *ch)
+{
+  void **ptrs[] = {(void **)&ch->profCount, (void **)&ch->profMin, (void **)&ch->profMax, (void **)&ch->profQueries, (void **)&ch->profSum};
+  for (void **q : ptrs) if (*q) { pool_free(*q); *q = nullptr; }
+}
 void free_chunk(IndexChunk *ch)
 {
   if (!ch) return;
   free_chunk_index(ch);
+  free_chunk_profile(ch);
   void *ptrs[] = {ch->contigGenome, ch->contigBinBase, ch->genomeBinStart, ch->posBase};
   for (void *q : ptrs) if (q) pool_free(q);
   delete ch;

@@ -13,6 +13,7 @@
 #include "kernels/l1.hpp"
 #include "kernels/l2.hpp"
 #include "kernels/reduce.hpp"
+#include "kernels/profile.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
 #include "kernels/nj.hpp"
@@ -451,6 +452,17 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
   pa.outStride = compact ? sk->nGenomes : set->nGenomes; pa.outCol0 = compact ? 0 : sk->g0;
   const size_t nPairs = (size_t)nQuery * (size_t)sk->nGenomes;
   hipLaunchKernelGGL(k_pair_reduce, dim3((unsigned)((nPairs + 3) / 4)), dim3(256), 0, ctx->stream, pa);   // one wave per pair
+  if (set->profile) {
+    // the conservation profile (kernels/profile.hpp): the bin table and the pair table are both complete here and gone with the next
+    // sub-batch; reduce_stage runs once per (sub-batch, index chunk), so every pair is added once
+    ProfileArgs fa;
+    fa.nQuery = nQuery; fa.nRefGenomes = sk->nGenomes; fa.bins = pa.bins; fa.binsPerQuery = binsPerQuery; fa.genomeBinStart = sk->genomeBinStart;
+    fa.pairCount = pa.pairCount; fa.pairIdentity = pa.pairIdentity; fa.outStride = pa.outStride; fa.outCol0 = pa.outCol0;
+    fa.minIdBits = set->profMinIdBits; fa.minFragments = set->profMinFragments;
+    fa.count = sk->profCount; fa.minBits = sk->profMin; fa.maxBits = sk->profMax; fa.sum = sk->profSum; fa.queries = sk->profQueries;
+    if (binsPerQuery) hipLaunchKernelGGL(k_profile_bins, dim3(grid_for(binsPerQuery, kTPB)), dim3(kTPB), 0, ctx->stream, fa);
+    hipLaunchKernelGGL(k_profile_queries, dim3(grid_for((size_t)sk->nGenomes, kTPB)), dim3(kTPB), 0, ctx->stream, fa);
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -2160,6 +2172,109 @@ int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *skc, const ani_seq_batch_t
   return ANI_OK;
 }
 
+// ---- conservation profile (ani_abi.h: ani_sketch_profile_begin) ----
+// rule 1: the set-global first bin of every contig, from the contig lengths and fragLen alone
+static std::vector<uint64_t> profile_bin_start(const ani_sketch *sk)
+{
+  const int32_t binW = sk->params.fragLen - 20;
+  std::vector<uint64_t> start((size_t)sk->nContigs + 1, 0);
+  for (int32_t c = 0; c < sk->nContigs; c++) start[(size_t)c + 1] = start[c] + (uint64_t)(sk->contigLen[c] / binW) + 1;
+  return start;
+}
+
+int ani_sketch_profile_begin(ani_sketch *sk, float minIdentity, int32_t minFragments)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  ani_ctx *ctx = sk->ctx;
+  HIP_TRY(hipSetDevice(sk->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  sk->profile = false;
+  auto bail = [&](hipError_t e, const char *what) {
+    for (IndexChunk *ch : sk->chunks) free_chunk_profile(ch);
+    return fail(e == hipErrorOutOfMemory ? ANI_ERR_NOMEM : ANI_ERR_DEVICE, "profile accumulators: %s failed: %s", what, hipGetErrorString(e));
+  };
+  for (IndexChunk *ch : sk->chunks) {
+    free_chunk_profile(ch);
+    const size_t nb = ch->totalBins ? ch->totalBins : 1, ng = ch->nGenomes > 0 ? (size_t)ch->nGenomes : 1;
+    hipError_t e;
+    if ((e = pool_malloc((void **)&ch->profCount, nb * 4)) != hipSuccess || (e = pool_malloc((void **)&ch->profMin, nb * 4)) != hipSuccess
+        || (e = pool_malloc((void **)&ch->profMax, nb * 4)) != hipSuccess || (e = pool_malloc((void **)&ch->profSum, nb * 8)) != hipSuccess
+        || (e = pool_malloc((void **)&ch->profQueries, ng * 4)) != hipSuccess) return bail(e, "allocation");
+    if ((e = hipMemsetAsync(ch->profCount, 0, nb * 4, ctx->stream)) != hipSuccess || (e = hipMemsetAsync(ch->profMin, 0xff, nb * 4, ctx->stream)) != hipSuccess
+        || (e = hipMemsetAsync(ch->profMax, 0, nb * 4, ctx->stream)) != hipSuccess || (e = hipMemsetAsync(ch->profSum, 0, nb * 8, ctx->stream)) != hipSuccess
+        || (e = hipMemsetAsync(ch->profQueries, 0, ng * 4, ctx->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+  }
+  { const hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) return bail(e, "hipStreamSynchronize"); }
+  memcpy(&sk->profMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->profMinIdBits = 0;                 // -0.0 counts as 0
+  sk->profMinFragments = (uint32_t)minFragments;
+  sk->profile = true;
+  return ANI_OK;
+}
+
+int ani_sketch_profile_bins(const ani_sketch *sk, uint64_t *nBins)
+{
+  if (!sk || !nBins) return fail(ANI_ERR_ARG, "null argument");
+  *nBins = profile_bin_start(sk).back();
+  return ANI_OK;
+}
+
+int ani_sketch_profile_read(const ani_sketch *sk, ani_binprofile_t *bins, uint32_t *queries)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->profile) return fail(ANI_ERR_ARG, "ani_sketch_profile_read without ani_sketch_profile_begin");
+  ani_ctx *ctx = sk->ctx;
+  HIP_TRY(hipSetDevice(sk->device));
+  const std::vector<uint64_t> binStart = profile_bin_start(sk);
+  bool full = false;
+  constexpr size_t kPiece = (size_t)1 << 20;                    // bins per staged piece: 20 MB page-locked
+  for (const IndexChunk *ch : sk->chunks) {
+    if (queries && ch->nGenomes > 0) {
+      uint32_t *host = nullptr;
+      TRY(pinned_buffer(ctx, 1, (size_t)ch->nGenomes * 4, (void **)&host));
+      HIP_TRY(hipMemcpyAsync(host, ch->profQueries, (size_t)ch->nGenomes * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      for (int32_t g = 0; g < ch->nGenomes; g++) { queries[ch->g0 + g] = host[g]; full |= host[g] == kProfileFull; }
+    }
+    ani_binprofile_t *out = bins ? bins + binStart[ch->c0] : nullptr;
+    for (size_t b0 = 0; b0 < ch->totalBins; b0 += kPiece) {
+      const size_t n = std::min<size_t>(kPiece, ch->totalBins - b0);
+      uint8_t *host = nullptr;
+      TRY(pinned_buffer(ctx, 1, n * 20, (void **)&host));
+      const uint32_t *hc = (const uint32_t *)(host + n * 8), *hmn = hc + n, *hmx = hmn + n; const unsigned long long *hs = (const unsigned long long *)host;
+      HIP_TRY(hipMemcpyAsync(host, ch->profSum + b0, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(host + n * 8, ch->profCount + b0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (bins) {
+        HIP_TRY(hipMemcpyAsync(host + n * 12, ch->profMin + b0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(host + n * 16, ch->profMax + b0, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      for (size_t i = 0; i < n; i++) {
+        full |= hc[i] == kProfileFull;
+        if (!out) continue;
+        ani_binprofile_t r; r.count = hc[i]; r.reserved = 0; r.sum = hs[i];
+        const uint32_t mn = hc[i] ? hmn[i] : 0u, mx = hc[i] ? hmx[i] : 0u;      // the `min` of an empty bin is the sentinel on the device
+        memcpy(&r.minIdentity, &mn, 4); memcpy(&r.maxIdentity, &mx, 4);
+        out[b0 + i] = r;
+      }
+    }
+  }
+  if (full) return fail(ANI_ERR_LIMIT, "a counter of the profile has reached 2^32 - 1");
+  return ANI_OK;
+}
+
+int ani_sketch_profile_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->profile) return fail(ANI_ERR_ARG, "ani_sketch_profile_end without ani_sketch_profile_begin");
+  HIP_TRY(hipSetDevice(sk->device));
+  HIP_TRY(hipStreamSynchronize(sk->ctx->stream));        // a reduce_stage of an earlier call may still be adding
+  for (IndexChunk *ch : sk->chunks) free_chunk_profile(ch);
+  sk->profile = false;
+  return ANI_OK;
+}
 
 int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float minIdentity, int32_t *representative, float *identityToRep)
 {

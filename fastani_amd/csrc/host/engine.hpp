@@ -464,6 +464,9 @@ struct IndexChunk {
   uint32_t *contigBinBase = nullptr, *genomeBinStart = nullptr, *posBase = nullptr, *posSample = nullptr;
   uint32_t totalBins = 0, totalPosBins = 0;
   int32_t maxContigLen = 0;
+  // accumulators of the conservation profile (ani_sketch_profile_begin; kernels/profile.hpp): per bin of the chunk 20 bytes, per genome 4.
+  // Small tables like the reducer's: they survive free_chunk_index, so a streamed set keeps them while its index arrays come and go.
+  uint32_t *profCount = nullptr, *profMin = nullptr, *profMax = nullptr, *profQueries = nullptr; unsigned long long *profSum = nullptr;
 };
 
 struct ani_sketch {
@@ -489,6 +492,8 @@ struct ani_sketch {
   // LUTs
   ani::stat::Luts *luts = nullptr;        // host LUTs, shared by every sketch of the context with the same (k, identity cutoff)
   int32_t *dMinHits = nullptr, *dMinShared = nullptr; uint32_t *dIdLUT = nullptr; int dLutMaxS = 0;
+  // conservation profile (ani_sketch_profile_begin .. _end): reduce_stage adds every sub-batch to the chunks' accumulators while it is on
+  bool profile = false; uint32_t profMinIdBits = 0, profMinFragments = 1;
 };
 
 namespace anih {
@@ -635,6 +640,7 @@ int sketch_records(ani_ctx *ctx, const ani_params_t *p, const DeviceBatch &db, i
 int fragment_stage(ani_ctx *ctx, const ani_params_t &p, const DeviceBatch &db, FragSet *qr);
 // ---- engine_index.hip ----
 void free_chunk_index(IndexChunk *ch);
+void free_chunk_profile(IndexChunk *ch);
 void free_chunk(IndexChunk *ch);
 void free_sketch_device(ani_sketch *sk);
 int upload_luts(ani_sketch *sk, int maxS);

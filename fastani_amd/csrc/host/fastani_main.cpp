@@ -84,6 +84,8 @@ struct Options {
   int sketchContain = -1;                              // --sketchContain MODE: .screen, .sketchgraph and .sketchclusters under the containment estimate (an ani_contain_mode; -1 = off)
   float sketchCluster = 0.0f;                          // --sketchCluster T: the .sketchclusters file, greedy clustering under the estimate at >= T (0 = off)
   float sketchGraph = 0.0f;                            // --sketchGraph T: the .sketchgraph file, the pairs at an estimate >= T, streamed (0 = off)
+  bool profile = false;                                // --profile: the .profile file, per-bin conservation of every reference over the queries
+  float profileMinANI = 95.0f; int profileMinFragments = 50;   // --profileMinANI, --profileMinFragments: the pairs that count (ani_sketch_profile_begin's gate)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
@@ -107,7 +109,7 @@ struct Options {
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
-    "             [--sketchGraph <value>]\n"
+    "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -157,6 +159,14 @@ struct Options {
     "                 shared/denominator [disabled by default]\n"
     "     --sketchGraph <value>  also output every pair of genomes at an estimate of at least this (0 < value <= 100), as --sketchANI\n"
     "                 prints it (.sketchgraph); any number of genomes; --sketchContain max: the containment estimate [disabled by default]\n"
+    "     --profile   also output, for every reference genome, the conservation of each of its bins of fragLen - 20 bases over the query\n"
+    "                 genomes that match it (.profile: reference, contig (1-based ordinal in its file), start, end (0-based, half open),\n"
+    "                 queries (the query genomes that count for this reference), covered (those of them with a fragment whose best\n"
+    "                 reciprocal hit lies in the bin), mean, min, max of their identities there, NA where covered is 0).  The bins with\n"
+    "                 covered near queries are the core genome, the others islands.  In an all-vs-all run a genome is one of its own\n"
+    "                 queries.  Works with every input mode [disabled by default]\n"
+    "     --profileMinANI <value>  a query genome counts for a reference from this ANI on (0 < value <= 100) [default : 95]\n"
+    "     --profileMinFragments <value>  ... and from this many matched fragments on (the fourth column of the output; >= 1) [default : 50]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -192,6 +202,7 @@ Options parse(int argc, char **argv)
   Options o;
   std::string refName, refList, qryName, qryList;
   bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
+  bool profileMinANI = false, profileMinFragments = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -232,6 +243,11 @@ Options parse(int argc, char **argv)
     else if (a == "-o" || a == "--output") o.out = need(i);
     else if (a == "--sketchGraph") { o.sketchGraph = (float)atof(need(i));
       if (!(o.sketchGraph > 0.0f && o.sketchGraph <= 100.0f)) { std::cerr << "ERROR, --sketchGraph takes an ANI threshold in (0, 100]" << std::endl; exit(1); } }
+    else if (a == "--profile") o.profile = true;
+    else if (a == "--profileMinANI") { o.profileMinANI = (float)atof(need(i)); profileMinANI = true;
+      if (!(o.profileMinANI > 0.0f && o.profileMinANI <= 100.0f)) { std::cerr << "ERROR, --profileMinANI takes an ANI in (0, 100]" << std::endl; exit(1); } }
+    else if (a == "--profileMinFragments") { o.profileMinFragments = atoi(need(i)); profileMinFragments = true;
+      if (o.profileMinFragments < 1) { std::cerr << "ERROR, --profileMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
     else if (a == "--saveSketch") o.saveSketch = need(i);
@@ -252,6 +268,8 @@ Options parse(int argc, char **argv)
     exit(1); }
   if (o.sketchCluster > 0.0f && sketchContain && o.sketchContain != ANI_CONTAIN_MAX) { std::cerr << "ERROR, --sketchCluster takes --sketchContain max only" << std::endl;
     exit(1); }
+  if (profileMinANI && !o.profile) { std::cerr << "ERROR, --profileMinANI needs --profile" << std::endl; exit(1); }
+  if (profileMinFragments && !o.profile) { std::cerr << "ERROR, --profileMinFragments needs --profile" << std::endl; exit(1); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -614,6 +632,48 @@ struct QuerySigs {
 };
 QuerySigs g_qsigs;
 
+// --profile: the conservation profile (ani_sketch_profile_begin) of every reference, keyed by reference index.  The run is sharded by
+// reference, so a reference genome lives in one sketch at a time, which sees every query (of a wave) before it is destroyed: the profile
+// is begun where a reference sketch comes into being (a shard, a block of a sketch file, a reference split) and taken just before the
+// sketch is destroyed.  A block that is loaded once per wave of queries adds to what its earlier loads left: everything is a count, an
+// integer sum or a minimum / maximum.
+struct ProfileTable {
+  bool on = false; float minANI = 95.0f; int32_t minFragments = 50;
+  struct Ref { bool have = false; std::vector<int32_t> contigLen; std::vector<ani_binprofile_t> bins; uint64_t queries = 0; };
+  std::vector<Ref> ref;
+  void init(const Options &o) { on = o.profile; minANI = o.profileMinANI; minFragments = o.profileMinFragments; if (on) ref.resize(o.refs.size()); }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_profile_begin(sk, minANI, minFragments)) { std::cerr << "ERROR, ani_sketch_profile_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  // the profile of `sk` into the table: genome g of the sketch is reference refOf(g)
+  void take(const ani_sketch *sk, int32_t fragLen, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    uint64_t nBins = 0; int32_t nGenomes = 0; const int32_t *cl = nullptr, *gcs = nullptr;
+    if (ani_sketch_profile_bins(sk, &nBins) || ani_sketch_stats(sk, nullptr, nullptr, nullptr, nullptr, &nGenomes) || ani_sketch_tables(sk, &cl, &gcs)) {
+      std::cerr << "ERROR, profile: " << ani_last_error() << std::endl; exit(1); }
+    std::vector<ani_binprofile_t> bins((size_t)nBins); std::vector<uint32_t> queries((size_t)std::max(nGenomes, 1));
+    if (ani_sketch_profile_read(sk, bins.data(), queries.data())) { std::cerr << "ERROR, ani_sketch_profile_read: " << ani_last_error() << std::endl; exit(1); }
+    size_t b0 = 0;
+    for (int32_t g = 0; g < nGenomes; g++) {
+      size_t n = 0;
+      for (int32_t c = gcs[g]; c < gcs[g + 1]; c++) n += (size_t)(cl[c] / (fragLen - 20)) + 1;
+      Ref &r = ref[refOf(g)];
+      if (!r.have) { r.have = true; r.contigLen.assign(cl + gcs[g], cl + gcs[g + 1]); r.bins.assign(n, ani_binprofile_t{0, 0.0f, 0.0f, 0, 0}); }
+      r.queries += queries[(size_t)g];
+      for (size_t i = 0; i < n; i++) {
+        const ani_binprofile_t &x = bins[b0 + i]; ani_binprofile_t &y = r.bins[i];
+        if (!x.count) continue;
+        y.minIdentity = y.count ? std::min(y.minIdentity, x.minIdentity) : x.minIdentity; y.maxIdentity = std::max(y.maxIdentity, x.maxIdentity);
+        y.count += x.count; y.sum += x.sum;
+      }
+      b0 += n;
+    }
+  }
+};
+ProfileTable g_profile;
+
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
 // no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
@@ -880,9 +940,12 @@ struct Streaming {
     auto parts = collect ? map_waves() : map_resident();
     trace("queries mapped");
     for (auto &v : parts) { rows.insert(rows.end(), v.begin(), v.end()); std::vector<ani_cgi_t>().swap(v); }
-    for (int d = 0; d < nDev; d++) { if (shard[d].sk) ani_sketch_destroy(shard[d].sk);
+    for (int d = 0; d < nDev; d++) { if (shard[d].sk) { take_profile(d); ani_sketch_destroy(shard[d].sk); }
       std::cerr << "INFO [thread " << d << "], skch::main, ready to exit the loop" << std::endl; }
   }
+
+  // --profile: what the queries left in the shard's sketch, before the sketch goes (shard-local genome -> reference file index)
+  void take_profile(int d) { const int32_t g0 = shard[d].g0; g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); }); }
 
   // every device sketches its run of the reference slices into its shard's tables and record parts (all-vs-all: the query sets too)
   void sketch_references()
@@ -946,6 +1009,7 @@ struct Streaming {
     if (m.fromFile) {
       const int nRef = (int)o.refs.size();
       for (int d = 0; d < nDev; d++) {
+        if (shard[d].sk) take_profile(d);                                                                     // (before g0 moves on to the next block)
         const int64_t s0 = ((int64_t)nRef * d) / nDev, s1 = ((int64_t)nRef * (d + 1)) / nDev;               // the device's shard ...
         shard[d].g0 = (int32_t)(s0 + ((s1 - s0) * blk) / nBlocks);                                               // ... and the block of it
         shard[d].nGenomes = (int32_t)(s0 + ((s1 - s0) * (blk + 1)) / nBlocks) - shard[d].g0;
@@ -975,6 +1039,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
+    for (int d = 0; d < nDev; d++) g_profile.begin(shard[d].sk);
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1205,6 +1270,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
+    g_profile.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1259,6 +1325,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
         if (sp == 0) std::cerr << "INFO [thread 0], skch::main, Time spent post mapping : " << secs_since(tm) << " sec" << std::endl;
       }
     }
+    g_profile.take(sk, ap.fragLen, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });      // the split's genome g is reference refIdx[g]
     ani_sketch_destroy(sk);
   }
   for (int sp = 0; sp < nSplits; sp++) std::cerr << "INFO [thread " << sp << "], skch::main, ready to exit the loop" << std::endl;
@@ -1315,6 +1382,30 @@ void write_txt(const Options &o, const std::vector<ani_cgi_t> &rows, const Trust
   for (auto &e : rows)
     if (trusted(e))
       f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << e.identity << "\t" << e.countSeq << "\t" << e.totalQueryFragments << "\n";
+}
+
+// ---- .profile: per reference (reference-list order) and bin (contig order): reference, contig, start, end, queries, covered, mean,
+// min, max; the identities as the output file prints them, NA where no query reached the bin.  A bin that cannot hold the start of a
+// whole fragment (the tail of a contig) is left out unless something was mapped there.
+void write_profile(const Options &o, int32_t fragLen)
+{
+  BufferedFile f(o.out + ".profile");
+  const int64_t binW = fragLen - 20;
+  for (size_t r = 0; r < g_profile.ref.size(); r++) {
+    const ProfileTable::Ref &p = g_profile.ref[r];
+    size_t b = 0;
+    for (size_t c = 0; c < p.contigLen.size(); c++) {
+      const int64_t len = p.contigLen[c];
+      for (int64_t j = 0; j <= len / binW; j++, b++) {
+        const ani_binprofile_t &x = p.bins[b];
+        const int64_t start = j * binW;
+        if (start > len - fragLen && !x.count) continue;
+        f.out << o.refs[r] << "\t" << c + 1 << "\t" << start << "\t" << std::min((j + 1) * binW, len) << "\t" << p.queries << "\t" << x.count;
+        if (x.count) f.out << "\t" << (float)((double)x.sum / 1048576.0 / (double)x.count) << "\t" << x.minIdentity << "\t" << x.maxIdentity << "\n";
+        else f.out << "\tNA\tNA\tNA\n";
+      }
+    }
+  }
 }
 
 // The cells of the .matrix, shared by the .clusters writer so that the two files never disagree: genomes numbered queries first, then
@@ -1826,6 +1917,7 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
+  g_profile.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
   Startup su(o, m, ap);
@@ -1844,6 +1936,7 @@ int main(int argc, char **argv)
   const Trusted trusted(o, ap.fragLen, lengths);
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
+  if (o.profile) write_profile(o, ap.fragLen);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

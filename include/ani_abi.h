@@ -319,6 +319,41 @@ int ani_compute_cgi(ani_ctx *ctx, const ani_sketch *sk, const ani_mapping_t *map
 int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *sk, const ani_seq_batch_t *queries, int32_t firstQueryId,
                       ani_cgi_t **out, size_t *m);
 
+/* ---- per-bin conservation profile of the reference genomes (no counterpart in the reference, which folds the bin table of
+ * computeCoreIdentity.hpp:237-254 into a row per pair and drops it).  Between begin and end the sketch adds up,
+ * per reference bin of fragLen - 20 bases, how many query genomes reached the bin and how identical they were there: the bins present
+ * in every query are the core genome, the others islands.  Everything is integer or bit pattern: the result depends on no schedule,
+ * reduction order, sub-batch size, index chunking, residency mode or order of calls.
+ *  1. Bins.  Contig c of the sketch (set-global contig id, the order of ani_sketch_tables) has contigLen[c] / (fragLen - 20) + 1 bins;
+ *     bin j holds the start positions [j (fragLen - 20), (j + 1)(fragLen - 20)).  Bins are numbered contig by contig over the whole set:
+ *     binStart[c] = the bins of the contigs before c, nBins = binStart[nContigs] (64 bit; the numbering does not restart with an index
+ *     chunk).
+ *  2. Cell.  For a query genome q reduced against the sketch, cell(q, b) is what the reducer's bin table holds for bin b: the maximum,
+ *     over the fragments f of q whose 1-way winner lies in b, of that winner's identity; the 1-way winner of f is the maximum under
+ *     (nucIdentity bits, refSeqId, refStartPos) over f's mappings to b's genome; no such fragment: the cell is empty.  The row of
+ *     (q, g) stays what it is: countSeq = the non-empty cells of g, identity = their float mean in bin order.
+ *  3. Gate.  The pair (q, g) contributes iff it has a row, countSeq >= minFragments and bits(identity) >= bits(minIdentity);
+ *     minIdentity in [0, 100] (-0.0 counts as 0), minFragments >= 1.
+ *  4. Accumulation, per contributing pair: queries[g] += 1, and for every non-empty cell of g: count[b] += 1, sum[b] += fix(cell),
+ *     minIdentity[b] / maxIdentity[b] by bit pattern; fix(x) = (uint64_t) llrint((double) x * 2^20), round half even (exact for
+ *     x >= 8; a sum of 2^32 cells stays below 2^59).  A bin with count = 0 reads {0, 0.0f, 0.0f, 0, 0}.
+ *  5. Which calls.  Every call that reduces against the sketch between begin and end: ani_map_cgi_batch, ani_map_cgi_fragset(s),
+ *     ani_compute_cgi (and the test entry point ani_reduce_check); ani_map_query reduces nothing and adds nothing.  A genome mapped
+ *     twice counts twice.  A call that fails before it reduces anything (the argument checks of ani_compute_cgi) leaves the profile as
+ *     it was; after any other failed call the profile is unspecified until the next begin.
+ *  6. Rows are untouched: with or without a profile every mapping call returns the same rows, bit for bit.
+ * begin allocates and zeroes the accumulators on the device (20 bytes per bin + 4 per genome; 3 GB for 90 000 x 5 Mbp); a second begin
+ * resets them and takes the new gate.  bins works with or without a begin.  read does not reset; either pointer may be NULL.  end releases
+ * (ani_sketch_destroy does too).  ANI_ERR_ARG: a null sketch, minIdentity outside [0, 100] (NaN included), minFragments < 1, read or end
+ * without a begin; ANI_ERR_NOMEM: the device cannot hold the accumulators (the scalar checks come first); ANI_ERR_LIMIT at read: count and
+ * queries are 32 bit and a counter has reached 2^32 - 1 (it stays there instead of wrapping).  ani_sketch_save does not write the profile,
+ * and ani_sketch_set_ref_id_base does not apply: bins and genomes are the sketch's own. */
+typedef struct { uint32_t count; float minIdentity, maxIdentity; uint32_t reserved; uint64_t sum; } ani_binprofile_t;   /* 24 bytes */
+int ani_sketch_profile_begin(ani_sketch *sk, float minIdentity, int32_t minFragments);
+int ani_sketch_profile_bins(const ani_sketch *sk, uint64_t *nBins);
+int ani_sketch_profile_read(const ani_sketch *sk, ani_binprofile_t *bins /* [nBins] */, uint32_t *queries /* [nGenomes] */);
+int ani_sketch_profile_end(ani_sketch *sk);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
