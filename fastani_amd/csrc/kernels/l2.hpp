@@ -174,15 +174,15 @@ __host__ __device__ inline L2Result l2_candidate(const uint32_t *q, int s,
 //                candidate's event stream
 //   k_l2_codes   one workgroup per fragment: the fragment sketch sits in LDS; every reference minimizer of every
 //                candidate range is ranked against it once and written as its (at most) two window events — it enters the
-//                super-window, it leaves it — at their places in the candidate's MERGED event stream.  The merged order of the
+//                super-window, it leaves it — at their places in the candidate's MERGED event stream.  The entries of the first
+//                super-window but its last are not written as inserts: their sum goes in front of the stream as state (below).  The merged order of the
 //                events depends on the reference positions only and is precomputed per index entry (index.hpp:
 //                k_index_window_links), so a place is a few integer operations.  One event = 16 bits:
 //                  bit 0 = hash is a query hash, bits 1..9 = gap (or rank-1), bit 10 = a same-hash neighbour may share a
 //                  super-window with this entry (nearDup, precomputed at index build), bit 11 = insert (else delete),
-//                  bit 12 = do not evaluate the window after this event (first super-window still filling / the insert of
-//                  the same position follows)
-//   k_l2_sim     one lane per candidate: applies its events in order, one per loop pass, 8 events per 16-byte load, no position
-//                arithmetic and no second cursor.  State in LDS: one byte per sketch rank (7-bit gap counter + presence bit),
+//                  bit 12 = do not evaluate the window after this event (the insert of the same position follows)
+//   k_l2_sim     one lane per candidate: loads the first super-window's state, then applies the events in order, one per loop pass,
+//                8 events per 16-byte load, no position arithmetic and no second cursor.  State in LDS: one byte per sketch rank (7-bit gap counter + presence bit),
 //                byte-interleaved over the wave.  Entries flagged nearDup consult the same-hash links (exact set semantics,
 //                slidingMap.hpp:150-154,:178).  A gap counter that would pass 127 sends the candidate to k_l2.
 // ------------------------------------------------------------------------------------------------
@@ -251,14 +251,19 @@ struct L2Geom {
 using L2GeomA = L2Geom<255>;
 using L2GeomB = L2Geom<319>;
 constexpr int kL2SimTPB = 64;
+// A candidate's piece of the code buffer, in 16-bit entries: the fields of the first super-window as the simulation keeps them (one byte
+// per field, kStateWords dwords of its class), then the events.
+__host__ __device__ __forceinline__ int l2_state_entries(bool classA) { return 2 * (classA ? L2GeomA::kStateWords : L2GeomB::kStateWords); }
 
-struct L2Range { int32_t beg0, end0, last, nEvents; };    // nEvents = length of the candidate's event stream
+// nEvents = length of the candidate's event stream: the events from the insert of the first super-window's LAST entry on (the
+// entries [beg0, end0 - 1) before it are handed over as state)
+struct L2Range { int32_t beg0, end0, last, nEvents; };
 
 struct L2FastArgs {
   L2Args g;
   int32_t c0, c1;                  // candidate chunk [c0, c1)
   L2Range *ranges;                 // [c1-c0]
-  int32_t *codeCount;              // [c1-c0] 16-bit events per candidate rounded up to 8, 0 = not on the fast path (or nothing to simulate)
+  int32_t *codeCount;              // [c1-c0] 16-bit entries per candidate (state + events rounded up to 8), 0 = not on the fast path (or nothing to simulate)
   const uint32_t *codeOff;         // [c1-c0] exclusive scan of codeCount (in entries)
   uint32_t *codes;
   int32_t *slowFlag;               // [c1-c0] 1 = take the general kernel
@@ -302,7 +307,8 @@ static __global__ __launch_bounds__(kTPB) void k_l2_ranges(L2FastArgs a)
   if (fast && r.end0 < r.last) {
     const int32_t lastDel = (r.last - 1) - (int32_t)(a.g.mWin[r.last - 1] & kWinMask) - 2;     // deletes with D_j <= I_(last-1)
     const int32_t nDel = lastDel >= r.beg0 ? lastDel - r.beg0 + 1 : 0;
-    nEv = (r.end0 - r.beg0) + (r.last - 1 - r.end0) + nDel;
+    // the inserts of [beg0, end0 - 1) are never evaluated and come first: k_l2_codes hands their sum over as state instead
+    nEv = 1 + (r.last - 1 - r.end0) + nDel;
   }
   r.nEvents = nEv;
   a.ranges[i] = r;
@@ -311,8 +317,10 @@ static __global__ __launch_bounds__(kTPB) void k_l2_ranges(L2FastArgs a)
     a.codeCount[i] = 0; a.slowFlag[i] = 16;          // done
     return;
   }
-  a.codeCount[i] = fast ? ((nEv + 8) & ~7) : 0;      // 16-bit events, padded to 16-byte blocks with at least one pad slot (k_l2_codes)
-  a.slowFlag[i] = fast ? ((s <= L2GeomA::kMaxS && a.allowFast != 2) ? 0 : 4) : 1;
+  const bool classA = s <= L2GeomA::kMaxS && a.allowFast != 2;
+  // 16-bit events, padded to 16-byte blocks with at least one pad slot (k_l2_codes), behind the state
+  a.codeCount[i] = fast ? l2_state_entries(classA) + ((nEv + 8) & ~7) : 0;
+  a.slowFlag[i] = fast ? (classA ? 0 : 4) : 1;
 }
 
 constexpr uint32_t kL2DupBit = 1u << 10, kL2InsBit = 1u << 11, kL2NoEvalBit = 1u << 12;
@@ -388,13 +396,24 @@ __device__ __forceinline__ uint32_t l2_rank_deep(const uint32_t *qs, const uint3
 // A lane ranks four entries per pass, 64 apart (every load is one contiguous 256-byte run per wave); the loads of the next pass or
 // candidate are in flight while the current one is ranked.  The rank lookup has no loop: 2048 buckets for ~240 sketch hashes, so a
 // bucket holds at most two of them except in rare cases, which a wave vote sends to a binary search.
-constexpr int kL2StageEvents = 2048;        // events per wave window (4 KiB)
+// The first super-window is not written as events.  Its entries [beg0, end0 - 1) are never evaluated and always come first in the
+// stream, and the state they leave behind depends on their multiset only, so the wave that ranks them adds each one's field change
+// (+2 for a non-query hash, +1 for a query hash, at field rank >> 1) into a histogram in its LDS window — 16-bit counters packed
+// in pairs, plain ds_add; nothing can carry: a range has <= kL2FastMaxEntries entries — and when the passes over them are done it
+// packs the counters to the simulation's bytes and writes them in front of the events, 256 bytes per wave instruction.  A field
+// beyond 255 is the overflow the simulation would have met while the window fills: the candidate goes to k_l2.  The pivot of that
+// state is found by the simulation while it loads it (64 candidates per wave there, one here: a wave scan in this kernel cost
+// more than the serial search it replaced, docs/history.md section 2.5).
+constexpr int kL2WaveWindow = 2048;         // 16-bit slots per wave window (4 KiB): the histogram, then the staged events
+constexpr int kL2HistWords = (kL2FastMaxS + 1) / 2;                   // one 16-bit counter per field 0..kL2FastMaxS
+constexpr int kL2StageEvents = kL2WaveWindow - 2 * kL2HistWords;      // events a wave stages in LDS (1728)
+static_assert(kL2HistWords == 2 * L2GeomB::kStateWords && (kL2HistWords & 3) == 0 && L2GeomB::kStateWords <= 2 * kWave, "histogram: two dwords per state dword, 16-byte multiple, two state dwords per lane");
 constexpr int kL2CandBatch = 40;            // candidates whose descriptors are fetched at once
 static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
 {
   __shared__ uint32_t qs[kL2FastMaxS + 2];
   __shared__ __attribute__((aligned(16))) uint32_t st2[kL2RankBuckets];
-  __shared__ __attribute__((aligned(16))) uint16_t stageAll[(kTPB / kWave) * kL2StageEvents];
+  __shared__ __attribute__((aligned(16))) uint16_t stageAll[(kTPB / kWave) * kL2WaveWindow];
   __shared__ L2Range cRange[kL2CandBatch];         // the candidates' descriptors, fetched side by side (nEvents < 0: no stream)
   __shared__ uint64_t cOff[kL2CandBatch];
   __shared__ int cRangeScan[8];                    // scratch of the workgroup scan
@@ -434,13 +453,21 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
   // from here on the waves go their own ways; the counters are dead, the windows are free
 
   const int lane = threadIdx.x & (kWave - 1), wv = wave_uniform((int32_t)(threadIdx.x >> 6));
-  uint16_t *stage = stageAll + wv * kL2StageEvents;
+  uint32_t *hist = (uint32_t *)(stageAll + wv * kL2WaveWindow);
+  uint16_t *stage = stageAll + wv * kL2WaveWindow + 2 * kL2HistWords;
+  const bool classA = s <= L2GeomA::kMaxS && a.allowFast != 2;          // as k_l2_ranges decides it
+  const int stateWords = classA ? L2GeomA::kStateWords : L2GeomB::kStateWords;
+  // a lane owns the counters of the state dwords `lane` and `lane + 64` (class B: 80 dwords): it clears them here, and again when it
+  // has read them; class A never touches the others (rank <= s <= 255)
+  for (int x = lane; x < stateWords; x += kWave) { hist[2 * x] = 0u; hist[2 * x + 1] = 0u; }
+  ANI_WAVE_SYNC();
   // Work items of this wave = (candidate, pass of 4 * 64 entries), in order.  Everything in an item is wave-uniform and kept in
   // scalar registers (wave_uniform): the item loop then branches on scalars and the per-entry bounds tests take scalar operands.
   struct Item {
     int32_t c; uint32_t jb;                          // candidate, first entry of the pass
     char *ob; const char *hb, *wb;                   // wave-uniform bases: event stream, hashes, window links (32-bit byte offsets per lane)
     uint32_t m, nInit, nInsAll, nDel, dump; bool staged, lastPass;
+    uint32_t K; int32_t beg0;                        // entries [0, K) = [beg0, end0 - 1) become state, not events
   };
   constexpr uint32_t kPass = 4u * kWave;
   int32_t batch0 = cA, batch1 = cA + kL2CandBatch < cB ? cA + kL2CandBatch : cB;      // candidates whose descriptors are in LDS
@@ -451,11 +478,12 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
       if (r.nEvents < 0) continue;
       r.beg0 = wave_uniform(r.beg0); r.end0 = wave_uniform(r.end0); r.last = wave_uniform(r.last);
       it.c = c; it.jb = 0;
-      it.ob = (char *)((uint16_t *)a.codes + wave_uniform(cOff[c - batch0]));
+      it.ob = (char *)((uint16_t *)a.codes + wave_uniform(cOff[c - batch0]) + (uint64_t)(2 * stateWords));
       it.hb = (const char *)(a.g.mHash + r.beg0); it.wb = (const char *)(a.g.mWin + r.beg0);
       it.m = (uint32_t)(r.last - r.beg0);
       it.nInit = (uint32_t)(r.end0 - r.beg0); it.nInsAll = it.m - 1;          // inserts (first window included) are the entries [0, m-1)
-      it.nDel = (uint32_t)r.nEvents - it.nInsAll;                             // deletes are the entries [0, nDel)
+      it.K = it.nInit - 1u; it.beg0 = r.beg0;
+      it.nDel = (uint32_t)r.nEvents + it.K - it.nInsAll;                      // deletes are the entries [0, nDel)
       it.dump = (uint32_t)r.nEvents;                                          // pad slot
       it.staged = (uint32_t)r.nEvents < (uint32_t)kL2StageEvents;
       it.lastPass = kPass >= it.m;
@@ -499,8 +527,33 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
   #pragma unroll
         for (int e = 0; e < E; e++) rk[e] = l2_rank_deep(qs, st2, sh, s, h[e], rk[e]);
       }
+      // entries of the first super-window (all but its last): into the histogram.  Wave-uniform branch; per-lane predicate — the
+      // window can end anywhere in a pass and span several.  An entry whose hash already sits in [beg0, it) adds nothing
+      // (slidingMap.hpp:150-154); those are rare and looked up behind a wave vote.
+      // The 64 entries of a slot e are all inside the window, all outside, or (one slot per candidate) split: wave-uniform tests.
+      if (cur.jb < cur.K) {
+        uint32_t dl[4] = {0u, 0u, 0u, 0u}; uint32_t dupAny = 0;
+  #pragma unroll
+        for (int e = 0; e < E; e++) {
+          const uint32_t x0 = cur.jb + e * kWave;
+          if (x0 >= cur.K) continue;
+          const uint32_t d = 2u - (rk[e] & 1u);
+          if (x0 + kWave <= cur.K) { dl[e] = d; dupAny |= wl[e]; }
+          else { const bool in = x0 + lane < cur.K; dl[e] = in ? d : 0u; dupAny |= in ? wl[e] : 0u; }
+        }
+        if (__any((dupAny & kWinDupBit) != 0)) {
+  #pragma unroll
+          for (int e = 0; e < E; e++)
+            if (dl[e] && (wl[e] & kWinDupBit) && dup_prev(a.g.dup, (uint32_t)cur.beg0 + cur.jb + lane + e * kWave) >= cur.beg0) dl[e] = 0u;
+        }
+  #pragma unroll
+        for (int e = 0; e < E; e++)                                                         // (adding 0 is cheaper than a branch around it)
+          if (cur.jb + e * kWave < cur.K) atomicAdd(&hist[rk[e] >> 2], dl[e] << ((rk[e] & 2u) << 3));
+      }
       // Two events per entry, stored without control flow: an event that does not exist (entries beyond the range, the never-inserted
-      // last entry, entries that never leave) goes to the pad slot behind the stream (k_l2_ranges reserves one).
+      // last entry, entries that never leave, the inserts handed over as state) goes to the pad slot behind the stream (k_l2_ranges
+      // reserves one).  Places are those of the merged stream less the K inserts in front of it.  A slot whose 64 entries are all
+      // handed over (wave-uniform) has no insert events at all: neither computed nor stored.
       uint32_t pi[4], pd[4]; uint16_t ci[4], cdl[4];
       const uint32_t dumpSlot = cur.dump;
   #pragma unroll
@@ -510,22 +563,25 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
         // field change of the event, 3-bit two's complement: insert +2 (010), of a query hash +1 (001); delete -2 (110) / -1 (111)
         const uint32_t mq = 0u - (rk[e] & 1u);                                            // all ones for a query hash
         // insert of entry x: after the inserts of the entries before it and the deletes of the entries up to x - B - 2
-        const int32_t db = (int32_t)x - (int32_t)(wl[e] & kWinMask) - 1;                 // deletes that precede it
-        pi[e] = x < cur.nInsAll ? x + (uint32_t)(db < 0 ? 0 : db) : dumpSlot;
-        ci[e] = (uint16_t)((cd | kL2InsBit | (2u << kL2DeltaShift) | ((int32_t)x < (int32_t)cur.nInit - 1 ? kL2NoEvalBit : 0u)) ^ (mq & (3u << kL2DeltaShift)));
+        pi[e] = dumpSlot; ci[e] = 0;
+        if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) {
+          const int32_t db = (int32_t)x - (int32_t)(wl[e] & kWinMask) - 1;               // deletes that precede it
+          pi[e] = x - cur.K < cur.nInsAll - cur.K ? x - cur.K + (uint32_t)(db < 0 ? 0 : db) : dumpSlot;
+          ci[e] = (uint16_t)((cd | kL2InsBit | (2u << kL2DeltaShift)) ^ (mq & (3u << kL2DeltaShift)));
+        }
         // delete of entry x: after the deletes of the entries before it and the inserts of the entries below x + A (at least the first
         // window's)
         const uint32_t ib = x + ((wl[e] >> kWinShiftA) & kWinMask);
-        pd[e] = x < cur.nDel ? x + (ib < cur.nInit ? cur.nInit : ib) : dumpSlot;
+        pd[e] = x < cur.nDel ? x + (ib < cur.nInit ? cur.nInit : ib) - cur.K : dumpSlot;
         // kWinMoreBit (bit 30) -> kL2NoEvalBit (bit 12)
         cdl[e] = (uint16_t)(cd | ((wl[e] >> 18) & kL2NoEvalBit) | (6u << kL2DeltaShift) | (mq & (1u << kL2DeltaShift)));
       }
       if (cur.staged) {                                                                   // wave-uniform choice
   #pragma unroll
-        for (int e = 0; e < E; e++) { stage[pi[e]] = ci[e]; stage[pd[e]] = cdl[e]; }
+        for (int e = 0; e < E; e++) { if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) stage[pi[e]] = ci[e]; stage[pd[e]] = cdl[e]; }
       } else {
   #pragma unroll
-        for (int e = 0; e < E; e++) { *(uint16_t *)(cur.ob + pi[e] * 2u) = ci[e]; *(uint16_t *)(cur.ob + pd[e] * 2u) = cdl[e]; }
+        for (int e = 0; e < E; e++) { if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) *(uint16_t *)(cur.ob + pi[e] * 2u) = ci[e]; *(uint16_t *)(cur.ob + pd[e] * 2u) = cdl[e]; }
       }
     };
     {
@@ -534,6 +590,21 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
       else if (left > 2u * kWave) pass_body(std::integral_constant<int, 3>());
       else if (left > (uint32_t)kWave) pass_body(std::integral_constant<int, 2>());
       else pass_body(std::integral_constant<int, 1>());
+    }
+    // the passes over the first super-window are done (once per candidate: the first pass that reaches entry K)
+    if (cur.jb + kPass >= cur.K && (cur.jb == 0u || cur.jb < cur.K)) {
+      ANI_WAVE_SYNC();
+      uint32_t *state = (uint32_t *)cur.ob - stateWords;
+      uint32_t ovf = 0;
+      for (int x = lane; x < stateWords; x += kWave) {               // state dword x = fields 4x .. 4x+3; class B: a second round of 16 lanes
+        const uint32_t c0 = hist[2 * x], c1 = hist[2 * x + 1];
+        hist[2 * x] = 0u; hist[2 * x + 1] = 0u;                      // for the wave's next candidate
+        ovf |= (c0 | c1) & 0xff00ff00u;
+        state[x] = perm_b32(c1, c0, 0x06040200u);                    // the low bytes of the four counters
+      }
+      // the simulation would have overflowed this byte while the window fills
+      if (__any(ovf != 0) && lane == 0) a.slowFlag[cur.c - a.c0] = 3;
+      ANI_WAVE_SYNC();
     }
     if (cur.staged && cur.lastPass) {                // the candidate's stream is complete in the window: write it out
       ANI_WAVE_SYNC();
@@ -562,7 +633,11 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
 // (byte-interleaved over the wave: one shift to address it; the only bank conflicts are between the four lanes of a dword
 // column whose g differ by a multiple of 4 — the LDS pipe has an order of magnitude of slack under the VALU work of a step).
 struct L2Regs { int s, iStar, tot, shared; uint32_t ovfAcc; };   // tot = iStar + (non-query hashes below the pivot) = rank of q_iStar in the union
+#ifdef ANI_L2_WORD_INTERLEAVE                                  // build switch for A/B measurements: the conflict-free word-interleaved layout
+constexpr bool kL2ByteInterleave = false;
+#else
 constexpr bool kL2ByteInterleave = true;
+#endif
 __device__ __forceinline__ int l2_field_off(int g) { return kL2ByteInterleave ? (g << 6) : (((g >> 2) << 8) + (g & 3)); }
 
 // The kernel is VALU-bound, so the event is applied with as few vector instructions as the arithmetic allows: the field change comes
@@ -619,6 +694,15 @@ __device__ __forceinline__ void l2_apply(uint8_t *F, L2Regs &r, uint32_t code, b
 // keep the block in scratch memory and store it there once per block — 29 GB of writes per benchmark step that nothing ever read
 // back — and member-wise assignment split the 16-byte load into four.)
 typedef uint32_t L2Block __attribute__((vector_size(16)));
+// acc + the sum of the four bytes of x (v_sad_u8 against zero)
+__device__ __forceinline__ uint32_t l2_byte_sum(uint32_t x, uint32_t acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_sad_u8(x, 0u, acc);
+#else
+  return acc + (x & 0xffu) + ((x >> 8) & 0xffu) + ((x >> 16) & 0xffu) + (x >> 24);
+#endif
+}
 __device__ __forceinline__ L2Block l2_block_zero() { const L2Block b = {0u, 0u, 0u, 0u}; return b; }
 __device__ __forceinline__ L2Block l2_block_load(bool on, const uint4 *p, L2Block otherwise)
 {
@@ -640,9 +724,6 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
     if ((unsigned int)(blockIdx.x * blockDim.x) >= n) return;         // whole workgroup beyond the list
     c = (unsigned int)slot < n ? list[slot] : a.c1;
   }
-  // four lanes share each state dword, so the whole wave clears the state, whether or not a lane has a candidate
-#pragma unroll
-  for (int x = 0; x < G::kStateWords; x++) S[x * kWave] = 0u;
   unsigned long long cntE = 0, cntS = 0, cntQ = 0;
   const int myFlag = c < a.c1 ? a.slowFlag[c - a.c0] : 1;
   const bool mine = (G::kMaxS == 255) ? (myFlag == 0) : (myFlag == 4);
@@ -650,13 +731,53 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
   L2Range r; r.beg0 = 0; r.end0 = 0; r.last = 0; r.nEvents = 0;
   if (mine) r = a.ranges[i];
   const int n = r.nEvents;                                            // 0 for a lane without a candidate: it idles
-  L2Regs R; R.s = mine ? a.g.fragS[a.g.candFrag[c]] : 1; R.iStar = R.s; R.tot = R.s; R.shared = 0; R.ovfAcc = 0;
-  const uint4 *p = (const uint4 *)((const uint16_t *)a.codes + (mine ? a.codeOff[i] : 0u));      // idle lanes read the head of the buffer
+  const int nHand = mine ? r.end0 - r.beg0 - 1 : 0;                   // inserts that arrive as state: the entries [beg0, end0 - 1)
+  // The candidate's piece of the code buffer: state of the first super-window (k_l2_codes summed its inserts), then the events.
+  const uint4 *p = (const uint4 *)((const uint16_t *)a.codes + (mine ? a.codeOff[i] : 0u));      // idle lanes read nothing
+  L2Regs R; R.s = mine ? a.g.fragS[a.g.candFrag[c]] : 1; R.ovfAcc = 0;
+  // Four lanes share each state dword of the byte-interleaved layout, so every lane writes its fields, zeros if it has no candidate.
+  // The pivot of the loaded state is found on the way, a dword (four ranks) at a time:
+  //     iStar = max{i : G(i) <= s},  G(i) = i + sum_{g<i} n[g]  (strictly increasing),  tot = G(iStar),  shared = sum_{i<=iStar} b[i].
+  // G increases, so the dwords whose four ranks all qualify are a prefix; the ranks of the first dword that does not are looked at
+  // one by one afterwards.
+  int accN = 0, accFull = 0, nFull = 0, shFull = 0;                   // sum of n[] so far / over the qualifying dwords, their number, their sum of b[]
+#pragma unroll
+  for (int x4 = 0; x4 < G::kStateWords / 4; x4++) {
+    L2Block v = l2_block_zero();
+    if (mine) v = *(const L2Block *)(p + x4);
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+      const uint32_t dw = v[y];
+      const int x = 4 * x4 + y;
+      if (kL2ByteInterleave) {
+#pragma unroll
+        for (int b = 0; b < 4; b++) F[l2_field_off(4 * x + b)] = (uint8_t)(dw >> (8 * b));
+      } else S[x * kWave] = dw;
+      accN = (int)l2_byte_sum((dw >> 1) & 0x7f7f7f7fu, (uint32_t)accN);
+      const bool full = 4 * (x + 1) + accN <= R.s;                    // G(4x + 4) <= s
+      nFull += full ? 1 : 0;
+      accFull = full ? accN : accFull;
+      shFull += full ? __popc(dw & 0x01010101u) : 0;
+    }
+  }
+  p += G::kStateWords / 4;
+  {
+    int run = accFull, below = accFull, cnt = 0, sh = shFull;         // nFull <= s / 4 < kStateWords: the dword exists
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int f = F[l2_field_off(4 * nFull + j)];                   // n[i-1] << 1 | b[i]
+      run += f >> 1;
+      const bool ok = 4 * nFull + j + 1 + run <= R.s;                 // G(i) <= s (which implies i <= s); true for a prefix of the four
+      below = ok ? run : below; cnt += ok ? 1 : 0; sh += ok ? (f & 1) : 0;
+    }
+    R.iStar = 4 * nFull + cnt; R.tot = R.iStar + below; R.shared = sh;
+  }
   const int nBlk = (n + 7) >> 3;
   int best = 0, begAtBest = -1, begAtLast = -1, steps = 0, delCount = 0;
-  // A lane without a candidate of this class (class-B and general-path candidates sit in the same length-ordered list: about every
-  // tenth lane) reads no stream: its words stay zero — event 0 is "delete a non-query hash from field 0 and evaluate", harmless on
-  // its own cleared state — so that it counts as PLAIN below instead of sending its whole wave through the general form for good.
+  // A lane without a candidate of this class (class-B and general-path candidates sit in the same length-ordered list; on the
+  // benchmark, where 1.25 % of the fragments have s > 255, about one lane in eighty) reads no stream: its words stay zero — event 0 is "delete a non-query hash from field 0 and
+  // evaluate", harmless on its own cleared state — so that it counts as PLAIN below instead of sending its whole wave through the
+  // general form for good.
   L2Block cur = l2_block_load(mine, p, l2_block_zero());
   // one block = 8 events.  PLAIN: every lane of the wave has all 8 events and none of them is flagged nearDup (two wave votes per
   // block decide) — then an event needs no bounds test and no look-up path; otherwise the block takes the general form.
@@ -666,14 +787,14 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       const uint32_t code = (e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu);
-      const int ev = 8 * blk + e;                                     // events applied so far
+      const int ev = 8 * blk + e;                                     // events of the stream applied so far
       const bool on = PLAIN ? true : ev < n;
       const bool INS = (code & kL2InsBit) != 0;
       bool eff = on;
       if (!PLAIN) {
         if (__any(on && (code & kL2DupBit) != 0)) {
           if (on && (code & kL2DupBit)) {
-            const int insCount = ev - delCount;                       // entries [delCount, insCount) are in the window
+            const int insCount = nHand + ev - delCount;               // entries [delCount, insCount) are in the window
             if (INS) eff = dup_prev(a.g.dup, (uint32_t)(r.beg0 + insCount)) < r.beg0 + delCount;            // new iff no same-hash entry in [beg, end)
             // stays iff a later same-hash entry is in the window
             else { const int32_t nx = dup_next(a.g.dup, (uint32_t)(r.beg0 + delCount)); eff = !(nx >= 0 && nx < r.beg0 + insCount); }
@@ -692,54 +813,15 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
       steps += evl ? 1 : 0;
     }
   };
-  // Phase A: the first super-window fills.  Its inserts are never evaluated (kL2NoEvalBit: computeMap.hpp:448 inserts [beg, end)
-  // before the loop of :455 looks at anything), so they need no pivot — an event is its field update, 9 instructions instead of
-  // ~55 — and the pivot is found once afterwards: the state is a function of the window's multiset, not of the order of the events,
-  //     iStar = max{i : G(i) <= s},  G(i) = i + sum_{g<i} n[g]  (strictly increasing),  tot = G(iStar),  shared = sum_{i<=iStar} b[i].
-  // A quarter of all events are such inserts (~240 of ~960 per candidate).  The phase lasts while every lane's block holds eight of
-  // them; from then on the general loop below takes over, mid-window if need be.
-  // What it buys is bounded by the LDS round trip of the byte read-modify-write chain (eight dependent ones per block, 2.5 waves
-  // per SIMD to hide them): k_l2_sim 47.7 -> 43.7 ms per step.  Measured and dropped: the updates as LDS atomics on the shared
-  // dwords, returning (43.9 ms) or fire-and-forget with a sum check against carries between the lanes' bytes (46.7 ms); four events
-  // at a time with their fields read together and same-field events added up in registers (44.5 ms).
+  // The first super-window does not fill here.  Its inserts [beg0, end0 - 1) are never evaluated (computeMap.hpp:448 inserts [beg,
+  // end) before the loop of :455 looks at anything) and the state after them is a function of the window's multiset, not of the
+  // order of the events,
+  //     iStar = max{i : G(i) <= s},  G(i) = i + sum_{g<i} n[g]  (strictly increasing),  tot = G(iStar),  shared = sum_{i<=iStar} b[i],
+  // so k_l2_codes, whose wave holds every entry's rank, sums them in parallel and the pivot is found above, from registers, while
+  // the state is loaded; the stream starts at the insert of the window's last entry, after which the first evaluation happens.  (Until then this kernel replayed them:
+  // a fill phase of field updates without pivot, 9 instructions per event, that lasted as long as the shortest first window of
+  // the wave, the rest in the general form, and a serial pivot search of iStar steps; docs/history.md section 2.5.)
   int blk = 0;
-  {
-    constexpr uint32_t kFillPair = (kL2InsBit | kL2NoEvalBit) * 0x10001u, kDupPair = kL2DupBit * 0x10001u;
-    for (; __any(mine); blk++) {
-      const uint32_t andw = cur[0] & cur[1] & cur[2] & cur[3], orw = cur[0] | cur[1] | cur[2] | cur[3];
-      const bool fill = 8 * blk + 8 <= n && (andw & kFillPair) == kFillPair;
-      if (!__all(fill || !mine)) break;
-      const int nb = blk + 1 < nBlk ? blk + 1 : blk;
-      const L2Block nxt = l2_block_load(mine, p + nb, cur);
-      const bool anyDup = __any(mine && (orw & kDupPair) != 0);         // rare: an entry with a same-hash neighbour nearby
-      if (mine) {
-        const uint32_t wd[4] = {cur[0], cur[1], cur[2], cur[3]};
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          const uint32_t code = (e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu);
-          int d = (int)((code >> kL2DeltaShift) & 7u);                   // an insert's change is +1 or +2
-          // the window starts at the candidate's first entry and nothing has left it: entry number 8 blk + e is new unless a
-          // same-hash entry lies in [beg0, it) (slidingMap.hpp:150-154)
-          if (anyDup && (code & kL2DupBit) && dup_prev(a.g.dup, (uint32_t)(r.beg0 + 8 * blk + e)) >= r.beg0) d = 0;
-          uint8_t *pOwn = F + l2_field_off((int)((code >> 1) & 0x1ffu));
-          const int nw = (int)*pOwn + d;
-          R.ovfAcc |= (uint32_t)nw;
-          *pOwn = (uint8_t)nw;
-        }
-      }
-      cur = nxt;
-    }
-    if (blk > 0) {                                                      // wave-uniform
-      int iS = 0, tot = 0, sh = 0, acc = 0; bool open = mine;
-      for (int i = 1; __any(open && i <= R.s); i++) {
-        const int f = F[l2_field_off(i - 1)];                           // n[i-1] << 1 | b[i]
-        acc += f >> 1;
-        open = open && i <= R.s && i + acc <= R.s;
-        iS = open ? i : iS; tot = open ? i + acc : tot; sh += open ? (f & 1) : 0;
-      }
-      R.iStar = mine ? iS : R.iStar; R.tot = mine ? tot : R.tot; R.shared = mine ? sh : R.shared;
-    }
-  }
   for (; __any(blk < nBlk); blk++) {
     const int nb = blk + 1 < nBlk ? blk + 1 : blk;                     // never beyond the lane's own stream
     const L2Block nxt = l2_block_load(mine, p + nb, cur);
@@ -779,17 +861,18 @@ static __global__ void k_l2_collect_slow(int32_t c0, int32_t n, const int32_t *_
   if (i < n && (slowFlag[i] & 3)) { list[atomicAdd(count, 1u)] = c0 + i; atomicAdd(&reasons[slowFlag[i] & 3], 1ull); }
 }
 
-// Candidates of a chunk ordered by the length of their code stream (counting sort on codeCount / 16): the 64 lanes of a wave
+// Candidates of a chunk ordered by the length of their event stream (counting sort on the padded event count / 32; header and
+// state, the same for every candidate of a class, stay out of it; candidates without a stream have nEvents = 0): the 64 lanes of a wave
 // then run about the same number of steps instead of waiting for the longest of 64 random candidates.
-constexpr int kL2LenBuckets = 1024;      // codeCount <= 2 * 16384 -> bucket = codeCount >> 5
-static __global__ __launch_bounds__(kTPB) void k_l2_len_hist(const int32_t *__restrict__ codeCount, int32_t n, unsigned int *__restrict__ hist)
+constexpr int kL2LenBuckets = 1024;      // events <= 2 * 16384 -> bucket = padded events >> 5
+__device__ __forceinline__ int l2_len_bucket(const L2Range &r) { const int b = ((r.nEvents + 8) & ~7) >> 5; return b >= kL2LenBuckets ? kL2LenBuckets - 1 : b; }
+static __global__ __launch_bounds__(kTPB) void k_l2_len_hist(const L2Range *__restrict__ ranges, int32_t n, unsigned int *__restrict__ hist)
 {
   __shared__ unsigned int h[kL2LenBuckets];
   for (int i = threadIdx.x; i < kL2LenBuckets; i += kTPB) h[i] = 0;
   block_barrier();
   for (int i = blockIdx.x * kTPB + threadIdx.x; i < n; i += gridDim.x * kTPB) {
-    int b = codeCount[i] >> 5; b = b >= kL2LenBuckets ? kL2LenBuckets - 1 : b;
-    atomicAdd(&h[kL2LenBuckets - 1 - b], 1u);                  // longest first
+    atomicAdd(&h[kL2LenBuckets - 1 - l2_len_bucket(ranges[i])], 1u);      // longest first
   }
   block_barrier();
   for (int i = threadIdx.x; i < kL2LenBuckets; i += kTPB) if (h[i]) atomicAdd(&hist[i], h[i]);
@@ -799,7 +882,7 @@ static __global__ __launch_bounds__(kTPB) void k_l2_len_scan(unsigned int *__res
   __shared__ int ws[16];
   block_array_excl_scan((int *)hist, kL2LenBuckets, ws);
 }
-static __global__ __launch_bounds__(kTPB) void k_l2_len_scatter(const int32_t *__restrict__ codeCount, int32_t c0, int32_t n,
+static __global__ __launch_bounds__(kTPB) void k_l2_len_scatter(const L2Range *__restrict__ ranges, int32_t c0, int32_t n,
                                                          unsigned int *__restrict__ cursor, int32_t *__restrict__ order)
 {
   // one global atomic per (workgroup, bucket): ranks inside the workgroup come from LDS atomics
@@ -809,8 +892,7 @@ static __global__ __launch_bounds__(kTPB) void k_l2_len_scatter(const int32_t *_
   const int i = blockIdx.x * kTPB + threadIdx.x;
   int b = 0; unsigned int r = 0;
   if (i < n) {
-    b = codeCount[i] >> 5; b = b >= kL2LenBuckets ? kL2LenBuckets - 1 : b;
-    b = kL2LenBuckets - 1 - b;
+    b = kL2LenBuckets - 1 - l2_len_bucket(ranges[i]);
     r = atomicAdd(&cnt[b], 1u);
   }
   block_barrier();
