@@ -14,7 +14,7 @@ void free_chunk_index(IndexChunk *ch)
       (void **)&ch->mWpos,
                    (void **)&ch->sHash, (void **)&ch->table, (void **)&ch->contigFirstMin, (void **)&ch->posSample};
   for (void **q : ptrs) if (*q) { pool_free(*q); *q = nullptr; }
-  ch->resident = false; ch->nDup = 0;
+  ch->resident = false; ch->nDup = 0; ch->tableAlloc = 0;
 }
 // the accumulators of the conservation profile (ani_sketch_profile_begin)
 void free_chunk_profile(IndexChunk *ch)
@@ -273,7 +273,7 @@ int build_chunk_index(ani_ctx *ctx, const ani_params_t *p, IndexChunk *sk)
       if (winLinks && sk->nDup) hipLaunchKernelGGL(k_index_mark_dups, dim3(grid_for((size_t)sk->nDup)), dim3(256), 0, ctx->stream,
           (const uint64_t *)sk->dupList, sk->nDup, sk->mWin);
       SK_HIP(hipStreamSynchronize(ctx->stream));                             // cnt / best / sentinel are host memory
-      sk->tableSlots = nSlots;
+      sk->tableSlots = nSlots; sk->tableAlloc = (uint32_t)alloc;
     }
     SK_HIP(hipGetLastError());
   }
@@ -469,6 +469,26 @@ int exact_unique(ani_sketch *sk)
   return ANI_OK;
 }
 
+// TEST INFRASTRUCTURE (ani_index_probe_check below): table_probe as l1_probe calls it, one thread per hash
+static __global__ void k_index_probe_check(const TableSlot *__restrict__ table, int w, uint32_t nSlots, const uint32_t *__restrict__ hashes, uint32_t n,
+                                           uint32_t *__restrict__ firstCnt)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t first, cnt;
+  table_probe(table, w, nSlots, hashes[i], first, cnt);
+  firstCnt[2 * (size_t)i] = first; firstCnt[2 * (size_t)i + 1] = cnt;
+}
+
+// TEST INFRASTRUCTURE (ani_index_links_check below): the same-hash links of an entry as the L2 kernels read them
+static __global__ void k_index_links_check(DupLinks dup, const uint32_t *__restrict__ entries, uint32_t n, int32_t *__restrict__ out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = entries[i];
+  out[3 * (size_t)i] = dup_flag(dup, j) ? 1 : 0; out[3 * (size_t)i + 1] = dup_prev(dup, j); out[3 * (size_t)i + 2] = dup_next(dup, j);
+}
+
 }  // namespace anih
 
 extern "C" {
@@ -537,6 +557,93 @@ int ani_sketch_from_records(ani_ctx *ctx, const ani_params_t *p, const void *dev
   const int rc = add_chunks(ctx, sk, parts);
   if (rc != ANI_OK) { free_sketch_device(sk); delete sk; return rc; }
   *out = sk;
+  return ANI_OK;
+}
+
+// TEST INFRASTRUCTURE (declared in host/engine.hpp, not part of include/ani_abi.h, no product code calls them): the arrays of one index
+// chunk copied to the host, table_probe over a list of hashes, and dup_flag / dup_prev / dup_next over a list of entries.
+// tests/test_index_build.py builds sketches from synthetic records (ani_sketch_from_records above) and holds every array to its definition.
+int ani_index_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, int what, void *out, uint64_t capBytes, uint64_t *bytes)
+{
+  if (!ctx || !sk || !bytes || sk->ctx != ctx) return fail(ANI_ERR_ARG, "ani_index_check: bad argument");
+  if (chunk < 0 || (size_t)chunk >= sk->chunks.size()) return fail(ANI_ERR_ARG, "ani_index_check: chunk %d of %zu", chunk, sk->chunks.size());
+  const IndexChunk *ch = sk->chunks[(size_t)chunk];
+  if (!ch->resident) return fail(ANI_ERR_ARG, "ani_index_check: the index arrays of chunk %d are not resident", chunk);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t n = ch->n, bitWords = (n + 31) / 32 + 1;
+  const int32_t cmw = sk->params.fragLen - (sk->params.windowSize - 1) - (sk->params.kmerSize - 1);
+  const uint64_t info[12] = {n, ch->nUnique, ch->nDup, ch->tableSlots, ch->tableAlloc, ch->totalPosBins, (uint64_t)ch->nContigs, (uint64_t)ch->c0,
+      (uint64_t)ch->nGenomes, (uint64_t)ch->g0, (uint64_t)(n && cmw >= 1 && cmw + 2 <= (int32_t)ani::kWinMask), bitWords};
+  const void *src = nullptr; size_t sz = 0;
+  switch (what) {
+    case 0: src = info; sz = sizeof info; break;
+    case 1: src = ch->sHash; sz = n * 4; break;
+    case 2: src = ch->sSW; sz = n * 8; break;
+    case 3: src = ch->mWin; sz = n * 4; break;
+    case 4: src = ch->dupBits; sz = bitWords * 4; break;
+    case 5: src = ch->dupList; sz = (size_t)ch->nDup * 8; break;
+    case 6: src = ch->contigFirstMin; sz = ((size_t)ch->nContigs + 1) * 4; break;
+    case 7: src = ch->posBase; sz = ((size_t)ch->nContigs + 1) * 4; break;
+    case 8: src = ch->posSample; sz = ((size_t)ch->totalPosBins + 1) * 4; break;
+    case 9: src = ch->table; sz = (size_t)ch->tableAlloc * sizeof(ani::TableSlot); break;
+    default: return fail(ANI_ERR_ARG, "ani_index_check: no array %d", what);
+  }
+  *bytes = sz;
+  if (!out || !sz) return ANI_OK;
+  if (capBytes < sz) return fail(ANI_ERR_ARG, "ani_index_check: array %d takes %zu bytes, the buffer has %llu", what, sz, (unsigned long long)capBytes);
+  if (!src) return fail(ANI_ERR_INTERNAL, "ani_index_check: array %d of a resident chunk is missing", what);
+  if (what == 0) { memcpy(out, src, sz); return ANI_OK; }
+  HIP_TRY(hipStreamSynchronize(ctx->stream2)); HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
+  return ANI_OK;
+}
+
+int ani_index_probe_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *hashes, size_t n, uint32_t *firstCnt)
+{
+  if (!ctx || !sk || sk->ctx != ctx || (n && (!hashes || !firstCnt)) || n > ((size_t)1 << 24)) return fail(ANI_ERR_ARG, "ani_index_probe_check: bad argument");
+  if (chunk < 0 || (size_t)chunk >= sk->chunks.size()) return fail(ANI_ERR_ARG, "ani_index_probe_check: chunk %d of %zu", chunk, sk->chunks.size());
+  const IndexChunk *ch = sk->chunks[(size_t)chunk];
+  if (!ch->resident) return fail(ANI_ERR_ARG, "ani_index_probe_check: the index arrays of chunk %d are not resident", chunk);
+  if (!n) return ANI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  uint32_t *dIn = nullptr, *dOut = nullptr;
+  HIP_TRY(pool_malloc((void **)&dIn, n * 4));
+  hipError_t e = pool_malloc((void **)&dOut, n * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(dIn, hashes, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_index_probe_check, dim3(grid_for(n, 256, 65536)), dim3(256), 0, ctx->stream, (const ani::TableSlot *)ch->table,
+                       sk->params.windowSize, ch->tableSlots, (const uint32_t *)dIn, (uint32_t)n, dOut);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(firstCnt, dOut, n * 8, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  pool_free(dIn); if (dOut) pool_free(dOut);
+  HIP_TRY(e); HIP_TRY(e2);
+  return ANI_OK;
+}
+
+int ani_index_links_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *entries, size_t n, int32_t *out)
+{
+  if (!ctx || !sk || sk->ctx != ctx || (n && (!entries || !out)) || n > ((size_t)1 << 24)) return fail(ANI_ERR_ARG, "ani_index_links_check: bad argument");
+  if (chunk < 0 || (size_t)chunk >= sk->chunks.size()) return fail(ANI_ERR_ARG, "ani_index_links_check: chunk %d of %zu", chunk, sk->chunks.size());
+  const IndexChunk *ch = sk->chunks[(size_t)chunk];
+  if (!ch->resident) return fail(ANI_ERR_ARG, "ani_index_links_check: the index arrays of chunk %d are not resident", chunk);
+  for (size_t i = 0; i < n; i++) if (entries[i] >= ch->n) return fail(ANI_ERR_ARG, "ani_index_links_check: entry %u of %u", entries[i], ch->n);
+  if (!n) return ANI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  uint32_t *dIn = nullptr; int32_t *dOut = nullptr;
+  HIP_TRY(pool_malloc((void **)&dIn, n * 4));
+  hipError_t e = pool_malloc((void **)&dOut, n * 12);
+  if (e == hipSuccess) e = hipMemcpyAsync(dIn, entries, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    const ani::DupLinks dup{ch->dupList, ch->nDup, ch->dupBits};
+    hipLaunchKernelGGL(k_index_links_check, dim3(grid_for(n, 256, 65536)), dim3(256), 0, ctx->stream, dup, (const uint32_t *)dIn, (uint32_t)n, dOut);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, n * 12, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  pool_free(dIn); if (dOut) pool_free(dOut);
+  HIP_TRY(e); HIP_TRY(e2);
   return ANI_OK;
 }
 

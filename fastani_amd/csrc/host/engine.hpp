@@ -67,6 +67,21 @@ extern "C" int ani_prim_device_scan(ani_ctx *ctx, const int32_t *in, uint32_t *o
 extern "C" int ani_reduce_check(ani_ctx *ctx, const ani_sketch *sk, const ani_mapping_t *mappings, size_t n, const int32_t *queryFragStart,
                                 int32_t nQuery, int32_t genomeBase, int32_t firstQueryId, ani_cgi_t **out, size_t *m);
 
+// TEST INFRASTRUCTURE (engine_index.hip, beside ani_sketch_from_records; not part of include/ani_abi.h, no product code calls them): one
+// index chunk as build_chunk_index left it.  ani_index_check copies array `what` of chunk `chunk` to the host buffer `out` of
+// capBytes bytes (out = NULL: the size only) and returns its size in *bytes:
+//   0 info: uint64 {n, nUnique, nDup, tableSlots, allocated table slots, totalPosBins, nContigs, c0, nGenomes, g0, window links built, words of dupBits}
+//   1 sHash  2 sSW  3 mWin  4 dupBits  5 dupList  6 contigFirstMin (nContigs + 1)  7 posBase (nContigs + 1)  8 posSample (totalPosBins + 1)
+//   9 the probe table: every allocated slot (12 bytes each), the sentinel and the slot behind it included
+// ani_index_probe_check runs table_probe — one thread per hash, with the table, window size and tableSlots that l1_probe gets — over
+// n host hashes: firstCnt[2 i] = first, firstCnt[2 i + 1] = cnt.  ani_index_links_check runs dup_flag / dup_prev / dup_next over the
+// chunk's DupLinks for n host entry numbers (each below the chunk's n): out[3 i .. 3 i + 2] = flag, prev, next.  A chunk whose index
+// arrays are not resident is ANI_ERR_ARG.  tests/test_index_build.py holds all three to numpy definitions.
+struct ani_sketch;
+extern "C" int ani_index_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, int what, void *out, uint64_t capBytes, uint64_t *bytes);
+extern "C" int ani_index_probe_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *hashes, size_t n, uint32_t *firstCnt);
+extern "C" int ani_index_links_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *entries, size_t n, int32_t *out);
+
 namespace ani { struct TableSlot; }
 
 namespace anih {
@@ -460,6 +475,7 @@ struct IndexChunk {
   uint32_t *dupBits = nullptr; uint64_t *dupList = nullptr; uint32_t nDup = 0;   // same-hash links of near duplicates (index.hpp: DupLinks)
   uint64_t *sSW = nullptr;
   ani::TableSlot *table = nullptr; uint32_t tableSlots = 0;     // order-preserving probe table over the distinct hashes (index.hpp)
+  uint32_t tableAlloc = 0;                 // slots allocated: the end clusters may run past tableSlots, then the sentinel and one empty slot
   int32_t *contigFirstMin = nullptr, *contigGenome = nullptr;
   uint32_t *contigBinBase = nullptr, *genomeBinStart = nullptr, *posBase = nullptr, *posSample = nullptr;
   uint32_t totalBins = 0, totalPosBins = 0;
