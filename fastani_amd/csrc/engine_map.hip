@@ -35,16 +35,19 @@ void launch_l2_sim_a(unsigned grid, hipStream_t s, const L2FastArgs &fa, const i
 void launch_l2_sim_b(unsigned grid, hipStream_t s, const L2FastArgs &fa, const int32_t *list, const unsigned int *listCount);
 static_assert(kL1FilterMinHits == 300 && kL1HitCapMax == 4080, "defaults of ani_ctx::l1FilterMin / l1LdsMax (host/engine.hpp)");
 
-// L1 + L2 + identity for the fragments of `fs` against ONE index chunk; candidates and their results stay in the context's
-// buffers (ocFrag/ocSeq [chunk-local seqIds]/refStart/idBits/l2Best) for the reducer or the mapping export.
-int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, int32_t *nCandOut)
+// What the L1 half did with the fragments of one call (ani_l1_check reports it; map_stage does not ask)
+struct L1Route { unsigned long long tiny = 0, small = 0, mid = 0, big = 0; int attempts = 0; };
+
+// The L1 half of map_stage: processing order, probe, class launches, the pool retry loop, scan and k_l1_order.  The ordered candidates
+// stay in ocFrag / ocSeq [chunk-local seqIds] / ocStart / ocEnd; *fragOrderOut is the processing order the L2 half needs (nullptr: ascending).
+static int l1_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, const int32_t **fragOrderOut, int32_t *nCandOut,
+                    L1Route *route = nullptr)
 {
   if (ctx->timerPending.size() > 4096) flush_timers(ctx);
   const ani_params_t &p = set->params;
-  const int k = p.kmerSize, w = p.windowSize, L = p.fragLen;
+  const int w = p.windowSize, L = p.fragLen;
   const size_t nF = (size_t)fs.nFrag;
-  const int maxS = fs.maxS;
-  *nCandOut = 0;
+  *nCandOut = 0; *fragOrderOut = nullptr;
   if (nF == 0) return ANI_OK;
   unsigned long long host[CNT_N];
   host[CNT_QPOOL] = fs.nHashes;
@@ -220,6 +223,7 @@ int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, 
     HIP_TRY(hipGetLastError());
     TRY(read_counters(ctx, host));
     if (attempt == 0) { hitsTotal = host[CNT_HITS]; probeOverflow = (uint32_t)host[CNT_NEG]; ctx->counters.l1MidFragments += nMid; }
+    if (route) route->attempts = attempt + 1;
     if (ctx->poolMaxStripe[POOL_CAND] <= stripe_cap(ccap)) break;
     if (attempt > 2) return fail(ANI_ERR_INTERNAL, "candidate pool did not converge");
     if (ccap >= kCandLimit) return fail(ANI_ERR_LIMIT, "more than 2^31 L1 candidates in one query batch");
@@ -237,6 +241,7 @@ int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, 
     ctx->candPerFrag = mx;
   // the next small batch starts from what this one needed (bounded: 1 GB of pool)
   } else ctx->smallBatchCandCap = std::min<uint64_t>(grown_cap(ctx->poolMaxStripe[POOL_CAND]), (uint64_t)1 << 26);
+  if (route) { route->tiny = nTiny; route->small = nSmall; route->mid = nMid; route->big = nBig; }
   if (probeOverflow != 0)                      // k_l1_probe: hit counts and offsets are 32-bit per fragment
     return fail(ANI_ERR_LIMIT, "%u query fragment(s) have 2^31 or more seed hits in one index chunk (a hash with ~10^9 occurrences: low-complexity / "
                                "repetitive references); use the reference's -s sanity check or a smaller ANI_MAX_INDEX_MINIMIZERS", probeOverflow);
@@ -254,10 +259,20 @@ int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, 
       HIP_TRY(hipGetLastError());
     }
   }
-  *nCandOut = (int32_t)nCand;
+  *nCandOut = (int32_t)nCand; *fragOrderOut = fragOrder;
   ctx->counters.l1Candidates += nCand;
-  if (nCand == 0) return ANI_OK;
+  return ANI_OK;
+}
 
+// The L2 half of map_stage: sliding MinHash and identity for the nCand > 0 ordered candidates l1_stage left; results in
+// refStart / idBits / l2Best.
+static int l2_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, const int32_t *fragOrder, uint64_t nCand)
+{
+  const ani_params_t &p = set->params;
+  const int k = p.kmerSize, w = p.windowSize, L = p.fragLen;
+  const size_t nF = (size_t)fs.nFrag;
+  const int maxS = fs.maxS;
+  unsigned long long host[CNT_N];
   // ---- L2 ----
   TRY(ctx->l2Best.ensure(nCand * 4)); TRY(ctx->l2First.ensure(nCand * 4)); TRY(ctx->l2Last.ensure(nCand * 4));
   TRY(ctx->refStart.ensure(nCand * 4)); TRY(ctx->idBits.ensure(nCand * 4));
@@ -422,6 +437,16 @@ int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, 
   ctx->counters.l2WindowEntriesB += host[CNT_ENTRIES_B]; ctx->counters.l2QueryHashesB += host[CNT_SUMQ_B];
   ctx->counters.l2SlowLimit += host[CNT_REASON + 1]; ctx->counters.l2SlowDup += host[CNT_REASON + 2]; ctx->counters.l2SlowOverflow += host[CNT_REASON + 3];
   return ANI_OK;
+}
+
+// L1 + L2 + identity for the fragments of `fs` against ONE index chunk; candidates and their results stay in the context's
+// buffers (ocFrag/ocSeq [chunk-local seqIds]/refStart/idBits/l2Best) for the reducer or the mapping export.
+int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, int32_t *nCandOut)
+{
+  const int32_t *fragOrder = nullptr;
+  TRY(l1_stage(ctx, set, sk, fs, &fragOrder, nCandOut));
+  if (*nCandOut == 0) return ANI_OK;
+  return l2_stage(ctx, set, sk, fs, fragOrder, (uint64_t)*nCandOut);
 }
 
 // 1-way / 2-way / mean (computeCoreIdentity.hpp:214-297) for the candidates map_stage left in the context's buffers, against one
@@ -2125,6 +2150,54 @@ int ani_reduce_check(ani_ctx *ctx, const ani_sketch *skc, const ani_mapping_t *m
   TRY(reduce_mapping_list(ctx, sk, mappings, n, queryFragStart, nQuery, fs, firstQueryId, &rows));
   *m = rows.n; *out = rows.release();
   if (!*out) return fail(ANI_ERR_NOMEM, "host allocation failed");
+  return ANI_OK;
+}
+
+// TEST INFRASTRUCTURE (declared in host/engine.hpp, not part of include/ani_abi.h, no product code calls it): the L1 half of map_stage
+// (l1_stage above: processing order, k_l1_probe, the class launches, the pool retry loop, the scan, k_l1_order) run once for the kept
+// fragment set `f` against index chunk `chunk`, which is made resident as the map path makes it (ensure_chunk) after
+// upload_luts(sk, f's maxS).  info = {nFrag, nCand, poolSize, tiny, small, mid, big fragments of this call, attempts of the candidate pool};
+// *out = one malloc'ed block of 32-bit words (ani_free releases it), *words long:
+//   ocFrag, ocSeq, ocStart, ocEnd [nCand each: what the L2 half would receive], fragHits [nFrag], probeFirst, probeCnt [poolSize each,
+//   aligned with the hash pool; 0xffffffff where k_l1_probe wrote nothing].
+// A null argument, a chunk that does not exist or cannot be made resident, a fragment set of another context's device or of other
+// parameters (k, window, fragLen) are ANI_ERR_ARG; what l1_stage itself reports (ANI_ERR_LIMIT) comes back as it is.
+// tests/test_l1.py holds every array to the sequential definition of computeMap.hpp:283-354.
+int ani_l1_check(ani_ctx *ctx, const ani_sketch *skc, int32_t chunk, const ani_fragset *f, uint64_t *info, int32_t **out, size_t *words)
+{
+  if (!ctx || !skc || !f || !info || !out || !words || skc->ctx != ctx) return fail(ANI_ERR_ARG, "ani_l1_check: bad argument");
+  if (f->device != ctx->device) return fail(ANI_ERR_ARG, "ani_l1_check: fragment set lives on device %d, context on %d", f->device, ctx->device);
+  ani_sketch *sk = const_cast<ani_sketch *>(skc);
+  if (chunk < 0 || (size_t)chunk >= sk->chunks.size()) return fail(ANI_ERR_ARG, "ani_l1_check: chunk %d of %zu", chunk, sk->chunks.size());
+  if (f->params.kmerSize != sk->params.kmerSize || f->params.windowSize != sk->params.windowSize || f->params.fragLen != sk->params.fragLen)
+    return fail(ANI_ERR_ARG, "ani_l1_check: fragment set and sketch were built with different parameters");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FragSet &fs = f->fs;
+  TRY(upload_luts(sk, fs.maxS));
+  if (ensure_chunk(sk, (size_t)chunk) != ANI_OK || !sk->chunks[chunk]->resident)
+    return fail(ANI_ERR_ARG, "ani_l1_check: the index arrays of chunk %d cannot be made resident", chunk);
+  const size_t nF = (size_t)fs.nFrag, nP = (size_t)fs.poolSize;
+  // the probe results as l1_stage sizes them, marked where the probe does not write
+  TRY(ctx->probeFirst.ensure((nP + 1) * 4)); TRY(ctx->probeCnt.ensure((nP + 1) * 4));
+  HIP_TRY(hipMemsetAsync(ctx->probeFirst.p, 0xff, (nP + 1) * 4, ctx->stream)); HIP_TRY(hipMemsetAsync(ctx->probeCnt.p, 0xff, (nP + 1) * 4, ctx->stream));
+  const int32_t *fragOrder = nullptr; int32_t nCand = 0; L1Route route;
+  TRY(l1_stage(ctx, sk, sk->chunks[chunk], fs, &fragOrder, &nCand, &route));
+  const size_t nC = (size_t)nCand, total = 4 * nC + nF + 2 * nP;
+  int32_t *host = (int32_t *)malloc((total ? total : 1) * 4);
+  if (!host) return fail(ANI_ERR_NOMEM, "host allocation failed");
+  hipError_t e = hipSuccess;
+  const void *src[7] = {ctx->ocFrag.p, ctx->ocSeq.p, ctx->ocStart.p, ctx->ocEnd.p, ctx->fragHits.p, ctx->probeFirst.p, ctx->probeCnt.p};
+  const size_t len[7] = {nC, nC, nC, nC, nF, nP, nP};
+  size_t at = 0;
+  for (int i = 0; i < 7; i++) {
+    if (len[i] && e == hipSuccess) e = hipMemcpyAsync(host + at, src[i], len[i] * 4, hipMemcpyDeviceToHost, ctx->stream);
+    at += len[i];
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { free(host); HIP_TRY(e); }
+  info[0] = nF; info[1] = nC; info[2] = nP; info[3] = route.tiny; info[4] = route.small; info[5] = route.mid; info[6] = route.big;
+  info[7] = (uint64_t)route.attempts;
+  *out = host; *words = total;
   return ANI_OK;
 }
 

@@ -82,6 +82,17 @@ extern "C" int ani_index_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk
 extern "C" int ani_index_probe_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *hashes, size_t n, uint32_t *firstCnt);
 extern "C" int ani_index_links_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const uint32_t *entries, size_t n, int32_t *out);
 
+// TEST INFRASTRUCTURE (engine_map.hip, beside ani_reduce_check; not part of include/ani_abi.h, no product code calls it): the L1 half of
+// map_stage — processing order, k_l1_probe, the class launches, the candidate pool's retry loop, the scan and k_l1_order — run once for
+// the kept fragment set `f` against index chunk `chunk` of `sk` (made resident as the map path makes it, after upload_luts(sk, maxS of f)).
+//   info[8] = {nFrag, nCand, poolSize, fragments routed to the wave kernel, to class S, to class M, to the batched path, pool attempts}
+//   *out    = malloc'ed 32-bit words (ani_free), *words of them: ocFrag, ocSeq, ocStart, ocEnd [nCand each, as the L2 half would receive
+//             them], fragHits [nFrag], probeFirst, probeCnt [poolSize each; 0xffffffff where the probe wrote nothing]
+// A null argument, a chunk that does not exist or cannot be made resident, a fragment set on another device or of other parameters are
+// ANI_ERR_ARG.  tests/test_l1.py holds the arrays to the sequential definition of computeMap.hpp:283-354.
+struct ani_fragset;
+extern "C" int ani_l1_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const ani_fragset *f, uint64_t *info, int32_t **out, size_t *words);
+
 namespace ani { struct TableSlot; }
 
 namespace anih {
@@ -405,7 +416,7 @@ struct ani_ctx {
   int l1FilterMin = 300 /* ani::kL1FilterMinHits */, l1LdsMax = 4080 /* ani::kL1HitCapMax */;
   // first guess of the same-hash link list (env ANI_TEST_DUP_PAIR_CAP, tests: forces the rerun)
   uint64_t dupPairCap = 0;
-  // env ANI_TEST_L1_TINY=0: fragments with <= 64 seed hits take the workgroup path like the others
+  // env ANI_TEST_L1_TINY=0: fragments with <= 256 seed hits (ani::kL1HitCapTiny) take the workgroup path like the others
   bool l1Tiny = true;
   // the L2 simulation on the side stream, beside the next chunk's ranges / codes kernels (env ANI_TEST_L2_OVERLAP=0 switches it off; see the L2 loop)
   bool l2Overlap = true;

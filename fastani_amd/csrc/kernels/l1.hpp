@@ -9,7 +9,8 @@
 // H <= HCAP seed hits,
 // gather the hit runs into LDS as 64-bit (seqId<<32 | wpos) keys, bitonic sort in registers (common.hpp: block_sort), flag valid runs, compact, flag
 // group heads by neighbour comparison (run starts/ends are non-decreasing, so "overlaps the previous candidate" only needs
-// the previous valid run), scan, emit.  Two LDS classes (<= 2048 hits: 6 workgroups per CU; <= 4096: 3), the larger driven by a fragment list.  Fragments
+// the previous valid run), scan, emit.  Two LDS classes (S: <= 2032 hits, 20 KiB of LDS, 7 workgroups per CU; M: <= 4080 hits, 40 KiB, 4 per CU —
+// the constants below), the larger driven by a fragment list; fragments with at most 256 hits are finished by one wave each (k_l1_tiny).  Fragments
 // with more hits take the batched global-memory path: k_l1_big_offsets / _gather -> device radix sort -> k_l1_big_unpack / _candidates.
 #pragma once
 #include "common.hpp"
@@ -69,7 +70,7 @@ struct L1Args {
   L1FragDesc *fragDesc;                 // [nFrag] by position in the processing order (k_l1_probe writes, the gather kernels read)
   int filterMinHits;                    // kL1FilterMinHits (ANI_TEST_L1_FILTER_MIN: test knob; 0 = always filter, large = never)
   int ldsHitCap;                        // fragments with more seed hits take the batched global-memory path (<= kL1HitCapMax; ANI_TEST_L1_LDS_MAX)
-  int tinyPath;                         // fragments with <= 64 seed hits are finished by one wave (l1_tiny; ANI_TEST_L1_TINY=0 switches it off: A/B and tests)
+  int tinyPath;                         // fragments with <= 256 seed hits (kL1HitCapTiny) are finished by one wave (l1_tiny; ANI_TEST_L1_TINY=0 switches it off: A/B and tests)
 };
 
 // Counter indices of a hit's two tiles for the noise filter (k_l1): tiles of width 2^shift, the second tiling offset by half a tile.
@@ -109,7 +110,7 @@ __device__ __forceinline__ bool l1_head(const uint64_t *hits, const VT *V, int j
 }
 
 // Sorted hits -> candidate regions of one fragment (computeMap.hpp:313-354).  hits/V may live in LDS or in global memory.
-// VT: type of the run indices in V (uint16_t in class S: its hits number <= 2048)
+// VT: type of the run indices in V (uint16_t in both LDS classes: their hits number <= 4080)
 template <class VT>
 __device__ inline void l1_emit_candidates(const L1Args &a, int f, int s, int H, int m /* minimumHits of s, :301 */, const uint64_t *hits, VT *V,
                                           int *ws, unsigned long long *sBasePtr)
@@ -267,14 +268,14 @@ static __global__ __launch_bounds__(kTPB) void k_l1_probe(L1Args a)
       if (H64) atomicAdd(stat_slot(a.sumHits), H64);
       if (tooMany) atomicAdd(a.overflowCount, 1u);
       else if (s[q] > 0) {
-        // fragments of the larger LDS classes are listed so that their 48 / 96 KiB workgroups are only launched for them
+        // fragments of the larger LDS class are listed so that its 40 KiB workgroups are only launched for them
         if (s[q] <= kL1MaxS && H <= a.ldsHitCap) {
           // (a long sketch with a handful of hits: the wave kernel)
           // (positions in the processing order: fragDesc)
           if (H > kL1HitCapSmall || (s[q] > kL1SmallMaxS && !(H <= 4 * kWave && a.tinyPath))) a.midList[atomicAdd(a.midCount, 1u)] = i0 + q;
           // (striped statistics counters: the host launches k_l1_tiny if there are any,
           else if (H > 0 && H <= 4 * kWave && a.tinyPath) atomicAdd(stat_slot(a.tinyCount), 1ull);
-          // and k_l1<0, 2048> over a list instead of over every fragment if there are few)
+          // and k_l1<0, 2032> over a list instead of over every fragment if there are few)
           else if (H > 0) atomicAdd(stat_slot(a.smallCount), 1ull);
         } else a.bigList[atomicAdd(a.bigCount, 1u)] = f;         // beyond every LDS class: global-memory path
       }
@@ -287,7 +288,7 @@ static __global__ __launch_bounds__(kTPB) void k_l1_probe(L1Args a)
 // genome — every visit of a fragment to a foreign reference shard of a multi-GPU run, to a foreign index chunk of a large database:
 // ~240 probes, a few chance hits (minimizer hashes crowd the low end of the 32-bit range), rarely a candidate.  Such a fragment is a
 // chain of five dependent round trips to memory and nothing else, so what counts is how many of them a CU has in flight: 32 here,
-// 6 in the workgroup kernel (24 KiB of LDS per fragment), which took 17.5 ms for the 1.67 M fragment visits of one rank of an 8-GPU
+// 6 in the workgroup kernel of the time (24 KiB of LDS per fragment; 20 KiB and 7 now), which took 17.5 ms for the 1.67 M fragment visits of one rank of an 8-GPU
 // job, 1.46 M of them of this kind (profiles/r04g_bench_sim8.json.log).
 //   gather: lane l takes the sketch hashes l, l + 64, ...; the order of the hits does not matter (they are sorted next), so a wave
 //           scan of the lanes' hit counts places them;  sort: 1, 2 or 4 keys per lane in registers over the lane-exchange network
@@ -377,15 +378,15 @@ static __global__ __launch_bounds__(kTPB) void k_l1_tiny(L1Args a)
   if (i >= a.nFrag) return;
   const L1FragDesc d = l1_frag_desc(a.fragDesc + i);
   const int f = wave_uniform(d.f), s = wave_uniform((int32_t)(d.sm & 0xffffu)), H = wave_uniform(d.H);
-  // the workgroup classes / the batched path (same class predicate as k_l1_probe: H > ldsHitCap is bigList's) / nothing to do (k_l1<0, 2048> or k_l1_list
+  // the workgroup classes / the batched path (same class predicate as k_l1_probe: H > ldsHitCap is bigList's) / nothing to do (k_l1<0, 2032> or k_l1_list
   // writes the zero counts)
   if (s <= 0 || s > kL1MaxS || H <= 0 || H > kL1HitCapTiny || H > a.ldsHitCap) return;
   l1_tiny(a, f, s, H, wave_uniform(d.off), wave_uniform((int32_t)(d.sm >> 16)), hits[wv], V[wv]);
 }
 
-// The fragments of class S (256 < H <= 2048) as a list, for batches in which they are the exception: a fragment set that meets a
+// The fragments of class S (256 < H <= 2032) as a list, for batches in which they are the exception: a fragment set that meets a
 // foreign reference shard or index chunk has no seed hit at all for most of its fragments, and a workgroup that finds nothing to do
-// still costs its dispatch — ~9 ns each with 24 KiB of LDS to reserve, 13 of the 17 ms k_l1<0, 2048> took for the 1.67 M fragment
+// still costs its dispatch — ~9 ns each with the 24 KiB of LDS class S then reserved (20 KiB now), 13 of the 17 ms k_l1<0, 2032> (then <0, 2048>) took for the 1.67 M fragment
 // visits of one rank of an 8-GPU job (profiles/r04h_bench_sim8.json.log).  One thread per fragment: fragments without hits get their
 // zero counts here, class-S fragments are appended in order (one atomic per workgroup).
 static __global__ __launch_bounds__(kTPB) void k_l1_list(L1Args a, int32_t *__restrict__ list, unsigned int *__restrict__ cursor)
@@ -414,11 +415,11 @@ static __global__ __launch_bounds__(kTPB) void k_l1_list(L1Args a, int32_t *__re
 
 // Pass 2: gather + sort + candidate regions for the fragments whose hit count is in (HLO, HCAP]; everything in LDS.
 // (Measured and removed in round 3: class M "in two walks" — the hit runs read twice, first only to feed the filter's counters,
-// then to stage the survivors in the 24 KiB of class S instead of 48 KiB.  1000 references: class M 4.8 -> 4.3 ms per launch; 10 000
+// then to stage the survivors in the 24 KiB that class S had then instead of 48 KiB (the classes have 20 and 40 KiB now).  1000 references: class M 4.8 -> 4.3 ms per launch; 10 000
 // references, where class M is mostly noise and the gather is all there is: L1 stage 83 -> 87 ms per 300 queries.  One read wins.
 // Also measured and removed: 32-bit sort keys (rank of the contig among the fragment's distinct contigs << posBits | wpos: 3 instead of
 // 7 instructions per key and lane-exchange stage).  The ranks need a hash set of the contig ids in LDS, the distinct ids sorted, a
-// look-up per hit — five more barrier-separated phases and 20 more registers (5 instead of 6 workgroups per CU): k_l1<0,2048> went
+// look-up per hit — five more barrier-separated phases and 20 more registers (5 instead of 6 workgroups per CU): class S, then k_l1<0,2048>, went
 // from 30.7 to 41.2 ms per step, bit-exact.)
 template <int HLO, int HCAP>
 static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a, const int32_t *__restrict__ list)
