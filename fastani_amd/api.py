@@ -42,6 +42,8 @@ CGI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("countSeq", 
 SIGPAIR_DT = np.dtype([("a", "<i4"), ("b", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
 NEIGHBOR_DT = np.dtype([("neighbor", "<i4"), ("shared", "<i4"), ("size", "<i4"), ("identity", "<f4")])
 BINPROFILE_DT = np.dtype([("count", "<u4"), ("minIdentity", "<f4"), ("maxIdentity", "<f4"), ("reserved", "<u4"), ("sum", "<u8")])
+FRAGDIST_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("minIdentity", "<f4"), ("q1", "<f4"), ("median", "<f4"),
+                        ("q3", "<f4"), ("maxIdentity", "<f4"), ("sum", "<u8")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -139,6 +141,9 @@ def _bind(lib):
         "ani_sketch_profile_bins": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "ani_sketch_profile_read": (C.c_int, [vp, vp, vp]),
         "ani_sketch_profile_end": (C.c_int, [vp]),
+        "ani_sketch_fragdist_begin": (C.c_int, [vp, C.c_float, C.c_int32, vp, C.c_int32]),
+        "ani_sketch_fragdist_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_fragdist_end": (C.c_int, [vp]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
@@ -931,6 +936,26 @@ class Sketch:
 
     def profile_end(self):
         self.e._chk(self.e.lib.ani_sketch_profile_end(self.h))
+
+    def fragdist_begin(self, edges=(), min_identity=0.0, min_fragments=1):
+        """start (or restart) the per-pair fragment identity distributions: every mapping call that reduces against this sketch appends a
+        record per pair whose row has countSeq >= min_fragments and identity >= min_identity; `edges`: up to 63 ascending class edges
+        in [0, 100] for the records' histograms (ani_sketch_fragdist_begin)"""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
+        self.e._chk(self.e.lib.ani_sketch_fragdist_begin(self.h, float(min_identity), int(min_fragments), e.ctypes.data if len(e) else None, len(e)))
+        self._fragdist_classes = len(e) + 1
+
+    def fragdist_take(self):
+        """-> (records FRAGDIST_DT[n], hist uint32[n, nEdges + 1]) appended since fragdist_begin or the last take, in row order; empties the list"""
+        rp, hp, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_fragdist_take(self.h, C.byref(rp), C.byref(hp), C.byref(n)))
+        k = self._fragdist_classes
+        rec = self.e._take(rp, n.value, FRAGDIST_DT)
+        hist = self.e._take(hp, n.value * k, np.dtype("<u4")).reshape(n.value, k)
+        return rec, hist
+
+    def fragdist_end(self):
+        self.e._chk(self.e.lib.ani_sketch_fragdist_end(self.h))
 
     def profile_layout(self):
         """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and

@@ -14,6 +14,7 @@
 #include "kernels/l2.hpp"
 #include "kernels/reduce.hpp"
 #include "kernels/profile.hpp"
+#include "kernels/fragdist.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
 #include "kernels/nj.hpp"
@@ -449,6 +450,86 @@ int map_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &fs, 
   return l2_stage(ctx, set, sk, fs, fragOrder, (uint64_t)*nCandOut);
 }
 
+// The fragment distributions of one (sub-batch, index chunk) (kernels/fragdist.hpp), from the bin table and the
+// pair table k_pair_reduce has just completed: gate -> flags -> scan -> list, then the records piece by piece (fragDistPiece records
+// per launch: the device holds one piece, whatever the number of gated pairs) through page-locked memory into ctx->fdStage, where
+// collect_rows finds them.  Only while the sketch has the mode on.
+static int fragdist_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const PairArgs &pa)
+{
+  const size_t nPairs = (size_t)pa.nQuery * (size_t)sk->nGenomes;
+  if (nPairs == 0) return ANI_OK;
+  FragDistArgs fa;
+  fa.nQuery = pa.nQuery; fa.nRefGenomes = sk->nGenomes; fa.bins = pa.bins; fa.binsPerQuery = pa.binsPerQuery; fa.genomeBinStart = sk->genomeBinStart;
+  fa.pairCount = pa.pairCount; fa.pairIdentity = pa.pairIdentity; fa.outStride = pa.outStride; fa.outCol0 = pa.outCol0;
+  fa.minIdBits = set->fdMinIdBits; fa.minFragments = set->fdMinFragments; fa.genomeBase = sk->g0; fa.nEdges = set->fdEdges;
+  memcpy(fa.edgeBits, set->fdEdgeBits, sizeof fa.edgeBits);
+  TRY(ctx->fdFlags.ensure(nPairs * 4)); TRY(ctx->fdOff.ensure(nPairs * 4));
+  hipLaunchKernelGGL(k_fragdist_flags, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, fa, ctx->fdFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t total = 0;
+  TRY(device_scan(ctx, ctx->fdFlags.as<int32_t>(), ctx->fdOff.as<uint32_t>(), (uint32_t)nPairs, &total));
+  if (total == 0) return ANI_OK;
+  TRY(ctx->fdList.ensure((size_t)total * 4));
+  hipLaunchKernelGGL(k_fragdist_list, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, (uint32_t)nPairs, (const int32_t *)ctx->fdFlags.as<int32_t>(),
+                     (const uint32_t *)ctx->fdOff.as<uint32_t>(), ctx->fdList.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  const size_t width = (size_t)set->fdEdges + 1, piece = std::min<size_t>(ctx->fragDistPiece, (size_t)total);
+  TRY(ctx->fdRec.ensure(piece * sizeof(FragDistRec))); TRY(ctx->fdHist.ensure(piece * width * 4));
+  uint8_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, piece * (sizeof(FragDistRec) + width * 4), (void **)&host));
+  FragDistBuf &st = ctx->fdStage;
+  if (!st.reserve((size_t)total, width)) return fail(ANI_ERR_NOMEM, "host allocation of %llu fragment distribution records failed", (unsigned long long)total);
+  static_assert(sizeof(FragDistRec) == sizeof(ani_fragdist_t), "the device record is the ABI's");
+  for (size_t first = 0; first < (size_t)total; first += piece) {
+    const size_t n = std::min<size_t>(piece, (size_t)total - first);
+    hipLaunchKernelGGL(k_fragdist_records, dim3((unsigned)n), dim3(kWave), 0, ctx->stream, fa, (const uint32_t *)ctx->fdList.as<uint32_t>(), (uint32_t)first,
+                       (uint32_t)n, ctx->fdRec.as<FragDistRec>(), ctx->fdHist.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, ctx->fdRec.p, n * sizeof(FragDistRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(host + piece * sizeof(FragDistRec), ctx->fdHist.p, n * width * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // (into fresh pages: through the host pool, 135 MB of records and histograms per 1000 x 1000 call took one thread longer than the kernels)
+    const size_t slice = 4096, at = st.n;
+    parallel_for((n + slice - 1) / slice, (uint64_t)n * (sizeof(FragDistRec) + width * 4), [&](size_t i) {
+      const size_t r0 = i * slice, m = std::min(slice, n - r0);
+      memcpy(st.rec + at + r0, host + r0 * sizeof(FragDistRec), m * sizeof(FragDistRec));
+      memcpy(st.hist + (at + r0) * width, host + piece * sizeof(FragDistRec) + r0 * width * 4, m * width * 4);
+    });
+    st.n += n;
+  }
+  return ANI_OK;
+}
+
+// The staged records of a sub-batch (`in`: chunk by chunk, per chunk queries ascending, per query references ascending) in (query,
+// reference) order, appended to `out` with the ids `patch` gives them.  `ordered`: they come from one chunk and are in that order
+// already (they are moved, or copied in one piece); else a stable distribution by the query's slot in the sub-batch.
+template <class SlotOf, class Patch>
+static int fragdist_distribute(FragDistBuf &in, size_t width, size_t nq, bool ordered, SlotOf slot_of, Patch patch, FragDistBuf *out)
+{
+  const size_t n = in.n;
+  if (n == 0) return ANI_OK;
+  const size_t at = out->n;
+  if (ordered && at == 0) out->swap(in);
+  else {
+    if (!out->reserve(n, width)) return fail(ANI_ERR_NOMEM, "host allocation of %zu fragment distribution records failed", n);
+    if (ordered) { memcpy(out->rec + at, in.rec, n * sizeof(ani_fragdist_t)); memcpy(out->hist + at * width, in.hist, n * width * 4); }
+    else {
+      std::vector<size_t> start(nq + 1, 0);
+      for (size_t r = 0; r < n; r++) start[slot_of(in.rec[r]) + 1]++;
+      for (size_t q = 0; q < nq; q++) start[q + 1] += start[q];
+      for (size_t r = 0; r < n; r++) {
+        const size_t to = at + start[slot_of(in.rec[r])]++;
+        out->rec[to] = in.rec[r];
+        memcpy(out->hist + to * width, in.hist + r * width, width * 4);
+      }
+    }
+    out->n = at + n;
+  }
+  for (size_t r = at; r < at + n; r++) patch(out->rec[r]);
+  in.clear();
+  return ANI_OK;
+}
+
 // 1-way / 2-way / mean (computeCoreIdentity.hpp:214-297) for the candidates map_stage left in the context's buffers, against one
 // index chunk; the (count, identity) results go to the chunk's column block of the dense [nQuery][nRefGenomes] table in ctx->rows.
 // `compact`: the table holds this chunk's genomes only ([nQuery][chunk genomes]; a streamed set is reduced and read back chunk by chunk)
@@ -488,6 +569,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     if (binsPerQuery) hipLaunchKernelGGL(k_profile_bins, dim3(grid_for(binsPerQuery, kTPB)), dim3(kTPB), 0, ctx->stream, fa);
     hipLaunchKernelGGL(k_profile_queries, dim3(grid_for((size_t)sk->nGenomes, kTPB)), dim3(kTPB), 0, ctx->stream, fa);
   }
+  if (set->fragdist) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(fragdist_stage(ctx, set, sk, pa));
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -495,12 +580,21 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 
 // the dense table of a sub-batch (all chunks reduced) -> rows in (query, reference genome) order, appended to `rows`
 // (`block`: the table is the compact one of that chunk — reference genome = block->g0 + column)
+// (fdOut: where the sub-batch's fragment distribution records go while that mode is on — default: the sketch's pending list)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
-    const int32_t *queryIds = nullptr)
+    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
   if (nPairs == 0) return ANI_OK;
+  if (set->fragdist) {
+    // the records reduce_stage staged come chunk by chunk with the query's index in the sub-batch: the rows' order and ids
+    const int32_t base = set->refIdBase;
+    TRY(fragdist_distribute(ctx->fdStage, (size_t)set->fdEdges + 1, (size_t)nQuery, block || set->chunks.size() == 1,
+        [](const ani_fragdist_t &r) { return (size_t)r.qryGenomeId; },
+        [&](ani_fragdist_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
+        fdOut ? fdOut : &set->fdPending));
+  }
   uint32_t *dense = nullptr;
   TRY(pinned_buffer(ctx, 1, nPairs * 8 + 8, (void **)&dense));
   HIP_TRY(hipMemcpyAsync(dense, ctx->rows.p, nPairs * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -592,6 +686,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   }
   TRY(upload_luts(sk, maxS));
   std::vector<RowBuf> part(sub.size());
+  std::vector<FragDistBuf> fdPart(sk->fragdist ? sub.size() : 0);       // the fragment distribution records take the rows' way
   for (size_t c = 0; c < sk->chunks.size(); c++) {
     TRY(ensure_chunk(sk, c));
     IndexChunk *ch = sk->chunks[c];
@@ -600,7 +695,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       int32_t nCand = 0;
       TRY(map_stage(ctx, sk, ch, sb.v, &nCand));
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
-      TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds));
+      TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -630,6 +725,13 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       });
       rows->n += total;
     }
+  }
+  for (size_t i = 0; i < fdPart.size(); i++) {
+    const int32_t q0 = sub[i].firstQueryId, nq = sub[i].g1 - sub[i].g0;
+    const int32_t *ids = sub[i].queryIds;
+    TRY(fragdist_distribute(fdPart[i], (size_t)sk->fdEdges + 1, (size_t)nq, sk->chunks.size() == 1, [&](const ani_fragdist_t &r) {
+          return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
+        [](ani_fragdist_t &) {}, &sk->fdPending));
   }
   return ANI_OK;
 }
@@ -2105,9 +2207,10 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
+  if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
   return ANI_OK;
 }
 
@@ -2346,6 +2449,52 @@ int ani_sketch_profile_end(ani_sketch *sk)
   HIP_TRY(hipStreamSynchronize(sk->ctx->stream));        // a reduce_stage of an earlier call may still be adding
   for (IndexChunk *ch : sk->chunks) free_chunk_profile(ch);
   sk->profile = false;
+  return ANI_OK;
+}
+
+// ---- fragment identity distributions (ani_abi.h: ani_sketch_fragdist_begin) ----
+int ani_sketch_fragdist_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, const float *edges, int32_t nEdges)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  if (nEdges < 0 || nEdges > kFragDistMaxEdges) return fail(ANI_ERR_ARG, "%d class edges: 0 to %d are taken", nEdges, kFragDistMaxEdges);
+  if (nEdges > 0 && !edges) return fail(ANI_ERR_ARG, "null edges");
+  uint32_t eb[kFragDistMaxEdges] = {0};
+  for (int32_t e = 0; e < nEdges; e++) {
+    if (!(edges[e] >= 0.0f && edges[e] <= 100.0f)) return fail(ANI_ERR_ARG, "edge %d (%g) outside [0, 100]", e, (double)edges[e]);
+    if (e && !(edges[e] > edges[e - 1])) return fail(ANI_ERR_ARG, "edge %d (%g) is not above its predecessor", e, (double)edges[e]);
+    if (edges[e] != 0.0f) memcpy(&eb[e], &edges[e], 4);            // -0.0 counts as 0
+  }
+  memcpy(&sk->fdMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->fdMinIdBits = 0;                    // -0.0 counts as 0
+  sk->fdMinFragments = (uint32_t)minFragments;
+  sk->fdEdges = nEdges; memcpy(sk->fdEdgeBits, eb, sizeof eb);
+  sk->fdPending.clear(); sk->ctx->fdStage.clear();
+  sk->fragdist = true;
+  return ANI_OK;
+}
+
+int ani_sketch_fragdist_take(ani_sketch *sk, ani_fragdist_t **rec, uint32_t **hist, size_t *n)
+{
+  if (!sk || !rec || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->fragdist) return fail(ANI_ERR_ARG, "ani_sketch_fragdist_take without ani_sketch_fragdist_begin");
+  *rec = nullptr; *n = 0;
+  if (hist) *hist = nullptr;
+  FragDistBuf &pd = sk->fdPending;
+  if (pd.n == 0) { pd.clear(); return ANI_OK; }
+  *rec = pd.rec; *n = pd.n;                     // the buffers themselves: ani_free releases them
+  if (hist) *hist = pd.hist; else free(pd.hist);
+  pd.rec = nullptr; pd.hist = nullptr; pd.n = pd.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_fragdist_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->fragdist) return fail(ANI_ERR_ARG, "ani_sketch_fragdist_end without ani_sketch_fragdist_begin");
+  sk->fdPending.clear(); sk->ctx->fdStage.clear();
+  sk->fragdist = false;
   return ANI_OK;
 }
 

@@ -394,6 +394,31 @@ inline unsigned grid_for(size_t n, unsigned block = 256, unsigned maxBlocks = 0x
 }  // namespace anih
 using namespace anih;
 
+// records of the per-pair fragment distributions on the host (ani_sketch_fragdist_begin; kernels/fragdist.hpp): rec[i] with its
+// `width` = nEdges + 1 histogram counters at hist[i * width]; malloc'ed and geometrically grown like the result rows, so that
+// ani_sketch_fragdist_take hands the two buffers to the caller as they are (ani_free releases them)
+struct FragDistBuf {
+  ani_fragdist_t *rec = nullptr; uint32_t *hist = nullptr; size_t n = 0, cap = 0;
+  FragDistBuf() = default;
+  FragDistBuf(const FragDistBuf &) = delete;
+  FragDistBuf &operator=(const FragDistBuf &) = delete;
+  ~FragDistBuf() { clear(); }
+  bool reserve(size_t extra, size_t width)              // room for `extra` more records; false: out of memory (the buffer stays as it was)
+  {
+    if (n + extra <= cap && rec && hist) return true;
+    const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 1024);
+    void *r = realloc(rec, want * sizeof(ani_fragdist_t));
+    if (!r) return false;
+    rec = (ani_fragdist_t *)r;
+    void *h = realloc(hist, want * width * 4);
+    if (!h) return false;
+    hist = (uint32_t *)h; cap = want;
+    return true;
+  }
+  void swap(FragDistBuf &o) { std::swap(rec, o.rec); std::swap(hist, o.hist); std::swap(n, o.n); std::swap(cap, o.cap); }
+  void clear() { free(rec); free(hist); rec = nullptr; hist = nullptr; n = cap = 0; }
+};
+
 // =====================================================================================================
 struct ani_ctx {
   int device = 0;
@@ -464,6 +489,11 @@ struct ani_ctx {
   DevBuf l2Ranges[2], l2CodeCount[2], l2CodeOff[2], l2Codes[2], l2SlowFlag[2], l2ClassList[2], l2Order[2], l2LenHist[2];   // two chunk sets (see the L2 loop)
   DevBuf l2SlowList;
   DevBuf bins, queryFragments, rows;
+  // fragment distributions (only while a sketch has them on): the gate's flags, offsets and list of a (sub-batch, chunk), one piece of
+  // records on the device, and the records reduce_stage has staged for the sub-batch's collect_rows (query = index in the sub-batch)
+  DevBuf fdFlags, fdOff, fdList, fdRec, fdHist;
+  FragDistBuf fdStage;
+  uint32_t fragDistPiece = 1u << 18;      // records per launch and copy (env ANI_TEST_FRAGDIST_PIECE, tests)
 };
 
 // One index over a contiguous run of reference genomes: < 2^31 minimizers, 32-bit indices, chunk-local seqIds.  A reference set
@@ -521,6 +551,10 @@ struct ani_sketch {
   int32_t *dMinHits = nullptr, *dMinShared = nullptr; uint32_t *dIdLUT = nullptr; int dLutMaxS = 0;
   // conservation profile (ani_sketch_profile_begin .. _end): reduce_stage adds every sub-batch to the chunks' accumulators while it is on
   bool profile = false; uint32_t profMinIdBits = 0, profMinFragments = 1;
+  // fragment distributions (ani_sketch_fragdist_begin .. _end): reduce_stage makes a record per gated pair while they are on, collect_rows
+  // gives the records the rows' ids and order and appends them to `fdPending`, which ani_sketch_fragdist_take hands over
+  bool fragdist = false; uint32_t fdMinIdBits = 0, fdMinFragments = 1; int32_t fdEdges = 0; uint32_t fdEdgeBits[63] = {0};
+  FragDistBuf fdPending;
 };
 
 namespace anih {

@@ -86,6 +86,9 @@ struct Options {
   float sketchGraph = 0.0f;                            // --sketchGraph T: the .sketchgraph file, the pairs at an estimate >= T, streamed (0 = off)
   bool profile = false;                                // --profile: the .profile file, per-bin conservation of every reference over the queries
   float profileMinANI = 95.0f; int profileMinFragments = 50;   // --profileMinANI, --profileMinFragments: the pairs that count (ani_sketch_profile_begin's gate)
+  bool fragDist = false;                               // --fragDist: the .fragdist file, the spread of the fragment identities behind every -o line
+  std::vector<float> fragDistEdges;                    // --fragDistEdges: the class edges of its histograms (default_fragdist_edges)
+  float fragDistMinANI = 0.0f; int fragDistMinFragments = 1;   // --fragDistMinANI, --fragDistMinFragments: the pairs that get a line (ani_sketch_fragdist_begin's gate)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
   // the uses of the genome sketches that go through the pair step (ani_signature_pairs) and its 65 536 genomes
@@ -110,6 +113,7 @@ struct Options {
     "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
+    "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -167,6 +171,15 @@ struct Options {
     "                 queries.  Works with every input mode [disabled by default]\n"
     "     --profileMinANI <value>  a query genome counts for a reference from this ANI on (0 < value <= 100) [default : 95]\n"
     "     --profileMinFragments <value>  ... and from this many matched fragments on (the fourth column of the output; >= 1) [default : 50]\n"
+    "     --fragDist  also write <output>.fragdist: the spread of the fragment identities an ANI value is the mean of.  Line 1 is\n"
+    "             #edges<TAB>e0,e1,...; then, for every line of the output file, in its order: query, reference, fragments, and the\n"
+    "             minimum, first quartile, median, third quartile and maximum of the pair's reciprocal best fragment identities, then\n"
+    "             h0,h1,...: the number of them in the classes [.., e0), [e0, e1), ..., [eK, ..].  A recombined pair or a contaminated\n"
+    "             assembly shows as a second mode.  Host memory: 40 + 4 x classes bytes per pair until the file is written (172 bytes\n"
+    "             with the default edges: 17 GB for the 10^8 pairs of a 10 000 x 10 000 run; the two gates below are the remedy)\n"
+    "     --fragDistEdges <a,b,...>  at most 63 ascending class edges in [0, 100] [default : 70,71,...,99,99.5,99.9]\n"
+    "     --fragDistMinANI <value>  only the pairs from this ANI on get a line (0 <= value <= 100) [default : 0, every line of the output]\n"
+    "     --fragDistMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -203,6 +216,7 @@ Options parse(int argc, char **argv)
   std::string refName, refList, qryName, qryList;
   bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
   bool profileMinANI = false, profileMinFragments = false;
+  bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -248,6 +262,22 @@ Options parse(int argc, char **argv)
       if (!(o.profileMinANI > 0.0f && o.profileMinANI <= 100.0f)) { std::cerr << "ERROR, --profileMinANI takes an ANI in (0, 100]" << std::endl; exit(1); } }
     else if (a == "--profileMinFragments") { o.profileMinFragments = atoi(need(i)); profileMinFragments = true;
       if (o.profileMinFragments < 1) { std::cerr << "ERROR, --profileMinFragments takes a count of at least 1" << std::endl; exit(1); } }
+    else if (a == "--fragDist") o.fragDist = true;
+    else if (a == "--fragDistEdges") { fragDistEdges = true; o.fragDistEdges.clear();
+      const std::string v = need(i);
+      bool ok = !v.empty();
+      for (size_t at = 0; ok && at <= v.size();) {
+        const size_t to = std::min(v.find(',', at), v.size());
+        const std::string t = v.substr(at, to - at);
+        char *end = nullptr; const float e = t.empty() ? 0.0f : strtof(t.c_str(), &end);
+        ok = !t.empty() && end && !*end && e >= 0.0f && e <= 100.0f && (o.fragDistEdges.empty() || e > o.fragDistEdges.back()) && o.fragDistEdges.size() < 63;
+        o.fragDistEdges.push_back(e); at = to + 1;
+      }
+      if (!ok) { std::cerr << "ERROR, --fragDistEdges takes at most 63 ascending values in [0, 100], separated by commas" << std::endl; exit(1); } }
+    else if (a == "--fragDistMinANI") { o.fragDistMinANI = (float)atof(need(i)); fragDistMinANI = true;
+      if (!(o.fragDistMinANI >= 0.0f && o.fragDistMinANI <= 100.0f)) { std::cerr << "ERROR, --fragDistMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--fragDistMinFragments") { o.fragDistMinFragments = atoi(need(i)); fragDistMinFragments = true;
+      if (o.fragDistMinFragments < 1) { std::cerr << "ERROR, --fragDistMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
     else if (a == "-v" || a == "--version") version = true;
     else if (a == "--saveSketch") o.saveSketch = need(i);
@@ -270,6 +300,10 @@ Options parse(int argc, char **argv)
     exit(1); }
   if (profileMinANI && !o.profile) { std::cerr << "ERROR, --profileMinANI needs --profile" << std::endl; exit(1); }
   if (profileMinFragments && !o.profile) { std::cerr << "ERROR, --profileMinFragments needs --profile" << std::endl; exit(1); }
+  if (fragDistEdges && !o.fragDist) { std::cerr << "ERROR, --fragDistEdges needs --fragDist" << std::endl; exit(1); }
+  if (fragDistMinANI && !o.fragDist) { std::cerr << "ERROR, --fragDistMinANI needs --fragDist" << std::endl; exit(1); }
+  if (fragDistMinFragments && !o.fragDist) { std::cerr << "ERROR, --fragDistMinFragments needs --fragDist" << std::endl; exit(1); }
+  if (o.fragDist && !fragDistEdges) { for (int e = 70; e <= 99; e++) o.fragDistEdges.push_back((float)e); o.fragDistEdges.push_back(99.5f); o.fragDistEdges.push_back(99.9f); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
   if (qryName.empty() && qryList.empty()) { std::cerr << "Provide query file (s)\n"; exit(1); }
   if (!o.refSketch.empty()) {
@@ -674,6 +708,36 @@ struct ProfileTable {
 };
 ProfileTable g_profile;
 
+// --fragDist: the fragment identity distributions (ani_sketch_fragdist_begin) of the pairs, keyed by (query, reference) file index.  Begun
+// and drained where the profile is: a reference sketch holds the records of the queries mapped against it until it goes.
+struct FragDistTable {
+  bool on = false; float minANI = 0.0f; int32_t minFragments = 1; std::vector<float> edges;
+  std::vector<ani_fragdist_t> rec; std::vector<uint32_t> hist;
+  std::unordered_map<uint64_t, size_t> at;                 // (query << 32 | reference) -> record
+  void init(const Options &o) { on = o.fragDist; minANI = o.fragDistMinANI; minFragments = o.fragDistMinFragments; edges = o.fragDistEdges; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_fragdist_begin(sk, minANI, minFragments, edges.data(), (int32_t)edges.size())) {
+      std::cerr << "ERROR, ani_sketch_fragdist_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  // what the mapping calls left in `sk`: genome g of the sketch is reference refOf(g); the query ids are the run's own
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_fragdist_t *r = nullptr; uint32_t *h = nullptr; size_t n = 0;
+    if (ani_sketch_fragdist_take(sk, &r, &h, &n)) { std::cerr << "ERROR, ani_sketch_fragdist_take: " << ani_last_error() << std::endl; exit(1); }
+    const size_t w = edges.size() + 1;
+    for (size_t i = 0; i < n; i++) {
+      ani_fragdist_t e = r[i]; e.refGenomeId = (int32_t)refOf(e.refGenomeId);
+      at[((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId] = rec.size();
+      rec.push_back(e);
+    }
+    hist.insert(hist.end(), h, h + n * w);
+    ani_free(r); ani_free(h);
+  }
+};
+FragDistTable g_fragdist;
+
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
 // no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
@@ -945,7 +1009,12 @@ struct Streaming {
   }
 
   // --profile: what the queries left in the shard's sketch, before the sketch goes (shard-local genome -> reference file index)
-  void take_profile(int d) { const int32_t g0 = shard[d].g0; g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); }); }
+  void take_profile(int d)
+  {
+    const int32_t g0 = shard[d].g0;
+    g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_fragdist.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+  }
 
   // every device sketches its run of the reference slices into its shard's tables and record parts (all-vs-all: the query sets too)
   void sketch_references()
@@ -1039,7 +1108,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) g_profile.begin(shard[d].sk);
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1270,7 +1339,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1326,6 +1395,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
       }
     }
     g_profile.take(sk, ap.fragLen, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });      // the split's genome g is reference refIdx[g]
+    g_fragdist.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
   for (int sp = 0; sp < nSplits; sp++) std::cerr << "INFO [thread " << sp << "], skch::main, ready to exit the loop" << std::endl;
@@ -1405,6 +1475,28 @@ void write_profile(const Options &o, int32_t fragLen)
         else f.out << "\tNA\tNA\tNA\n";
       }
     }
+  }
+}
+
+// ---- .fragdist: "#edges", then per line of the output file whose pair passed the gate, in its order: query, reference, fragments, minimum,
+// first quartile, median, third quartile, maximum (the identities as the output file prints them) and the class counts
+void write_fragdist(const Options &o, const std::vector<ani_cgi_t> &rows, const Trusted &trusted)
+{
+  BufferedFile f(o.out + ".fragdist");
+  f.out << "#edges\t";
+  for (size_t e = 0; e < g_fragdist.edges.size(); e++) f.out << (e ? "," : "") << g_fragdist.edges[e];
+  f.out << "\n";
+  const size_t w = g_fragdist.edges.size() + 1;
+  for (auto &e : rows) {
+    if (!trusted(e)) continue;
+    const auto it = g_fragdist.at.find(((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId);
+    if (it == g_fragdist.at.end()) continue;                // the pair did not pass the gate
+    const ani_fragdist_t &x = g_fragdist.rec[it->second];
+    f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << x.count << "\t" << x.minIdentity << "\t" << x.q1 << "\t" << x.median << "\t"
+          << x.q3 << "\t" << x.maxIdentity << "\t";
+    const uint32_t *h = g_fragdist.hist.data() + it->second * w;
+    for (size_t c = 0; c < w; c++) f.out << (c ? "," : "") << h[c];
+    f.out << "\n";
   }
 }
 
@@ -1917,7 +2009,7 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o);
+  g_profile.init(o); g_fragdist.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
   Startup su(o, m, ap);
@@ -1937,6 +2029,7 @@ int main(int argc, char **argv)
   trace("rows ordered");
   write_txt(o, res.rows, trusted);
   if (o.profile) write_profile(o, ap.fragLen);
+  if (o.fragDist) write_fragdist(o, res.rows, trusted);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

@@ -354,6 +354,40 @@ int ani_sketch_profile_bins(const ani_sketch *sk, uint64_t *nBins);
 int ani_sketch_profile_read(const ani_sketch *sk, ani_binprofile_t *bins /* [nBins] */, uint32_t *queries /* [nGenomes] */);
 int ani_sketch_profile_end(ani_sketch *sk);
 
+/* ---- per-pair fragment identity distributions (no counterpart in the reference: an ANI value is the mean of the pair's cells, and the
+ * spread behind it is dropped with the bin table).  Between begin and end every call that reduces against the
+ * sketch (the calls of the profile's rule 5; ani_map_query adds nothing) appends one record per contributing pair to a list on the host,
+ * which take hands over.  Everything is integer or bit pattern.
+ *  1. Values.  For a pair (q, g), V is the multiset of the non-empty cells of g's bins for q (a cell: the profile's rule 2);
+ *     count = |V| = the row's countSeq.
+ *  2. Gate: the profile's rule 3.  The pair contributes iff it has a row, countSeq >= minFragments and bits(identity) >= bits(minIdentity);
+ *     minIdentity in [0, 100] (-0.0 counts as 0), minFragments >= 1.
+ *  3. Classes.  nEdges in 0 .. 63 finite floats in [0, 100], strictly ascending (-0.0 counts as 0).  class(x) = the number of edges e with
+ *     edges[e] <= x: a float comparison and, for these values, one of bit patterns; no arithmetic touches x.  A record has nEdges + 1
+ *     counters hist[class]; they add up to count.  A value bit-equal to an edge belongs to the class above the edge.
+ *  4. Order statistics, on the bit patterns.  With V sorted ascending as v[0 .. count - 1]: minIdentity = v[0], q1 = v[(count - 1) / 4],
+ *     median = v[(count - 1) / 2], q3 = v[3 (count - 1) / 4], maxIdentity = v[count - 1], the divisions integer: each of the five is a
+ *     value some cell holds.
+ *  5. Sum.  sum = the sum over V of fix(v), the profile's fix(x) = (uint64_t) llrint((double) x * 2^20).
+ *  6. Ids and order.  qryGenomeId and refGenomeId are those of the ani_cgi_t row the same call returned for the pair (firstQueryId, the
+ *     query ids of a merged set and ani_sketch_set_ref_id_base included).  The records of one call come in the order of that call's rows,
+ *     restricted to the pairs that pass the gate; calls follow each other in call order.
+ *  7. Rows are untouched: with the mode on or off every mapping call returns the same rows, bit for bit.  The profile and the
+ *     distribution can be on together and do not see each other.
+ *  8. Determinism.  Nothing depends on schedule, sub-batch size, index chunking, residency (resident, chunked, streamed) or piece sizes.
+ * begin starts (a second begin drops what is pending and takes the new gate and edges).  take hands over everything appended since begin
+ * or the last take and empties the list: rec[n], and, unless `hist` is NULL, hist[n][nEdges + 1]; both are released with ani_free; with
+ * n = 0 both come back NULL.  A caller that drains after every mapping call holds one call's worth (40 + 4 (nEdges + 1) bytes per record
+ * of host memory until taken).  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null sketch (or rec or n), a gate outside its
+ * ranges (NaN included), nEdges outside 0 .. 63, null edges with nEdges > 0, an edge that is NaN, infinite, outside [0, 100] or not above
+ * its predecessor, take or end without a begin; a refused begin leaves a running distribution as it was.  ANI_ERR_NOMEM: the records do
+ * not fit the host.  After a call that failed while reducing, the pending list is unspecified until the next begin. */
+typedef struct { int32_t refGenomeId, qryGenomeId; uint32_t count;
+                 float minIdentity, q1, median, q3, maxIdentity; uint64_t sum; } ani_fragdist_t;  /* 40 bytes */
+int ani_sketch_fragdist_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, const float *edges, int32_t nEdges);
+int ani_sketch_fragdist_take(ani_sketch *sk, ani_fragdist_t **rec, uint32_t **hist, size_t *n);
+int ani_sketch_fragdist_end(ani_sketch *sk);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
