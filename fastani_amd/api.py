@@ -44,6 +44,7 @@ NEIGHBOR_DT = np.dtype([("neighbor", "<i4"), ("shared", "<i4"), ("size", "<i4"),
 BINPROFILE_DT = np.dtype([("count", "<u4"), ("minIdentity", "<f4"), ("maxIdentity", "<f4"), ("reserved", "<u4"), ("sum", "<u8")])
 FRAGDIST_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("minIdentity", "<f4"), ("q1", "<f4"), ("median", "<f4"),
                         ("q3", "<f4"), ("maxIdentity", "<f4"), ("sum", "<u8")])
+HIT_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("querySeqId", "<i4"), ("identity", "<f4")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -144,6 +145,9 @@ def _bind(lib):
         "ani_sketch_fragdist_begin": (C.c_int, [vp, C.c_float, C.c_int32, vp, C.c_int32]),
         "ani_sketch_fragdist_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_fragdist_end": (C.c_int, [vp]),
+        "ani_sketch_hits_begin": (C.c_int, [vp, C.c_float, C.c_int32]),
+        "ani_sketch_hits_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_hits_end": (C.c_int, [vp]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
@@ -956,6 +960,21 @@ class Sketch:
 
     def fragdist_end(self):
         self.e._chk(self.e.lib.ani_sketch_fragdist_end(self.h))
+
+    def hits_begin(self, min_identity=0.0, min_fragments=1):
+        """start (or restart) the reciprocal best-hit records: every mapping call that reduces against this sketch appends one record per
+        non-empty cell of every pair whose row has countSeq >= min_fragments and identity >= min_identity (ani_sketch_hits_begin)"""
+        self.e._chk(self.e.lib.ani_sketch_hits_begin(self.h, float(min_identity), int(min_fragments)))
+
+    def hits_take(self):
+        """-> HIT_DT[n]: the records appended since hits_begin or the last take, pairs in row order, a pair's records in bin order; empties
+        the list"""
+        rp, n = C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_hits_take(self.h, C.byref(rp), C.byref(n)))
+        return self.e._take(rp, n.value, HIT_DT)
+
+    def hits_end(self):
+        self.e._chk(self.e.lib.ani_sketch_hits_end(self.h))
 
     def profile_layout(self):
         """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and

@@ -163,6 +163,7 @@ int ani_init(int device, ani_ctx **out)
   if (const char *ev = getenv("ANI_TEST_L1_HIT_LIMIT")) { const long long v = atoll(ev);
     if (v >= 1) c->l1HitLimit = std::min<uint64_t>((uint64_t)v, 0x7ffffff0ull); }
   if (const char *ev = getenv("ANI_TEST_FRAGDIST_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->fragDistPiece = (uint32_t)v; }
+  if (const char *ev = getenv("ANI_TEST_HITS_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->hitsPiece = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CAND_POOL_MIN")) { const long long v = atoll(ev); if (v >= 1) c->candPoolMin = (uint64_t)v; }
   if (const char *ev = getenv("ANI_TEST_L1_BIG_GROUP_HITS")) { const long long v = atoll(ev); if (v >= 1) c->l1BigGroupHits = (uint64_t)v; }
   if (const char *ev = getenv("ANI_TEST_L1_BIG_GROUP_FRAGS")) { const long long v = atoll(ev); if (v >= 1) c->l1BigGroupFrags = (uint64_t)v; }
@@ -194,7 +195,8 @@ void ani_shutdown(ani_ctx *c)
                     &c->l2Ranges[1], &c->l2CodeCount[1], &c->l2CodeOff[1], &c->l2Codes[1], &c->l2SlowFlag[1], &c->l2ClassList[1], &c->l2Order[1],
                         &c->l2LenHist[1], &c->l2SlowList, &c->l2Best,
                     &c->l2First, &c->l2Last, &c->refStart, &c->idBits, &c->keepFlags, &c->keepOff, &c->mapOut, &c->bins, &c->queryFragments, &c->rows,
-                    &c->fdFlags, &c->fdOff, &c->fdList, &c->fdRec, &c->fdHist};
+                    &c->fdFlags, &c->fdOff, &c->fdList, &c->fdRec, &c->fdHist,
+                    &c->hitOwner, &c->hitFlags, &c->hitOff, &c->hitList, &c->hitCount, &c->hitRecOff, &c->hitRec, &c->hitQSeq};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->timerEvents) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; i++) { if (c->evSimA[i]) (void)hipEventDestroy(c->evSimA[i]); if (c->evSetDone[i]) (void)hipEventDestroy(c->evSetDone[i]);

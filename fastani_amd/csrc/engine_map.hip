@@ -15,6 +15,7 @@
 #include "kernels/reduce.hpp"
 #include "kernels/profile.hpp"
 #include "kernels/fragdist.hpp"
+#include "kernels/hits.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
 #include "kernels/nj.hpp"
@@ -530,6 +531,102 @@ static int fragdist_distribute(FragDistBuf &in, size_t width, size_t nq, bool or
   return ANI_OK;
 }
 
+// The best-hit records of one (sub-batch, index chunk) (kernels/hits.hpp), from the bin table, the pair table
+// k_pair_reduce has just completed and the candidates k_oneway_bins read: gate -> flags -> scan, owner -> claim over the candidates,
+// the list, a second scan over the listed pairs' countSeq for the record offsets, then the records piece by piece (about hitsPiece records
+// per launch; a piece ends at a pair border and a larger pair is a piece of its own) through page-locked memory into ctx->hitStage,
+// where collect_rows finds them.  Only while the sketch has the mode on.
+static int hits_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const OneWayArgs &wa, const PairArgs &pa, const FragSet &fs)
+{
+  const size_t nPairs = (size_t)pa.nQuery * (size_t)sk->nGenomes, nBins = pa.binsPerQuery * (size_t)pa.nQuery;
+  if (nPairs == 0 || wa.nCand == 0 || nBins == 0) return ANI_OK;
+  if (!fs.fragQSeq) return fail(ANI_ERR_ARG, "best-hit records need the fragments' querySeqId");
+  TRY(ctx->hitOwner.ensure(nBins * 4));                // on top of the bin table: one more uint32 per cell while the mode is on
+  HitsArgs ha;
+  ha.w = wa; ha.fragQSeq = fs.fragQSeq; ha.nQuery = pa.nQuery; ha.nRefGenomes = sk->nGenomes; ha.genomeBinStart = sk->genomeBinStart;
+  ha.pairCount = pa.pairCount; ha.pairIdentity = pa.pairIdentity; ha.outStride = pa.outStride; ha.outCol0 = pa.outCol0;
+  ha.minIdBits = set->hitMinIdBits; ha.minFragments = set->hitMinFragments; ha.genomeBase = sk->g0; ha.seqBase = sk->c0;
+  ha.owner = ctx->hitOwner.as<uint32_t>();
+  TRY(ctx->hitFlags.ensure(nPairs * 4)); TRY(ctx->hitOff.ensure(nPairs * 4));
+  hipLaunchKernelGGL(k_hits_flags, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ha, ctx->hitFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t listed = 0, total = 0;
+  TRY(device_scan(ctx, ctx->hitFlags.as<int32_t>(), ctx->hitOff.as<uint32_t>(), (uint32_t)nPairs, &listed));
+  if (listed == 0) return ANI_OK;
+  HIP_TRY(hipMemsetAsync(ctx->hitOwner.p, 0, nBins * 4, ctx->stream));
+  hipLaunchKernelGGL(k_hits_owner, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, ha);
+  hipLaunchKernelGGL(k_hits_claim, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, ha);
+  TRY(ctx->hitList.ensure((size_t)listed * 4)); TRY(ctx->hitCount.ensure((size_t)listed * 4)); TRY(ctx->hitRecOff.ensure((size_t)listed * 4));
+  hipLaunchKernelGGL(k_hits_list, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ha, (const int32_t *)ctx->hitFlags.as<int32_t>(),
+                     (const uint32_t *)ctx->hitOff.as<uint32_t>(), ctx->hitList.as<uint32_t>(), ctx->hitCount.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  // (every record is a candidate of its own, so the sum stays below 2^31; the limit is the ABI's)
+  TRY(device_scan(ctx, ctx->hitCount.as<int32_t>(), ctx->hitRecOff.as<uint32_t>(), (uint32_t)listed, &total, 0xfffffff0ull));
+  if (total == 0) return ANI_OK;
+  std::vector<uint32_t> recOff((size_t)listed + 1);
+  HIP_TRY(hipMemcpyAsync(recOff.data(), ctx->hitRecOff.p, (size_t)listed * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  recOff[(size_t)listed] = (uint32_t)total;
+  // pieces: [a, b) of the list with recOff[b] - recOff[a] <= hitsPiece, or b = a + 1
+  std::vector<size_t> cut(1, 0);
+  size_t largest = 0;
+  for (size_t a = 0; a < (size_t)listed;) {
+    size_t b = a + 1;
+    while (b < (size_t)listed && (uint64_t)recOff[b + 1] - recOff[a] <= ctx->hitsPiece) b++;
+    largest = std::max<size_t>(largest, recOff[b] - recOff[a]);
+    cut.push_back(b); a = b;
+  }
+  TRY(ctx->hitRec.ensure(largest * sizeof(HitRec)));
+  uint8_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, largest * sizeof(HitRec), (void **)&host));
+  HitBuf &st = ctx->hitStage;
+  if (!st.reserve((size_t)total)) return fail(ANI_ERR_NOMEM, "host allocation of %llu best-hit records failed", (unsigned long long)total);
+  static_assert(sizeof(HitRec) == sizeof(ani_hit_t), "the device record is the ABI's");
+  for (size_t i = 0; i + 1 < cut.size(); i++) {
+    const size_t a = cut[i], b = cut[i + 1], n = recOff[b] - recOff[a];
+    hipLaunchKernelGGL(k_hits_records, dim3((unsigned)(b - a)), dim3(kWave), 0, ctx->stream, ha, (const uint32_t *)ctx->hitList.as<uint32_t>(),
+                       (const uint32_t *)ctx->hitRecOff.as<uint32_t>(), (uint32_t)a, (uint32_t)(b - a), recOff[a], ctx->hitRec.as<HitRec>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, ctx->hitRec.p, n * sizeof(HitRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t slice = 8192, at = st.n;
+    parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(HitRec), [&](size_t j) {
+      const size_t r0 = j * slice, m = std::min(slice, n - r0);
+      memcpy(st.rec + at + r0, host + r0 * sizeof(HitRec), m * sizeof(HitRec));
+    });
+    st.n += n;
+  }
+  return ANI_OK;
+}
+
+// The staged records of a sub-batch (`in`: chunk by chunk, per chunk pairs in (query, reference) order, per pair in bin order) in (query,
+// reference) order, appended to `out` with the ids `patch` gives them: fragdist_distribute for groups of any length — the distribution
+// by the query's slot is stable, so a pair's records stay together and in their order.
+template <class SlotOf, class Patch>
+static int hits_distribute(HitBuf &in, size_t nq, bool ordered, SlotOf slot_of, Patch patch, HitBuf *out)
+{
+  const size_t n = in.n;
+  if (n == 0) return ANI_OK;
+  const size_t at = out->n, slice = 65536;
+  if (ordered && at == 0) out->swap(in);
+  else {
+    if (!out->reserve(n)) return fail(ANI_ERR_NOMEM, "host allocation of %zu best-hit records failed", n);
+    if (ordered) parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(ani_hit_t), [&](size_t j) {      // (into fresh pages: see fragdist_stage)
+        memcpy(out->rec + at + j * slice, in.rec + j * slice, std::min(slice, n - j * slice) * sizeof(ani_hit_t)); });
+    else {
+      std::vector<size_t> start(nq + 1, 0);
+      for (size_t r = 0; r < n; r++) start[slot_of(in.rec[r]) + 1]++;
+      for (size_t q = 0; q < nq; q++) start[q + 1] += start[q];
+      for (size_t r = 0; r < n; r++) out->rec[at + start[slot_of(in.rec[r])]++] = in.rec[r];
+    }
+    out->n = at + n;
+  }
+  parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(ani_hit_t), [&](size_t j) {
+    for (size_t r = at + j * slice, r1 = at + std::min(n, (j + 1) * slice); r < r1; r++) patch(out->rec[r]); });
+  in.clear();
+  return ANI_OK;
+}
+
 // 1-way / 2-way / mean (computeCoreIdentity.hpp:214-297) for the candidates map_stage left in the context's buffers, against one
 // index chunk; the (count, identity) results go to the chunk's column block of the dense [nQuery][nRefGenomes] table in ctx->rows.
 // `compact`: the table holds this chunk's genomes only ([nQuery][chunk genomes]; a streamed set is reduced and read back chunk by chunk)
@@ -545,8 +642,9 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
   {
   StageTimer tm(ctx, &ctx->counters.msReduce);
   e1 = hipMemsetAsync(ctx->bins.p, 0, (nBins ? nBins : 1) * 4, ctx->stream);
+  OneWayArgs a;
+  a.nCand = 0;
   if (nCand) {
-    OneWayArgs a;
     a.nCand = nCand; a.candFrag = ctx->ocFrag.as<int32_t>(); a.candSeq = ctx->ocSeq.as<int32_t>(); a.refStart = ctx->refStart.as<int32_t>();
     a.idBits = ctx->idBits.as<uint32_t>(); a.fragGenome = fs.fragGenome; a.genomeBase = fs.genomeBase; a.contigGenome = sk->contigGenome;
     a.contigBinBase = sk->contigBinBase; a.binWidth = set->params.fragLen - 20; a.bins = ctx->bins.as<uint32_t>(); a.binsPerQuery = binsPerQuery;
@@ -573,6 +671,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(fragdist_stage(ctx, set, sk, pa));
   }
+  if (set->hits) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(hits_stage(ctx, set, sk, a, pa, fs));
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -580,9 +682,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 
 // the dense table of a sub-batch (all chunks reduced) -> rows in (query, reference genome) order, appended to `rows`
 // (`block`: the table is the compact one of that chunk — reference genome = block->g0 + column)
-// (fdOut: where the sub-batch's fragment distribution records go while that mode is on — default: the sketch's pending list)
+// (fdOut, hitOut: where the sub-batch's fragment distribution and best-hit records go while those modes are on — default: the sketch's
+// pending lists)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
-    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr)
+    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
@@ -594,6 +697,13 @@ int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuer
         [](const ani_fragdist_t &r) { return (size_t)r.qryGenomeId; },
         [&](ani_fragdist_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
         fdOut ? fdOut : &set->fdPending));
+  }
+  if (set->hits) {
+    const int32_t base = set->refIdBase;
+    TRY(hits_distribute(ctx->hitStage, (size_t)nQuery, block || set->chunks.size() == 1,
+        [](const ani_hit_t &r) { return (size_t)r.qryGenomeId; },
+        [&](ani_hit_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
+        hitOut ? hitOut : &set->hitPending));
   }
   uint32_t *dense = nullptr;
   TRY(pinned_buffer(ctx, 1, nPairs * 8 + 8, (void **)&dense));
@@ -687,6 +797,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   TRY(upload_luts(sk, maxS));
   std::vector<RowBuf> part(sub.size());
   std::vector<FragDistBuf> fdPart(sk->fragdist ? sub.size() : 0);       // the fragment distribution records take the rows' way
+  std::vector<HitBuf> hitPart(sk->hits ? sub.size() : 0);               // ... and so do the best-hit records
   for (size_t c = 0; c < sk->chunks.size(); c++) {
     TRY(ensure_chunk(sk, c));
     IndexChunk *ch = sk->chunks[c];
@@ -695,7 +806,8 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       int32_t nCand = 0;
       TRY(map_stage(ctx, sk, ch, sb.v, &nCand));
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
-      TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr));
+      TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr,
+          sk->hits ? &hitPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -732,6 +844,13 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
     TRY(fragdist_distribute(fdPart[i], (size_t)sk->fdEdges + 1, (size_t)nq, sk->chunks.size() == 1, [&](const ani_fragdist_t &r) {
           return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
         [](ani_fragdist_t &) {}, &sk->fdPending));
+  }
+  for (size_t i = 0; i < hitPart.size(); i++) {
+    const int32_t q0 = sub[i].firstQueryId, nq = sub[i].g1 - sub[i].g0;
+    const int32_t *ids = sub[i].queryIds;
+    TRY(hits_distribute(hitPart[i], (size_t)nq, sk->chunks.size() == 1, [&](const ani_hit_t &r) {
+          return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
+        [](ani_hit_t &) {}, &sk->hitPending));
   }
   return ANI_OK;
 }
@@ -2172,6 +2291,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
   const size_t nCh = sk->chunks.size();
   std::vector<std::vector<int32_t>> cFrag(nCh), cSeq(nCh), cStart(nCh); std::vector<std::vector<uint32_t>> cBits(nCh);
   std::vector<int32_t> fragQ;                        // several queries: fragment -> fs.genomeBase + its query
+  std::vector<int32_t> fragId;                       // best-hit records on: fragment -> its querySeqId as given
   int32_t lastQ = -1, f = -1, q = 0;
   size_t chunkOfSeqHint = 0;
   for (size_t i = 0; i < n; i++) {
@@ -2179,6 +2299,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     if (a.querySeqId != lastQ || f < 0) {
       f++; lastQ = a.querySeqId;
       if (queryFragStart) { while (a.querySeqId >= queryFragStart[q + 1]) q++; fragQ.push_back(fs.genomeBase + q); }
+      if (sk->hits) fragId.push_back(a.querySeqId);
     }
     size_t c = chunkOfSeqHint;
     while (c + 1 < nCh && a.refSeqId >= sk->chunks[c]->c0 + sk->chunks[c]->nContigs) c++;
@@ -2195,6 +2316,12 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   } else if (nF) HIP_TRY(hipMemsetAsync(ctx->fragGenome.p, 0, nF * 4, ctx->stream));
   fs.fragGenome = ctx->fragGenome.as<int32_t>();
+  if (sk->hits && nF) {
+    TRY(ctx->hitQSeq.ensure(nF * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->hitQSeq.p, fragId.data(), nF * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    fs.fragQSeq = ctx->hitQSeq.as<int32_t>();
+  }
   for (size_t c = 0; c < nCh; c++) {
     const size_t nc = cFrag[c].size();
     if (nc) {
@@ -2207,10 +2334,11 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n, fd0 = sk->fdPending.n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
   if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
+  if (sk->refIdBase) for (size_t i = h0; i < sk->hitPending.n; i++) sk->hitPending.rec[i].refGenomeId -= sk->refIdBase;
   return ANI_OK;
 }
 
@@ -2495,6 +2623,41 @@ int ani_sketch_fragdist_end(ani_sketch *sk)
   if (!sk->fragdist) return fail(ANI_ERR_ARG, "ani_sketch_fragdist_end without ani_sketch_fragdist_begin");
   sk->fdPending.clear(); sk->ctx->fdStage.clear();
   sk->fragdist = false;
+  return ANI_OK;
+}
+
+// ---- reciprocal best-hit records (ani_abi.h: ani_sketch_hits_begin) ----
+int ani_sketch_hits_begin(ani_sketch *sk, float minIdentity, int32_t minFragments)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  memcpy(&sk->hitMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->hitMinIdBits = 0;                   // -0.0 counts as 0
+  sk->hitMinFragments = (uint32_t)minFragments;
+  sk->hitPending.clear(); sk->ctx->hitStage.clear();
+  sk->hits = true;
+  return ANI_OK;
+}
+
+int ani_sketch_hits_take(ani_sketch *sk, ani_hit_t **rec, size_t *n)
+{
+  if (!sk || !rec || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->hits) return fail(ANI_ERR_ARG, "ani_sketch_hits_take without ani_sketch_hits_begin");
+  *rec = nullptr; *n = 0;
+  HitBuf &pd = sk->hitPending;
+  if (pd.n == 0) { pd.clear(); return ANI_OK; }
+  *rec = pd.rec; *n = pd.n;                     // the buffer itself: ani_free releases it
+  pd.rec = nullptr; pd.n = pd.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_hits_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->hits) return fail(ANI_ERR_ARG, "ani_sketch_hits_end without ani_sketch_hits_begin");
+  sk->hitPending.clear(); sk->ctx->hitStage.clear();
+  sk->hits = false;
   return ANI_OK;
 }
 

@@ -419,6 +419,28 @@ struct FragDistBuf {
   void clear() { free(rec); free(hist); rec = nullptr; hist = nullptr; n = cap = 0; }
 };
 
+// reciprocal best-hit records on the host (ani_sketch_hits_begin; kernels/hits.hpp): malloc'ed and geometrically grown like the result
+// rows, so that ani_sketch_hits_take hands the buffer to the caller as it is (ani_free releases it)
+struct HitBuf {
+  ani_hit_t *rec = nullptr; size_t n = 0, cap = 0;
+  HitBuf() = default;
+  HitBuf(const HitBuf &) = delete;
+  HitBuf &operator=(const HitBuf &) = delete;
+  ~HitBuf() { clear(); }
+  bool reserve(size_t extra)                            // room for `extra` more records; false: out of memory (the buffer stays as it was)
+  {
+    if (n + extra <= cap && rec) return true;
+    const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 1024);
+    if (want > SIZE_MAX / sizeof(ani_hit_t)) return false;
+    void *r = realloc(rec, want * sizeof(ani_hit_t));
+    if (!r) return false;
+    rec = (ani_hit_t *)r; cap = want;
+    return true;
+  }
+  void swap(HitBuf &o) { std::swap(rec, o.rec); std::swap(n, o.n); std::swap(cap, o.cap); }
+  void clear() { free(rec); rec = nullptr; n = cap = 0; }
+};
+
 // =====================================================================================================
 struct ani_ctx {
   int device = 0;
@@ -494,6 +516,12 @@ struct ani_ctx {
   DevBuf fdFlags, fdOff, fdList, fdRec, fdHist;
   FragDistBuf fdStage;
   uint32_t fragDistPiece = 1u << 18;      // records per launch and copy (env ANI_TEST_FRAGDIST_PIECE, tests)
+  // best-hit records (only while a sketch has them on): the owner table beside the bin table, the gate's flags, offsets, list and record
+  // offsets of a (sub-batch, chunk), one piece of records on the device, the querySeqId per fragment of a foreign mapping list, and the
+  // records reduce_stage has staged for the sub-batch's collect_rows (query = index in the sub-batch)
+  DevBuf hitOwner, hitFlags, hitOff, hitList, hitCount, hitRecOff, hitRec, hitQSeq;
+  HitBuf hitStage;
+  uint32_t hitsPiece = 1u << 22;          // records per launch and copy (env ANI_TEST_HITS_PIECE, tests)
 };
 
 // One index over a contiguous run of reference genomes: < 2^31 minimizers, 32-bit indices, chunk-local seqIds.  A reference set
@@ -555,6 +583,10 @@ struct ani_sketch {
   // gives the records the rows' ids and order and appends them to `fdPending`, which ani_sketch_fragdist_take hands over
   bool fragdist = false; uint32_t fdMinIdBits = 0, fdMinFragments = 1; int32_t fdEdges = 0; uint32_t fdEdgeBits[63] = {0};
   FragDistBuf fdPending;
+  // best-hit records (ani_sketch_hits_begin .. _end): reduce_stage makes a record per non-empty cell of every gated pair while they are
+  // on; they take the way of the fragment distributions' records to `hitPending`, which ani_sketch_hits_take hands over
+  bool hits = false; uint32_t hitMinIdBits = 0, hitMinFragments = 1;
+  HitBuf hitPending;
 };
 
 namespace anih {

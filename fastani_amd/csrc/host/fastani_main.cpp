@@ -88,6 +88,8 @@ struct Options {
   float profileMinANI = 95.0f; int profileMinFragments = 50;   // --profileMinANI, --profileMinFragments: the pairs that count (ani_sketch_profile_begin's gate)
   bool fragDist = false;                               // --fragDist: the .fragdist file, the spread of the fragment identities behind every -o line
   std::vector<float> fragDistEdges;                    // --fragDistEdges: the class edges of its histograms (default_fragdist_edges)
+  bool hits = false;                                   // --hits: the .hits file, the reciprocal best fragment hits behind every -o line
+  float hitsMinANI = 0.0f; int hitsMinFragments = 1;   // --hitsMinANI, --hitsMinFragments: the pairs that get lines (ani_sketch_hits_begin's gate)
   float fragDistMinANI = 0.0f; int fragDistMinFragments = 1;   // --fragDistMinANI, --fragDistMinFragments: the pairs that get a line (ani_sketch_fragdist_begin's gate)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
@@ -114,6 +116,7 @@ struct Options {
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
+    "             [--hits] [--hitsMinANI <value>] [--hitsMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -180,6 +183,15 @@ struct Options {
     "     --fragDistEdges <a,b,...>  at most 63 ascending class edges in [0, 100] [default : 70,71,...,99,99.5,99.9]\n"
     "     --fragDistMinANI <value>  only the pairs from this ANI on get a line (0 <= value <= 100) [default : 0, every line of the output]\n"
     "     --fragDistMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
+    "     --hits  also write <output>.hits: per line of the output, one line per matched fragment - the reciprocal best hits the ANI\n"
+    "                 value is the mean of - in the 12 columns of the .visual file (query, reference, identity, NA, NA, NA, query\n"
+    "                 start, query end, reference start, reference end, NA, NA; reference coordinates over the reference genome's\n"
+    "                 contigs), a pair's lines in reference order; works in every input mode, at any scale and with --gpus.  Where\n"
+    "                 several fragments reach one reference bin with equal identity the last fragment of the query is reported.\n"
+    "                 Host memory: 24 bytes per hit while a reference shard is mapped, 16 until the file is written, and 4 bytes\n"
+    "                 per query contig; the two options below are the remedy for runs whose hits do not fit\n"
+    "     --hitsMinANI <value>  only the pairs from this ANI on get lines (0 <= value <= 100) [default : 0, every line of the output]\n"
+    "     --hitsMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -216,7 +228,7 @@ Options parse(int argc, char **argv)
   std::string refName, refList, qryName, qryList;
   bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
   bool profileMinANI = false, profileMinFragments = false;
-  bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false;
+  bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false, hitsMinANI = false, hitsMinFragments = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -276,6 +288,11 @@ Options parse(int argc, char **argv)
       if (!ok) { std::cerr << "ERROR, --fragDistEdges takes at most 63 ascending values in [0, 100], separated by commas" << std::endl; exit(1); } }
     else if (a == "--fragDistMinANI") { o.fragDistMinANI = (float)atof(need(i)); fragDistMinANI = true;
       if (!(o.fragDistMinANI >= 0.0f && o.fragDistMinANI <= 100.0f)) { std::cerr << "ERROR, --fragDistMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--hits") o.hits = true;
+    else if (a == "--hitsMinANI") { o.hitsMinANI = (float)atof(need(i)); hitsMinANI = true;
+      if (!(o.hitsMinANI >= 0.0f && o.hitsMinANI <= 100.0f)) { std::cerr << "ERROR, --hitsMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--hitsMinFragments") { o.hitsMinFragments = atoi(need(i)); hitsMinFragments = true;
+      if (o.hitsMinFragments < 1) { std::cerr << "ERROR, --hitsMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "--fragDistMinFragments") { o.fragDistMinFragments = atoi(need(i)); fragDistMinFragments = true;
       if (o.fragDistMinFragments < 1) { std::cerr << "ERROR, --fragDistMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
@@ -302,6 +319,8 @@ Options parse(int argc, char **argv)
   if (profileMinFragments && !o.profile) { std::cerr << "ERROR, --profileMinFragments needs --profile" << std::endl; exit(1); }
   if (fragDistEdges && !o.fragDist) { std::cerr << "ERROR, --fragDistEdges needs --fragDist" << std::endl; exit(1); }
   if (fragDistMinANI && !o.fragDist) { std::cerr << "ERROR, --fragDistMinANI needs --fragDist" << std::endl; exit(1); }
+  if (hitsMinANI && !o.hits) { std::cerr << "ERROR, --hitsMinANI needs --hits" << std::endl; exit(1); }
+  if (hitsMinFragments && !o.hits) { std::cerr << "ERROR, --hitsMinFragments needs --hits" << std::endl; exit(1); }
   if (fragDistMinFragments && !o.fragDist) { std::cerr << "ERROR, --fragDistMinFragments needs --fragDist" << std::endl; exit(1); }
   if (o.fragDist && !fragDistEdges) { for (int e = 70; e <= 99; e++) o.fragDistEdges.push_back((float)e); o.fragDistEdges.push_back(99.5f); o.fragDistEdges.push_back(99.9f); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
@@ -608,10 +627,18 @@ struct GenomeLengths {
     uint64_t s = 0;
     for (int32_t l : g.lens) if (l >= fragLen) s += (uint64_t)(l / fragLen) * (uint64_t)fragLen;
     std::lock_guard<std::mutex> lk(mu); len.emplace(path, s);
+    if (keepContigs) contigs.emplace(path, g.lens);
+  }
+  // --hits: the contig lengths of every genome that passed through (4 bytes per contig), for the query coordinates of the .hits file
+  bool keepContigs = false;
+  const std::vector<int32_t> &contigs_of(const std::string &path)
+  {
+    static const std::vector<int32_t> none;
+    std::lock_guard<std::mutex> lk(mu); const auto it = contigs.find(path); return it == contigs.end() ? none : it->second;
   }
   uint64_t of(const std::string &path) { std::lock_guard<std::mutex> lk(mu); const auto it = len.find(path); return it == len.end() ? 0 : it->second; }
  private:
-  const int fragLen; std::mutex mu; std::unordered_map<std::string, uint64_t> len;
+  const int fragLen; std::mutex mu; std::unordered_map<std::string, uint64_t> len; std::unordered_map<std::string, std::vector<int32_t>> contigs;
 };
 
 // what follows from the options, decided once
@@ -737,6 +764,47 @@ struct FragDistTable {
   }
 };
 FragDistTable g_fragdist;
+
+// --hits: the best-hit records (ani_sketch_hits_begin) of the pairs, keyed by (query, reference) file index.  Begun and drained where the
+// profile is.  A record's reference contig becomes the offset of that contig inside its genome while the sketch that knows it is alive.
+struct HitsTable {
+  bool on = false; float minANI = 0.0f; int32_t minFragments = 1;
+  struct Hit { int32_t qSeq; float identity; int64_t refStart; };             // 16 bytes per record until the file is written
+  struct Run { size_t first; uint32_t n; };
+  std::vector<Hit> hit;
+  std::unordered_map<uint64_t, Run> at;                    // (query << 32 | reference) -> the pair's records, in their order
+  void init(const Options &o) { on = o.hits; minANI = o.hitsMinANI; minFragments = o.hitsMinFragments; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_hits_begin(sk, minANI, minFragments)) { std::cerr << "ERROR, ani_sketch_hits_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  // what the mapping calls left in `sk`: genome g of the sketch is reference refOf(g); the query ids are the run's own
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_hit_t *r = nullptr; size_t n = 0; const int32_t *cl = nullptr, *gcs = nullptr;
+    if (ani_sketch_hits_take(sk, &r, &n) || ani_sketch_tables(sk, &cl, &gcs)) { std::cerr << "ERROR, ani_sketch_hits_take: " << ani_last_error() << std::endl; exit(1); }
+    hit.reserve(hit.size() + n);
+    int32_t g = -1, seq = -1; int64_t off = 0;              // the genome and contig of the previous record: a pair's records ascend by contig
+    for (size_t i = 0; i < n; i++) {
+      const ani_hit_t &e = r[i];
+      const bool fresh = i == 0 || e.refGenomeId != r[i - 1].refGenomeId || e.qryGenomeId != r[i - 1].qryGenomeId;
+      if (fresh) at[((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)refOf(e.refGenomeId)] = Run{hit.size(), 0};
+      if (e.refGenomeId != g || e.refSeqId < seq) { g = e.refGenomeId; seq = gcs[g]; off = 0; }
+      for (; seq < e.refSeqId; seq++) off += cl[seq];
+      hit.push_back(Hit{e.querySeqId, e.identity, off + e.refStartPos});
+    }
+    // (counted afterwards: the map's entries may move while it grows)
+    for (size_t i = 0; i < n;) {
+      size_t j = i + 1;
+      while (j < n && r[j].refGenomeId == r[i].refGenomeId && r[j].qryGenomeId == r[i].qryGenomeId) j++;
+      at[((uint64_t)(uint32_t)r[i].qryGenomeId << 32) | (uint32_t)refOf(r[i].refGenomeId)].n = (uint32_t)(j - i);
+      i = j;
+    }
+    ani_free(r);
+  }
+};
+HitsTable g_hits;
 
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
@@ -1014,6 +1082,7 @@ struct Streaming {
     const int32_t g0 = shard[d].g0;
     g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_fragdist.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_hits.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
   }
 
   // every device sketches its run of the reference slices into its shard's tables and record parts (all-vs-all: the query sets too)
@@ -1108,7 +1177,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); }
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1339,7 +1408,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk); g_fragdist.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1396,6 +1465,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     }
     g_profile.take(sk, ap.fragLen, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });      // the split's genome g is reference refIdx[g]
     g_fragdist.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
+    g_hits.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
   for (int sp = 0; sp < nSplits; sp++) std::cerr << "INFO [thread " << sp << "], skch::main, ready to exit the loop" << std::endl;
@@ -1497,6 +1567,27 @@ void write_fragdist(const Options &o, const std::vector<ani_cgi_t> &rows, const 
     const uint32_t *h = g_fragdist.hist.data() + it->second * w;
     for (size_t c = 0; c < w; c++) f.out << (c ? "," : "") << h[c];
     f.out << "\n";
+  }
+}
+
+// ---- .hits: per line of the output file whose pair passed the gate, in its order, one line per record, in the records' order, in the
+// 12 columns of the .visual file: the query coordinates from the fragment's running id as .visual has them, the reference coordinates over
+// the reference genome's contigs
+void write_hits(const Options &o, const ani_params_t &ap, const std::vector<ani_cgi_t> &rows, const Trusted &trusted, GenomeLengths &lengths)
+{
+  BufferedFile f(o.out + ".hits");
+  int32_t q = -1; std::vector<int64_t> qOff;
+  for (auto &e : rows) {
+    if (!trusted(e)) continue;
+    const auto it = g_hits.at.find(((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId);
+    if (it == g_hits.at.end()) continue;                    // the pair did not pass the gate
+    if (e.qryGenomeId != q) { q = e.qryGenomeId; qOff = fragment_offsets(ap, lengths.contigs_of(o.queries[(size_t)q])); }
+    for (size_t i = it->second.first; i < it->second.first + it->second.n; i++) {
+      const HitsTable::Hit &h = g_hits.hit[i];
+      const int64_t qs = (size_t)h.qSeq < qOff.size() ? qOff[(size_t)h.qSeq] : 0;
+      f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << h.identity << "\tNA\tNA\tNA\t" << qs << "\t" << qs + ap.fragLen - 1 << "\t"
+            << h.refStart << "\t" << h.refStart + ap.fragLen - 1 << "\tNA\tNA\n";
+    }
   }
 }
 
@@ -2009,9 +2100,10 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o); g_fragdist.init(o);
+  g_profile.init(o); g_fragdist.init(o); g_hits.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
+  lengths.keepContigs = o.hits;
   Startup su(o, m, ap);
   std::cerr << "INFO [thread 0], skch::Sketch::build, window size for minimizer sampling  = " << ap.windowSize << std::endl;
   std::cerr << "INFO [thread 0], skch::main, Count of threads executing parallel_for : " << (o.sanityCheck ? o.threads : (int)su.dev.size()) << std::endl;
@@ -2030,6 +2122,7 @@ int main(int argc, char **argv)
   write_txt(o, res.rows, trusted);
   if (o.profile) write_profile(o, ap.fragLen);
   if (o.fragDist) write_fragdist(o, res.rows, trusted);
+  if (o.hits) write_hits(o, ap, res.rows, trusted, lengths);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

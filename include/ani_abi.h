@@ -388,6 +388,43 @@ int ani_sketch_fragdist_begin(ani_sketch *sk, float minIdentity, int32_t minFrag
 int ani_sketch_fragdist_take(ani_sketch *sk, ani_fragdist_t **rec, uint32_t **hist, size_t *n);
 int ani_sketch_fragdist_end(ani_sketch *sk);
 
+/* ---- reciprocal best-hit records of the fused path (the reference prints such records for --visualize only, one query genome per call
+ * and from a std::sort on the host).  Between begin and end every call that reduces against the sketch (the calls
+ * of the profile's rule 5; ani_map_query adds nothing) appends one record per non-empty cell of every contributing pair to a list on the
+ * host, which take hands over.  Everything is integer or bit pattern.
+ *  1. 1-way winner: the profile's rule 2.  For a fragment f of query genome q and a reference genome g it is the maximum under
+ *     (nucIdentity bits, refSeqId, refStartPos) over f's mappings to g; it lies in bin b = refStartPos / (fragLen - 20) of its contig.
+ *  2. Cell winner.  cell(q, b) = the maximum identity over the fragments whose 1-way winner lies in b.  The cell's hit is the fragment with
+ *     the LARGEST querySeqId among those whose 1-way winner lies in b with identity bits equal to the cell's.  querySeqId is unique per
+ *     fragment of a genome, so the hit is unique.  A fragment whose 1-way winner loses its cell has no record for that pair, even if
+ *     another of its mappings would have won a different cell.  (A stated tie rule: the reference leaves equal identities in one bin to
+ *     the order std::sort happens to produce.)
+ *  3. Gate: the profile's rule 3.  The pair contributes iff it has a row, countSeq >= minFragments and bits(identity) >= bits(minIdentity);
+ *     minIdentity in [0, 100] (-0.0 counts as 0), minFragments >= 1.
+ *  4. Record.  refGenomeId and qryGenomeId are those of the ani_cgi_t row the same call returned for the pair (firstQueryId, the query ids
+ *     of a merged set and ani_sketch_set_ref_id_base included).  refSeqId is the sketch's own set-global contig id, in the order of
+ *     ani_sketch_tables; the id base does not apply to it.  refStartPos and identity are those of the winning mapping, bit for bit.
+ *     querySeqId is the value ani_map_query reports for that fragment; for ani_compute_cgi (and ani_reduce_check) the mapping's own
+ *     querySeqId as given — not dense, up to 2^31 - 1.
+ *  5. Count.  A contributing pair has exactly countSeq records; their identities, summed in float in record order and divided by the
+ *     count, give the row's identity bit for bit.
+ *  6. Order.  The records of one call come in the order of that call's rows, restricted to the pairs that pass the gate; within a pair in
+ *     bin order, (refSeqId, bin) ascending; calls follow each other in call order.
+ *  7. Rows are untouched: with the mode on or off every mapping call returns the same rows, bit for bit.  The profile, the distributions
+ *     and the hits can be on together and do not see each other.
+ *  8. Determinism.  Nothing depends on schedule, sub-batch size, index chunking, residency (resident, chunked, streamed) or piece sizes.
+ * begin starts (a second begin drops what is pending and takes the new gate).  take hands over everything appended since begin or the
+ * last take and empties the list: rec[n], released with ani_free; with n = 0 it comes back NULL.  24 bytes per record of host memory until
+ * taken; the gate is the remedy for sets whose records do not fit.  While the mode is on the device holds one more uint32 per cell of a
+ * sub-batch's bin table.  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null sketch (or rec or n), a gate outside its ranges
+ * (NaN included), take or end without a begin; a refused begin leaves a running mode as it was.  ANI_ERR_NOMEM: the records do not fit the
+ * host, or the device cannot hold the extra table.  ANI_ERR_LIMIT: more than 2^32 - 16 records in one (sub-batch, index chunk).  After a
+ * call that failed while reducing, the pending list is unspecified until the next begin. */
+typedef struct { int32_t refGenomeId, qryGenomeId, refSeqId, refStartPos, querySeqId; float identity; } ani_hit_t;  /* 24 bytes */
+int ani_sketch_hits_begin(ani_sketch *sk, float minIdentity, int32_t minFragments);
+int ani_sketch_hits_take(ani_sketch *sk, ani_hit_t **rec, size_t *n);
+int ani_sketch_hits_end(ani_sketch *sk);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
