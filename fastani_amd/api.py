@@ -45,6 +45,8 @@ BINPROFILE_DT = np.dtype([("count", "<u4"), ("minIdentity", "<f4"), ("maxIdentit
 FRAGDIST_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("minIdentity", "<f4"), ("q1", "<f4"), ("median", "<f4"),
                         ("q3", "<f4"), ("maxIdentity", "<f4"), ("sum", "<u8")])
 HIT_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("querySeqId", "<i4"), ("identity", "<f4")])
+CI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("replicates", "<u4"), ("sum", "<u8"), ("lowSum", "<u8"),
+                  ("highSum", "<u8"), ("low", "<f4"), ("high", "<f4")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -148,6 +150,9 @@ def _bind(lib):
         "ani_sketch_hits_begin": (C.c_int, [vp, C.c_float, C.c_int32]),
         "ani_sketch_hits_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_hits_end": (C.c_int, [vp]),
+        "ani_sketch_ci_begin": (C.c_int, [vp, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]),
+        "ani_sketch_ci_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_ci_end": (C.c_int, [vp]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
@@ -975,6 +980,23 @@ class Sketch:
 
     def hits_end(self):
         self.e._chk(self.e.lib.ani_sketch_hits_end(self.h))
+
+    def ci_begin(self, replicates=200, level=95.0, seed=1, min_identity=0.0, min_fragments=1):
+        """start (or restart) the percentile bootstrap intervals of the ANI values: every mapping call that reduces against this sketch
+        appends one record per pair whose row has countSeq >= min_fragments and identity >= min_identity; `replicates` in 1 .. 1024,
+        `level` in percent (a multiple of 0.1 in 0.1 .. 99.9), `seed` a uint32 (ani_sketch_ci_begin)"""
+        permille = float(level) * 10.0
+        permille = int(round(permille)) if np.isfinite(permille) and abs(permille) < 2 ** 30 else -1
+        self.e._chk(self.e.lib.ani_sketch_ci_begin(self.h, float(min_identity), int(min_fragments), int(replicates), permille, int(seed) & 0xffffffff))
+
+    def ci_take(self):
+        """-> CI_DT[n]: the records appended since ci_begin or the last take, in row order; empties the list"""
+        rp, n = C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_ci_take(self.h, C.byref(rp), C.byref(n)))
+        return self.e._take(rp, n.value, CI_DT)
+
+    def ci_end(self):
+        self.e._chk(self.e.lib.ani_sketch_ci_end(self.h))
 
     def profile_layout(self):
         """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and

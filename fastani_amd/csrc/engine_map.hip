@@ -15,6 +15,7 @@
 #include "kernels/reduce.hpp"
 #include "kernels/profile.hpp"
 #include "kernels/fragdist.hpp"
+#include "kernels/ci.hpp"
 #include "kernels/hits.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/tree.hpp"
@@ -602,17 +603,18 @@ static int hits_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const OneWa
 // The staged records of a sub-batch (`in`: chunk by chunk, per chunk pairs in (query, reference) order, per pair in bin order) in (query,
 // reference) order, appended to `out` with the ids `patch` gives them: fragdist_distribute for groups of any length — the distribution
 // by the query's slot is stable, so a pair's records stay together and in their order.
-template <class SlotOf, class Patch>
-static int hits_distribute(HitBuf &in, size_t nq, bool ordered, SlotOf slot_of, Patch patch, HitBuf *out)
+// (the bootstrap intervals' records, one per pair, go the same way)
+template <class Rec, class SlotOf, class Patch>
+static int hits_distribute(RecBuf<Rec> &in, size_t nq, bool ordered, SlotOf slot_of, Patch patch, RecBuf<Rec> *out)
 {
   const size_t n = in.n;
   if (n == 0) return ANI_OK;
   const size_t at = out->n, slice = 65536;
   if (ordered && at == 0) out->swap(in);
   else {
-    if (!out->reserve(n)) return fail(ANI_ERR_NOMEM, "host allocation of %zu best-hit records failed", n);
-    if (ordered) parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(ani_hit_t), [&](size_t j) {      // (into fresh pages: see fragdist_stage)
-        memcpy(out->rec + at + j * slice, in.rec + j * slice, std::min(slice, n - j * slice) * sizeof(ani_hit_t)); });
+    if (!out->reserve(n)) return fail(ANI_ERR_NOMEM, "host allocation of %zu records failed", n);
+    if (ordered) parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(Rec), [&](size_t j) {      // (into fresh pages: see fragdist_stage)
+        memcpy(out->rec + at + j * slice, in.rec + j * slice, std::min(slice, n - j * slice) * sizeof(Rec)); });
     else {
       std::vector<size_t> start(nq + 1, 0);
       for (size_t r = 0; r < n; r++) start[slot_of(in.rec[r]) + 1]++;
@@ -621,9 +623,83 @@ static int hits_distribute(HitBuf &in, size_t nq, bool ordered, SlotOf slot_of, 
     }
     out->n = at + n;
   }
-  parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(ani_hit_t), [&](size_t j) {
+  parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(Rec), [&](size_t j) {
     for (size_t r = at + j * slice, r1 = at + std::min(n, (j + 1) * slice); r < r1; r++) patch(out->rec[r]); });
   in.clear();
+  return ANI_OK;
+}
+
+// The bootstrap intervals of one (sub-batch, index chunk) (kernels/ci.hpp), from the bin table and the pair table
+// k_pair_reduce has just completed: gate -> flags -> scan -> list, a second scan over the cells the listed pairs keep in the device pool
+// (those above the LDS cap), then the records piece by piece — ciPiece records per launch, fewer where the pairs' pool cells exceed 64 per
+// record of the piece; a piece ends at a pair border and a larger pair is a piece of its own — through page-locked memory into
+// ctx->ciStage, where collect_rows finds them; low and high are computed here.  Only while the sketch has the mode on.
+static int ci_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const PairArgs &pa)
+{
+  const size_t nPairs = (size_t)pa.nQuery * (size_t)sk->nGenomes;
+  if (nPairs == 0) return ANI_OK;
+  CiArgs ca;
+  ca.nQuery = pa.nQuery; ca.nRefGenomes = sk->nGenomes; ca.bins = pa.bins; ca.binsPerQuery = pa.binsPerQuery; ca.genomeBinStart = sk->genomeBinStart;
+  ca.pairCount = pa.pairCount; ca.pairIdentity = pa.pairIdentity; ca.outStride = pa.outStride; ca.outCol0 = pa.outCol0;
+  ca.minIdBits = set->ciMinIdBits; ca.minFragments = set->ciMinFragments; ca.genomeBase = sk->g0;
+  const uint32_t B = set->ciReplicates;
+  ca.replicates = B; ca.lowRank = (uint32_t)(((uint64_t)(B - 1) * (1000u - set->ciLevel)) / 2000u); ca.highRank = B - 1 - ca.lowRank; ca.seed = set->ciSeed;
+  ca.ldsCells = std::min<uint32_t>(ctx->ciLdsCells, (uint32_t)kCiLdsCells);
+  TRY(ctx->ciFlags.ensure(nPairs * 4)); TRY(ctx->ciOff.ensure(nPairs * 4));
+  hipLaunchKernelGGL(k_ci_flags, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ca, ctx->ciFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t listed = 0, poolTotal = 0;
+  TRY(device_scan(ctx, ctx->ciFlags.as<int32_t>(), ctx->ciOff.as<uint32_t>(), (uint32_t)nPairs, &listed));
+  if (listed == 0) return ANI_OK;
+  TRY(ctx->ciList.ensure((size_t)listed * 4)); TRY(ctx->ciPoolCells.ensure((size_t)listed * 4)); TRY(ctx->ciPoolOff.ensure((size_t)listed * 4));
+  hipLaunchKernelGGL(k_ci_list, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ca, (const int32_t *)ctx->ciFlags.as<int32_t>(),
+                     (const uint32_t *)ctx->ciOff.as<uint32_t>(), ctx->ciList.as<uint32_t>(), ctx->ciPoolCells.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  // (the pooled cells are cells of the bin table, which holds fewer than 2^32 - 16)
+  TRY(device_scan(ctx, ctx->ciPoolCells.as<int32_t>(), ctx->ciPoolOff.as<uint32_t>(), (uint32_t)listed, &poolTotal));
+  std::vector<uint32_t> poolOff;                       // only where a pair is above the cap: else every piece is ciPiece records
+  if (poolTotal) {
+    poolOff.resize((size_t)listed + 1);
+    HIP_TRY(hipMemcpyAsync(poolOff.data(), ctx->ciPoolOff.p, (size_t)listed * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    poolOff[(size_t)listed] = (uint32_t)poolTotal;
+  }
+  const size_t piece = std::min<size_t>(ctx->ciPiece, (size_t)listed);
+  const uint64_t poolPiece = (uint64_t)ctx->ciPiece * 64;
+  TRY(ctx->ciRec.ensure(piece * sizeof(CiRec)));
+  uint8_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, piece * sizeof(CiRec), (void **)&host));
+  CiBuf &st = ctx->ciStage;
+  if (!st.reserve((size_t)listed)) return fail(ANI_ERR_NOMEM, "host allocation of %llu interval records failed", (unsigned long long)listed);
+  static_assert(sizeof(CiRec) == sizeof(ani_ci_t), "the device record is the ABI's");
+  for (size_t a = 0; a < (size_t)listed;) {
+    size_t b = std::min(a + piece, (size_t)listed);
+    uint32_t poolBase = 0; size_t poolCells = 0;
+    if (poolTotal) {
+      b = a + 1;
+      while (b < a + piece && b < (size_t)listed && (uint64_t)poolOff[b + 1] - poolOff[a] <= poolPiece) b++;
+      poolBase = poolOff[a]; poolCells = poolOff[b] - poolOff[a];
+    }
+    const size_t n = b - a;
+    TRY(ctx->ciPool.ensure((poolCells ? poolCells : 1) * 4));     // (the stream is idle: the last piece has been copied)
+    hipLaunchKernelGGL(k_ci_records, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, ca, (const uint32_t *)ctx->ciList.as<uint32_t>(),
+                       (const uint32_t *)ctx->ciPoolOff.as<uint32_t>(), (uint32_t)a, (uint32_t)n, poolBase, ctx->ciPool.as<uint32_t>(), ctx->ciRec.as<CiRec>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, ctx->ciRec.p, n * sizeof(CiRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t slice = 4096, at = st.n;
+    parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(CiRec), [&](size_t i) {      // (into fresh pages: see fragdist_stage)
+      const size_t r0 = i * slice, m = std::min(slice, n - r0);
+      memcpy(st.rec + at + r0, host + r0 * sizeof(CiRec), m * sizeof(CiRec));
+      for (size_t r = at + r0; r < at + r0 + m; r++) {
+        ani_ci_t &x = st.rec[r];
+        const double den = (double)x.count * 1048576.0;
+        x.low = (float)((double)x.lowSum / den); x.high = (float)((double)x.highSum / den);
+      }
+    });
+    st.n += n;
+    a = b;
+  }
   return ANI_OK;
 }
 
@@ -675,6 +751,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(hits_stage(ctx, set, sk, a, pa, fs));
   }
+  if (set->ci) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(ci_stage(ctx, set, sk, pa));
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -682,10 +762,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 
 // the dense table of a sub-batch (all chunks reduced) -> rows in (query, reference genome) order, appended to `rows`
 // (`block`: the table is the compact one of that chunk — reference genome = block->g0 + column)
-// (fdOut, hitOut: where the sub-batch's fragment distribution and best-hit records go while those modes are on — default: the sketch's
-// pending lists)
+// (fdOut, hitOut, ciOut: where the sub-batch's fragment distribution, best-hit and interval records go while those modes are on —
+// default: the sketch's pending lists)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
-    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr)
+    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
@@ -704,6 +784,13 @@ int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuer
         [](const ani_hit_t &r) { return (size_t)r.qryGenomeId; },
         [&](ani_hit_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
         hitOut ? hitOut : &set->hitPending));
+  }
+  if (set->ci) {
+    const int32_t base = set->refIdBase;
+    TRY(hits_distribute(ctx->ciStage, (size_t)nQuery, block || set->chunks.size() == 1,
+        [](const ani_ci_t &r) { return (size_t)r.qryGenomeId; },
+        [&](ani_ci_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
+        ciOut ? ciOut : &set->ciPending));
   }
   uint32_t *dense = nullptr;
   TRY(pinned_buffer(ctx, 1, nPairs * 8 + 8, (void **)&dense));
@@ -798,6 +885,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   std::vector<RowBuf> part(sub.size());
   std::vector<FragDistBuf> fdPart(sk->fragdist ? sub.size() : 0);       // the fragment distribution records take the rows' way
   std::vector<HitBuf> hitPart(sk->hits ? sub.size() : 0);               // ... and so do the best-hit records
+  std::vector<CiBuf> ciPart(sk->ci ? sub.size() : 0);                   // ... and the interval records
   for (size_t c = 0; c < sk->chunks.size(); c++) {
     TRY(ensure_chunk(sk, c));
     IndexChunk *ch = sk->chunks[c];
@@ -807,7 +895,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       TRY(map_stage(ctx, sk, ch, sb.v, &nCand));
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
       TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr,
-          sk->hits ? &hitPart[i] : nullptr));
+          sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -851,6 +939,13 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
     TRY(hits_distribute(hitPart[i], (size_t)nq, sk->chunks.size() == 1, [&](const ani_hit_t &r) {
           return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
         [](ani_hit_t &) {}, &sk->hitPending));
+  }
+  for (size_t i = 0; i < ciPart.size(); i++) {
+    const int32_t q0 = sub[i].firstQueryId, nq = sub[i].g1 - sub[i].g0;
+    const int32_t *ids = sub[i].queryIds;
+    TRY(hits_distribute(ciPart[i], (size_t)nq, sk->chunks.size() == 1, [&](const ani_ci_t &r) {
+          return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
+        [](ani_ci_t &) {}, &sk->ciPending));
   }
   return ANI_OK;
 }
@@ -2334,11 +2429,12 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
   if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = h0; i < sk->hitPending.n; i++) sk->hitPending.rec[i].refGenomeId -= sk->refIdBase;
+  if (sk->refIdBase) for (size_t i = ci0; i < sk->ciPending.n; i++) sk->ciPending.rec[i].refGenomeId -= sk->refIdBase;
   return ANI_OK;
 }
 
@@ -2658,6 +2754,44 @@ int ani_sketch_hits_end(ani_sketch *sk)
   if (!sk->hits) return fail(ANI_ERR_ARG, "ani_sketch_hits_end without ani_sketch_hits_begin");
   sk->hitPending.clear(); sk->ctx->hitStage.clear();
   sk->hits = false;
+  return ANI_OK;
+}
+
+// ---- bootstrap intervals of the ANI values (ani_abi.h: ani_sketch_ci_begin) ----
+int ani_sketch_ci_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, int32_t replicates, int32_t levelPermille, uint32_t seed)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  if (replicates < 1 || replicates > kCiMaxReplicates) return fail(ANI_ERR_ARG, "%d replicates: 1 to %d are taken", replicates, kCiMaxReplicates);
+  if (levelPermille < 1 || levelPermille > 999) return fail(ANI_ERR_ARG, "level %d permille outside 1 .. 999", levelPermille);
+  memcpy(&sk->ciMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->ciMinIdBits = 0;                    // -0.0 counts as 0
+  sk->ciMinFragments = (uint32_t)minFragments;
+  sk->ciReplicates = (uint32_t)replicates; sk->ciLevel = (uint32_t)levelPermille; sk->ciSeed = seed;
+  sk->ciPending.clear(); sk->ctx->ciStage.clear();
+  sk->ci = true;
+  return ANI_OK;
+}
+
+int ani_sketch_ci_take(ani_sketch *sk, ani_ci_t **rec, size_t *n)
+{
+  if (!sk || !rec || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->ci) return fail(ANI_ERR_ARG, "ani_sketch_ci_take without ani_sketch_ci_begin");
+  *rec = nullptr; *n = 0;
+  CiBuf &pd = sk->ciPending;
+  if (pd.n == 0) { pd.clear(); return ANI_OK; }
+  *rec = pd.rec; *n = pd.n;                     // the buffer itself: ani_free releases it
+  pd.rec = nullptr; pd.n = pd.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_ci_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->ci) return fail(ANI_ERR_ARG, "ani_sketch_ci_end without ani_sketch_ci_begin");
+  sk->ciPending.clear(); sk->ctx->ciStage.clear();
+  sk->ci = false;
   return ANI_OK;
 }
 

@@ -419,27 +419,31 @@ struct FragDistBuf {
   void clear() { free(rec); free(hist); rec = nullptr; hist = nullptr; n = cap = 0; }
 };
 
-// reciprocal best-hit records on the host (ani_sketch_hits_begin; kernels/hits.hpp): malloc'ed and geometrically grown like the result
-// rows, so that ani_sketch_hits_take hands the buffer to the caller as it is (ani_free releases it)
-struct HitBuf {
-  ani_hit_t *rec = nullptr; size_t n = 0, cap = 0;
-  HitBuf() = default;
-  HitBuf(const HitBuf &) = delete;
-  HitBuf &operator=(const HitBuf &) = delete;
-  ~HitBuf() { clear(); }
+// reciprocal best-hit records on the host (ani_sketch_hits_begin; kernels/hits.hpp) and the bootstrap intervals (ani_sketch_ci_begin;
+// kernels/ci.hpp): malloc'ed and geometrically grown like the result rows, so that ani_sketch_hits_take / ani_sketch_ci_take hand the
+// buffer to the caller as it is (ani_free releases it)
+template <class Rec>
+struct RecBuf {
+  Rec *rec = nullptr; size_t n = 0, cap = 0;
+  RecBuf() = default;
+  RecBuf(const RecBuf &) = delete;
+  RecBuf &operator=(const RecBuf &) = delete;
+  ~RecBuf() { clear(); }
   bool reserve(size_t extra)                            // room for `extra` more records; false: out of memory (the buffer stays as it was)
   {
     if (n + extra <= cap && rec) return true;
     const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 1024);
-    if (want > SIZE_MAX / sizeof(ani_hit_t)) return false;
-    void *r = realloc(rec, want * sizeof(ani_hit_t));
+    if (want > SIZE_MAX / sizeof(Rec)) return false;
+    void *r = realloc(rec, want * sizeof(Rec));
     if (!r) return false;
-    rec = (ani_hit_t *)r; cap = want;
+    rec = (Rec *)r; cap = want;
     return true;
   }
-  void swap(HitBuf &o) { std::swap(rec, o.rec); std::swap(n, o.n); std::swap(cap, o.cap); }
+  void swap(RecBuf &o) { std::swap(rec, o.rec); std::swap(n, o.n); std::swap(cap, o.cap); }
   void clear() { free(rec); rec = nullptr; n = cap = 0; }
 };
+using HitBuf = RecBuf<ani_hit_t>;
+using CiBuf = RecBuf<ani_ci_t>;
 
 // =====================================================================================================
 struct ani_ctx {
@@ -522,6 +526,13 @@ struct ani_ctx {
   DevBuf hitOwner, hitFlags, hitOff, hitList, hitCount, hitRecOff, hitRec, hitQSeq;
   HitBuf hitStage;
   uint32_t hitsPiece = 1u << 22;          // records per launch and copy (env ANI_TEST_HITS_PIECE, tests)
+  // bootstrap intervals (only while a sketch has them on): the gate's flags, offsets and list of a (sub-batch, chunk), per listed pair
+  // the cells it keeps in the device pool and their offsets, one piece of records and of pool on the device, and the records reduce_stage
+  // has staged for the sub-batch's collect_rows (query = index in the sub-batch)
+  DevBuf ciFlags, ciOff, ciList, ciPoolCells, ciPoolOff, ciPool, ciRec;
+  CiBuf ciStage;
+  uint32_t ciPiece = 1u << 18;            // records per launch and copy, and 64 pool cells per record (env ANI_TEST_CI_PIECE, tests)
+  uint32_t ciLdsCells = 2560 /* ani::kCiLdsCells */;    // cells of a pair kept in LDS (env ANI_TEST_CI_LDS_CELLS lowers it, tests)
 };
 
 // One index over a contiguous run of reference genomes: < 2^31 minimizers, 32-bit indices, chunk-local seqIds.  A reference set
@@ -587,6 +598,10 @@ struct ani_sketch {
   // on; they take the way of the fragment distributions' records to `hitPending`, which ani_sketch_hits_take hands over
   bool hits = false; uint32_t hitMinIdBits = 0, hitMinFragments = 1;
   HitBuf hitPending;
+  // bootstrap intervals (ani_sketch_ci_begin .. _end): reduce_stage makes a record per gated pair while they are on; they take the way
+  // of the fragment distributions' records to `ciPending`, which ani_sketch_ci_take hands over
+  bool ci = false; uint32_t ciMinIdBits = 0, ciMinFragments = 1, ciReplicates = 200, ciLevel = 950, ciSeed = 1;
+  CiBuf ciPending;
 };
 
 namespace anih {

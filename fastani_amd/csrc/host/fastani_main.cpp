@@ -90,6 +90,9 @@ struct Options {
   std::vector<float> fragDistEdges;                    // --fragDistEdges: the class edges of its histograms (default_fragdist_edges)
   bool hits = false;                                   // --hits: the .hits file, the reciprocal best fragment hits behind every -o line
   float hitsMinANI = 0.0f; int hitsMinFragments = 1;   // --hitsMinANI, --hitsMinFragments: the pairs that get lines (ani_sketch_hits_begin's gate)
+  bool ci = false;                                     // --ci: the .ci file, a bootstrap interval beside the ANI of every -o line
+  int ciReplicates = 200, ciLevelPermille = 950; uint32_t ciSeed = 1;   // --ciReplicates, --ciLevel (percent), --ciSeed (ani_sketch_ci_begin)
+  float ciMinANI = 0.0f; int ciMinFragments = 1;       // --ciMinANI, --ciMinFragments: the pairs that get a line (its gate)
   float fragDistMinANI = 0.0f; int fragDistMinFragments = 1;   // --fragDistMinANI, --fragDistMinFragments: the pairs that get a line (ani_sketch_fragdist_begin's gate)
   bool compareRefs() const { return sketchANI || treeFill || sketchNeighbors > 0 || sketchCluster > 0.0f || sketchGraph > 0.0f; }   // these compare the references with each other
   bool signatures() const { return compareRefs() || sketchScreen > 0; }
@@ -117,6 +120,7 @@ struct Options {
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
     "             [--hits] [--hitsMinANI <value>] [--hitsMinFragments <value>]\n"
+    "             [--ci] [--ciReplicates <value>] [--ciLevel <value>] [--ciSeed <value>] [--ciMinANI <value>] [--ciMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
     "     -h, --help  print this help page\n"
@@ -192,6 +196,14 @@ struct Options {
     "                 per query contig; the two options below are the remedy for runs whose hits do not fit\n"
     "     --hitsMinANI <value>  only the pairs from this ANI on get lines (0 <= value <= 100) [default : 0, every line of the output]\n"
     "     --hitsMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
+    "     --ci  also write <output>.ci: a percentile bootstrap interval of every ANI value, resampled from the fragment identities it is\n"
+    "           the mean of.  Line 1 is \"#replicates<TAB>B<TAB>level<TAB>L<TAB>seed<TAB>s\"; then per line of the output, in its order:\n"
+    "           query, reference, ANI, low, high, fragments\n"
+    "     --ciReplicates <value>  bootstrap replicates, 1 to 1024 [default : 200]\n"
+    "     --ciLevel <value>  level of the interval in percent, a multiple of 0.1 in (0, 100) [default : 95]\n"
+    "     --ciSeed <value>  seed of the draws (a 32-bit number; the same seed gives the same file) [default : 1]\n"
+    "     --ciMinANI <value>  only the pairs from this ANI on get a line (0 <= value <= 100) [default : 0, every line of the output]\n"
+    "     --ciMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
     "     -o, --output <value>  output file name\n"
     "     -s, --sanityCheck  run sanity check (small-input mode: whole sets in host memory, one GPU, one index per -t split)\n"
     "     -v, --version  show version\n"
@@ -229,6 +241,7 @@ Options parse(int argc, char **argv)
   bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
   bool profileMinANI = false, profileMinFragments = false;
   bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false, hitsMinANI = false, hitsMinFragments = false;
+  const char *ciSub = nullptr;                         // the first --ci sub-option seen
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -293,6 +306,21 @@ Options parse(int argc, char **argv)
       if (!(o.hitsMinANI >= 0.0f && o.hitsMinANI <= 100.0f)) { std::cerr << "ERROR, --hitsMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hitsMinFragments") { o.hitsMinFragments = atoi(need(i)); hitsMinFragments = true;
       if (o.hitsMinFragments < 1) { std::cerr << "ERROR, --hitsMinFragments takes a count of at least 1" << std::endl; exit(1); } }
+    else if (a == "--ci") o.ci = true;
+    else if (a == "--ciReplicates") { o.ciReplicates = atoi(need(i)); if (!ciSub) ciSub = "--ciReplicates";
+      if (o.ciReplicates < 1 || o.ciReplicates > 1024) { std::cerr << "ERROR, --ciReplicates takes a count in 1 .. 1024" << std::endl; exit(1); } }
+    else if (a == "--ciLevel") { char *end = nullptr; const char *t = need(i); const double v = strtod(t, &end); if (!ciSub) ciSub = "--ciLevel";
+      const double pm = v * 10.0; const long r = (pm > 0.0 && pm < 1000.0) ? lround(pm) : 0;
+      if (!*t || !end || *end || !(r >= 1 && r <= 999) || fabs(pm - (double)r) > 1e-6) {
+        std::cerr << "ERROR, --ciLevel takes a level in (0, 100), a multiple of 0.1" << std::endl; exit(1); }
+      o.ciLevelPermille = (int)r; }
+    else if (a == "--ciSeed") { char *end = nullptr; const char *t = need(i); const unsigned long long v = strtoull(t, &end, 10); if (!ciSub) ciSub = "--ciSeed";
+      if (!*t || *t == '-' || !end || *end || v > 0xffffffffull) { std::cerr << "ERROR, --ciSeed takes a number in 0 .. 4294967295" << std::endl; exit(1); }
+      o.ciSeed = (uint32_t)v; }
+    else if (a == "--ciMinANI") { o.ciMinANI = (float)atof(need(i)); if (!ciSub) ciSub = "--ciMinANI";
+      if (!(o.ciMinANI >= 0.0f && o.ciMinANI <= 100.0f)) { std::cerr << "ERROR, --ciMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--ciMinFragments") { o.ciMinFragments = atoi(need(i)); if (!ciSub) ciSub = "--ciMinFragments";
+      if (o.ciMinFragments < 1) { std::cerr << "ERROR, --ciMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "--fragDistMinFragments") { o.fragDistMinFragments = atoi(need(i)); fragDistMinFragments = true;
       if (o.fragDistMinFragments < 1) { std::cerr << "ERROR, --fragDistMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "-s" || a == "--sanityCheck") o.sanityCheck = true;
@@ -321,6 +349,7 @@ Options parse(int argc, char **argv)
   if (fragDistMinANI && !o.fragDist) { std::cerr << "ERROR, --fragDistMinANI needs --fragDist" << std::endl; exit(1); }
   if (hitsMinANI && !o.hits) { std::cerr << "ERROR, --hitsMinANI needs --hits" << std::endl; exit(1); }
   if (hitsMinFragments && !o.hits) { std::cerr << "ERROR, --hitsMinFragments needs --hits" << std::endl; exit(1); }
+  if (ciSub && !o.ci) { std::cerr << "ERROR, " << ciSub << " needs --ci" << std::endl; exit(1); }
   if (fragDistMinFragments && !o.fragDist) { std::cerr << "ERROR, --fragDistMinFragments needs --fragDist" << std::endl; exit(1); }
   if (o.fragDist && !fragDistEdges) { for (int e = 70; e <= 99; e++) o.fragDistEdges.push_back((float)e); o.fragDistEdges.push_back(99.5f); o.fragDistEdges.push_back(99.9f); }
   if (refName.empty() && refList.empty() && o.refSketch.empty()) { std::cerr << "Provide reference file (s)\n"; exit(1); }
@@ -806,6 +835,35 @@ struct HitsTable {
 };
 HitsTable g_hits;
 
+// --ci: the bootstrap intervals (ani_sketch_ci_begin) of the pairs, keyed by (query, reference) file index.  Begun and drained where the
+// profile is.
+struct CiTable {
+  bool on = false; float minANI = 0.0f; int32_t minFragments = 1, replicates = 200, levelPermille = 950; uint32_t seed = 1;
+  std::vector<ani_ci_t> rec;
+  std::unordered_map<uint64_t, size_t> at;                 // (query << 32 | reference) -> record
+  void init(const Options &o)
+  { on = o.ci; minANI = o.ciMinANI; minFragments = o.ciMinFragments; replicates = o.ciReplicates; levelPermille = o.ciLevelPermille; seed = o.ciSeed; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_ci_begin(sk, minANI, minFragments, replicates, levelPermille, seed)) {
+      std::cerr << "ERROR, ani_sketch_ci_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  // what the mapping calls left in `sk`: genome g of the sketch is reference refOf(g); the query ids are the run's own
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_ci_t *r = nullptr; size_t n = 0;
+    if (ani_sketch_ci_take(sk, &r, &n)) { std::cerr << "ERROR, ani_sketch_ci_take: " << ani_last_error() << std::endl; exit(1); }
+    for (size_t i = 0; i < n; i++) {
+      ani_ci_t e = r[i]; e.refGenomeId = (int32_t)refOf(e.refGenomeId);
+      at[((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId] = rec.size();
+      rec.push_back(e);
+    }
+    ani_free(r);
+  }
+};
+CiTable g_ci;
+
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
 // no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
@@ -1083,6 +1141,7 @@ struct Streaming {
     g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_fragdist.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_hits.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_ci.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
   }
 
   // every device sketches its run of the reference slices into its shard's tables and record parts (all-vs-all: the query sets too)
@@ -1177,7 +1236,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); }
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1408,7 +1467,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1466,6 +1525,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     g_profile.take(sk, ap.fragLen, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });      // the split's genome g is reference refIdx[g]
     g_fragdist.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_hits.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
+    g_ci.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
   for (int sp = 0; sp < nSplits; sp++) std::cerr << "INFO [thread " << sp << "], skch::main, ready to exit the loop" << std::endl;
@@ -1567,6 +1627,21 @@ void write_fragdist(const Options &o, const std::vector<ani_cgi_t> &rows, const 
     const uint32_t *h = g_fragdist.hist.data() + it->second * w;
     for (size_t c = 0; c < w; c++) f.out << (c ? "," : "") << h[c];
     f.out << "\n";
+  }
+}
+
+// ---- .ci: "#replicates B level L seed s", then per line of the output file whose pair passed the gate, in its order: query, reference, the
+// line's own ANI, the interval's low and high (the identities as the output file prints them) and the fragments
+void write_ci(const Options &o, const std::vector<ani_cgi_t> &rows, const Trusted &trusted)
+{
+  BufferedFile f(o.out + ".ci");
+  f.out << "#replicates\t" << g_ci.replicates << "\tlevel\t" << (float)((double)g_ci.levelPermille / 10.0) << "\tseed\t" << g_ci.seed << "\n";
+  for (auto &e : rows) {
+    if (!trusted(e)) continue;
+    const auto it = g_ci.at.find(((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId);
+    if (it == g_ci.at.end()) continue;                      // the pair did not pass the gate
+    const ani_ci_t &x = g_ci.rec[it->second];
+    f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << e.identity << "\t" << x.low << "\t" << x.high << "\t" << x.count << "\n";
   }
 }
 
@@ -2100,7 +2175,7 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o); g_fragdist.init(o); g_hits.init(o);
+  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
   lengths.keepContigs = o.hits;
@@ -2123,6 +2198,7 @@ int main(int argc, char **argv)
   if (o.profile) write_profile(o, ap.fragLen);
   if (o.fragDist) write_fragdist(o, res.rows, trusted);
   if (o.hits) write_hits(o, ap, res.rows, trusted, lengths);
+  if (o.ci) write_ci(o, res.rows, trusted);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

@@ -425,6 +425,42 @@ int ani_sketch_hits_begin(ani_sketch *sk, float minIdentity, int32_t minFragment
 int ani_sketch_hits_take(ani_sketch *sk, ani_hit_t **rec, size_t *n);
 int ani_sketch_hits_end(ani_sketch *sk);
 
+/* ---- percentile bootstrap intervals of the ANI values (no counterpart in the reference: an ANI value is the mean of the pair's cells,
+ * and "95.1" from 1 600 cells prints like "95.1" from 40).  Between begin and end every call that reduces against
+ * the sketch (the calls of the profile's rule 5; ani_map_query adds nothing) appends one record per contributing pair to a list on the
+ * host, which take hands over.  Everything is integer and a stated counter-based hash.
+ *  1. Values.  For a pair (q, g), v[0 .. count - 1] are the non-empty cells of g's bins for q (a cell: the profile's rule 2), taken in bin
+ *     order, ascending bin number from genomeBinStart[g]; count is the row's countSeq.  F[i] = fix(v[i]), the profile's
+ *     fix(x) = (uint64_t) llrint((double) x * 2^20); sum = the sum of the F[i].
+ *  2. Gate: the profile's rule 3.  The pair contributes iff it has a row, countSeq >= minFragments and bits(identity) >= bits(minIdentity);
+ *     minIdentity in [0, 100] (-0.0 counts as 0), minFragments >= 1.
+ *  3. Draws.  fmix32 is MurmurHash3's 32-bit finalizer: h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16, all
+ *     arithmetic mod 2^32.  For replicate r in 0 .. B - 1 and draw j in 0 .. count - 1:
+ *       k(r) = fmix32(seed + 0x9e3779b9 (r + 1)),   u(r, j) = fmix32(k(r) ^ (0x85ebca6b (j + 1))),
+ *       idx(r, j) = ((uint64_t) u(r, j) * count) >> 32,   S[r] = the sum over j of F[idx(r, j)], a uint64 below 2^59.
+ *     The draws depend on (seed, r, j, count) only, not on the pair: common random numbers.  Two pairs with equal count resample the same
+ *     positions, so their intervals differ by their cells and not by their luck, and nothing depends on where a query sits in a sub-batch.
+ *  4. Interval.  L = levelPermille in 1 .. 999, lowRank = ((B - 1)(1000 - L)) / 2000 (integer division), highRank = B - 1 - lowRank.  With
+ *     S sorted ascending, lowSum = S[lowRank] and highSum = S[highRank]; low = (float)((double) lowSum / ((double) count * 1048576.0)), high
+ *     likewise (computed on the host).  Neither is clamped, and neither is forced to bracket the row's identity.  A pair whose cells are all
+ *     bit-equal has lowSum = highSum = sum; count = 1 is that case.
+ *  5. Ids and order: the distributions' rule 6.  The ids of the row the same call returned, in the rows' order, restricted to the gated
+ *     pairs; calls follow each other in call order.
+ *  6. Rows are untouched.  The profile, the distributions, the hits and the intervals can all be on together and do not see each other.
+ *  7. Determinism: the distributions' rule 8.  Nothing depends on schedule, sub-batch size, index chunking, residency or piece sizes.
+ * begin starts (a second begin drops what is pending and takes the new gate, B, L and seed).  take hands over everything appended since
+ * begin or the last take and empties the list: rec[n], released with ani_free; with n = 0 it comes back NULL.  48 bytes per record of host
+ * memory until taken.  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null sketch (or rec or n), a gate outside its ranges
+ * (NaN included), replicates outside 1 .. 1024, levelPermille outside 1 .. 999, take or end without a begin; a refused begin leaves a
+ * running mode as it was.  ANI_ERR_NOMEM: the records do not fit the host, or the device cannot hold a piece.  After a call that failed
+ * while reducing, the pending list is unspecified until the next begin. */
+typedef struct { int32_t refGenomeId, qryGenomeId; uint32_t count, replicates;
+                 uint64_t sum, lowSum, highSum; float low, high; } ani_ci_t;   /* 48 bytes */
+int ani_sketch_ci_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, int32_t replicates /* 1..1024 */,
+                        int32_t levelPermille /* 1..999 */, uint32_t seed);
+int ani_sketch_ci_take(ani_sketch *sk, ani_ci_t **rec, size_t *n);
+int ani_sketch_ci_end(ani_sketch *sk);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
