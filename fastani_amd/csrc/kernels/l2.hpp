@@ -642,16 +642,26 @@ __device__ __forceinline__ int l2_field_off(int g) { return kL2ByteInterleave ? 
 
 // The kernel is VALU-bound, so the event is applied with as few vector instructions as the arithmetic allows: the field change comes
 // ready-made in the event code; a counter that passes 127 is not intercepted but noticed afterwards (every new field value is OR-ed
-// into ovfAcc; bit 8 = a byte overflowed — the lane then computes garbage, harmlessly: iStar stays in [0, s] by construction, and the
+// into ovfAcc; bit 8 = a byte overflowed — the lane then computes garbage, harmlessly: every field it touches is one of its own, and the
 // candidate is redone by the general kernel); tot is carried instead of being re-added from two registers.
+//
+// When the pivot moves.  Between events the state keeps two invariants: tot = G(iStar) <= s, and iStar is maximal, i.e. iStar = s or
+// G(iStar + 1) = tot + 1 + n[iStar] > s (with iStar = s: tot = s, so tot + 1 + n[s] > s as well).  An event changes tot by one at the
+// most, so after an insert "tot > s" alone says that q_iStar left the s smallest, and after a delete "tot + 1 + n[iStar] <= s" alone
+// says that q_{iStar+1} joined them: an event that leaves both sides of the comparison as they were (a query hash, a gap beyond the
+// pivot, `on` = false) cannot satisfy it.  The tests the reference spells out beside it — not a query hash, idx < iStar for the
+// insert, iStar < s for the delete — are implied and not computed.  What they also did was to keep iStar inside [0, s] on a lane
+// that computes garbage (a byte overflowed, above); the index of the pivot-adjacent field is clamped to the fields of the class
+// instead (one v_med3 in place of the v_max that was there), and a lane without a candidate runs with s = 0, where nothing moves.
+template <int MAXS>
 __device__ __forceinline__ void l2_apply(uint8_t *F, L2Regs &r, uint32_t code, bool INS, bool on)
 {
-  const bool isQ = (code & 1u) != 0;
+  const int isQm = ((int)(code << 31)) >> 31;                        // all ones for a query hash
   const int idx = (int)((code >> 1) & 0x1ffu);
   const int d0 = ((int)(code << (32 - kL2DeltaShift - 3))) >> 29;     // sign-extended 3-bit field
   const int d = on ? d0 : 0;
   const int sg = INS ? 1 : -1;
-  int j = r.iStar - (INS ? 1 : 0); j = j < 0 ? 0 : j;               // pivot-adjacent field: n[j], b[j+1]
+  int j = r.iStar - (INS ? 1 : 0); j = j < 0 ? 0 : (j > MAXS ? MAXS : j);   // pivot-adjacent field: n[j], b[j+1]
   uint8_t *pOwn = F + l2_field_off(idx);
   const int own = *pOwn;
   int fj = F[l2_field_off(j)];
@@ -662,20 +672,19 @@ __device__ __forceinline__ void l2_apply(uint8_t *F, L2Regs &r, uint32_t code, b
   const int c1 = (fj >> 1) + 1;
   const bool lt = idx < r.iStar;                                     // rank idx+1 <= iStar  <=>  gap idx < iStar
   const int t = (on && lt) ? sg : 0;
-  r.shared += isQ ? t : 0;
-  r.tot += isQ ? 0 : t;
-  // insert: q_iStar leaves the s smallest iff rank idx+1 <= iStar and iStar + cStar > s;
-  // delete: q_{iStar+1} joins them iff iStar < s and iStar + cStar + 1 + n[iStar] <= s.  One comparison against s serves both.
-  const int reach = INS ? r.tot : r.tot + c1;
+  const int tq = t & isQm;
+  r.shared += tq;
+  r.tot += t - tq;
+  // insert: q_iStar leaves the s smallest iff iStar + cStar > s;
+  // delete: q_{iStar+1} joins them iff iStar + cStar + 1 + n[iStar] <= s.  One comparison against s serves both.
+  const int moved = r.tot + (INS ? -c1 : c1);                        // tot if the pivot moves over q and the n[] non-query hashes next to it
+  const int reach = INS ? r.tot : moved;
   const bool over = reach > r.s;
-  // insert: lt; delete: iStar < s (two selects and one comparison: cheaper than selecting between two flags)
-  const bool room = (INS ? idx : r.iStar) < (INS ? r.iStar : r.s);
-  const bool mv = on && !isQ && room && (over == INS);
-  const int mvm = -(int)mv;                                          // all ones if the pivot moves (masks, not selects: no branch around the rest)
-  const int mone = sg & mvm;                                         // insert: -1 on everything, delete: +1
+  const bool mv = over == INS;
+  const int mone = mv ? sg : 0;                                      // insert: -1 on everything, delete: +1
   r.iStar -= mone;
   r.shared -= mone & -(fj & 1);
-  r.tot -= (INS ? c1 : -c1) & mvm;                                   // the pivot moved over q and the n[] non-query hashes next to it
+  r.tot = mv ? moved : r.tot;
 }
 
 // slowFlag protocol: 0 = class A (pending or done), 4 = class B pending (s in 256..319), 8 = class B done, 16 = done without a
@@ -734,7 +743,7 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
   const int nHand = mine ? r.end0 - r.beg0 - 1 : 0;                   // inserts that arrive as state: the entries [beg0, end0 - 1)
   // The candidate's piece of the code buffer: state of the first super-window (k_l2_codes summed its inserts), then the events.
   const uint4 *p = (const uint4 *)((const uint16_t *)a.codes + (mine ? a.codeOff[i] : 0u));      // idle lanes read nothing
-  L2Regs R; R.s = mine ? a.g.fragS[a.g.candFrag[c]] : 1; R.ovfAcc = 0;
+  L2Regs R; R.s = mine ? a.g.fragS[a.g.candFrag[c]] : 0; R.ovfAcc = 0;     // s = 0: the pivot of a lane without a candidate never moves (l2_apply)
   // Four lanes share each state dword of the byte-interleaved layout, so every lane writes its fields, zeros if it has no candidate.
   // The pivot of the loaded state is found on the way, a dword (four ranks) at a time:
   //     iStar = max{i : G(i) <= s},  G(i) = i + sum_{g<i} n[g]  (strictly increasing),  tot = G(iStar),  shared = sum_{i<=iStar} b[i].
@@ -773,7 +782,16 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
     R.iStar = 4 * nFull + cnt; R.tot = R.iStar + below; R.shared = sh;
   }
   const int nBlk = (n + 7) >> 3;
-  int best = 0, begAtBest = -1, begAtLast = -1, steps = 0, delCount = 0;
+  // Result tracking (computeMap.hpp:468-476) without compares and selects.  Window starts never decrease along a stream, so the
+  // first evaluation that reaches the final best and the last evaluation at the final best are the smallest and the largest delCount
+  // among the evaluations whose shared equals the final best: each is one signed maximum over a packed key,
+  //     keyLast  = max(shared << 15 | delCount),     keyFirst = max(shared << 15 | (0x7fff - delCount))     (the same key ^ 0x7fff)
+  // (shared <= kL2FastMaxS < 2^9, delCount <= kL2FastMaxEntries < 0x7fff).  An event that is not evaluated has key -1, which is also
+  // the start value: "no evaluation at all" and "best stays 0" are told apart when the keys are unpacked behind the loop.
+  // noEvalCount: events of the stream that are not evaluated, counted once per block from the flag bits of its four words.
+  static_assert(kL2FastMaxS < (1 << 9) && kL2FastMaxEntries < 0x7fff, "packed result keys: shared << 15 | delCount");
+  static_assert(kL2NoEvalBit == 1u << 12, "run_block reads the flag as bit 12 of a code and as bit 4 of its high byte");
+  int keyLast = -1, keyFirst = -1, noEvalCount = 0, delCount = 0;
   // A lane without a candidate of this class (class-B and general-path candidates sit in the same length-ordered list; on the
   // benchmark, where 1.25 % of the fragments have s > 255, about one lane in eighty) reads no stream: its words stay zero — event 0 is "delete a non-query hash from field 0 and
   // evaluate", harmless on its own cleared state — so that it counts as PLAIN below instead of sending its whole wave through the
@@ -784,6 +802,17 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
   auto run_block = [&](auto plainTag, int blk, const L2Block &blkWords) {
     constexpr bool PLAIN = decltype(plainTag)::value;
     const uint32_t wd[4] = {blkWords[0], blkWords[1], blkWords[2], blkWords[3]};
+    {
+      // the high bytes of the eight codes, event e in byte e: bit 4 of a byte is the code's kL2NoEvalBit
+      const uint32_t hiA = perm_b32(wd[1], wd[0], 0x07050301u), hiB = perm_b32(wd[3], wd[2], 0x07050301u);
+      uint32_t mA = (kL2NoEvalBit >> 8) * 0x01010101u, mB = mA;
+      if (!PLAIN) {                                                   // only the lane's remaining events count
+        const int left = n - 8 * blk;
+        const uint64_t m = left >= 8 ? ~0ull : left <= 0 ? 0ull : (1ull << (8 * left)) - 1ull;
+        mA &= (uint32_t)m; mB &= (uint32_t)(m >> 32);
+      }
+      noEvalCount += __popc(hiA & mA) + __popc(hiB & mB);
+    }
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       const uint32_t code = (e & 1) ? (wd[e >> 1] >> 16) : (wd[e >> 1] & 0xffffu);
@@ -801,16 +830,15 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
           }
         }
       }
-      l2_apply(F, R, code, INS, eff);
-      delCount += (on && !INS) ? 1 : 0;
+      l2_apply<G::kMaxS>(F, R, code, INS, eff);
+      if (PLAIN) delCount = delCount + 1 - (INS ? 1 : 0);             // + !INS as one subtract-with-borrow on the mask INS already has
+      else delCount += (on && !INS) ? 1 : 0;
       // evaluate (computeMap.hpp:468-476) with the window starting at entry number delCount
-      const bool evl = on && (code & kL2NoEvalBit) == 0;
-      const int se = evl ? R.shared : -1;                             // best >= 0: an event without evaluation never compares
-      const bool better = se > best, tieOrBetter = se >= best;
-      best = better ? R.shared : best;
-      begAtBest = better ? delCount : begAtBest;
-      begAtLast = tieOrBetter ? delCount : begAtLast;
-      steps += evl ? 1 : 0;
+      int key = (int)(((uint32_t)R.shared << 15) | (uint32_t)delCount);
+      key |= ((int)(code << (31 - 12))) >> 31;                        // kL2NoEvalBit set: -1
+      if (!PLAIN) key = on ? key : -1;
+      keyLast = key > keyLast ? key : keyLast;
+      keyFirst = (key ^ 0x7fff) > keyFirst ? (key ^ 0x7fff) : keyFirst;   // (-1 ^ 0x7fff is negative too)
     }
   };
   // The first super-window does not fill here.  Its inserts [beg0, end0 - 1) are never evaluated (computeMap.hpp:448 inserts [beg,
@@ -835,6 +863,12 @@ static __global__ __launch_bounds__(kL2SimTPB) void k_l2_sim(L2FastArgs a, const
     if (R.ovfAcc & 0x100u) a.slowFlag[i] = 3;
     else {
       a.slowFlag[i] = (G::kMaxS == 255) ? 0 : 8;     // class B runs concurrently with class A: its "done" must not read as class A
+      // unpack the keys.  best stays 0: no evaluation was ever better than the start value, the first position stays unset, and
+      // the last position is that of the last evaluation (every one of them ties at 0), unset only if there was none.
+      const int best = keyLast >= 0 ? keyLast >> 15 : 0;
+      const int begAtBest = best > 0 ? 0x7fff - (keyFirst & 0x7fff) : -1;
+      const int begAtLast = keyLast >= 0 ? (keyLast & 0x7fff) : -1;
+      const int steps = n - noEvalCount;                              // every event of the stream was applied
       a.g.outBest[c] = best;
       a.g.outFirst[c] = begAtBest >= 0 ? a.g.mWpos[r.beg0 + begAtBest] : 0;
       a.g.outLast[c] = begAtLast >= 0 ? a.g.mWpos[r.beg0 + begAtLast] : 0;
