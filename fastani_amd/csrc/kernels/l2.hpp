@@ -409,13 +409,21 @@ constexpr int kL2HistWords = (kL2FastMaxS + 1) / 2;                   // one 16-
 constexpr int kL2StageEvents = kL2WaveWindow - 2 * kL2HistWords;      // events a wave stages in LDS (1728)
 static_assert(kL2HistWords == 2 * L2GeomB::kStateWords && (kL2HistWords & 3) == 0 && L2GeomB::kStateWords <= 2 * kWave, "histogram: two dwords per state dword, 16-byte multiple, two state dwords per lane");
 constexpr int kL2CandBatch = 40;            // candidates whose descriptors are fetched at once
+// A candidate as the waves of k_l2_codes take it up, derived from its L2Range where the descriptors are fetched (one thread per
+// candidate, vector arithmetic) and not by the wave that opens it (a serial chain on the scalar unit, once per candidate and wave):
+//   nEv    length of the event stream = its pad slot; < 0: no stream
+//   ent    first index entry (beg0); the range is the entries [0, m) from there
+//   nInit  entries of the first super-window: [0, nInit - 1) become state, the inserts of [nInit - 1, m - 1) events
+//   nDel   the entries [0, nDel) have a delete event
+//   oe     where the events start in the code buffer, in 16-bit entries (the state block sits in front of them)
+struct L2Cand { int32_t nEv; uint32_t ent, m, nInit, nDel, oe; };
+static_assert(sizeof(L2Cand) == sizeof(L2Range) + 8, "the LDS of k_l2_codes: no more than the raw descriptor and its 64-bit offset took");
 static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
 {
   __shared__ uint32_t qs[kL2FastMaxS + 2];
   __shared__ __attribute__((aligned(16))) uint32_t st2[kL2RankBuckets];
   __shared__ __attribute__((aligned(16))) uint16_t stageAll[(kTPB / kWave) * kL2WaveWindow];
-  __shared__ L2Range cRange[kL2CandBatch];         // the candidates' descriptors, fetched side by side (nEvents < 0: no stream)
-  __shared__ uint64_t cOff[kL2CandBatch];
+  __shared__ __attribute__((aligned(8))) L2Cand cands[kL2CandBatch];      // the candidates' descriptors, fetched side by side
   __shared__ int cRangeScan[8];                    // scratch of the workgroup scan
 #ifdef ANI_L2C_PAD_WORDS
   // occupancy experiment (profiles/r06h_l2_codes_occupancy_ab.txt): dead LDS, five workgroups per CU instead of six
@@ -438,13 +446,20 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
   // A candidate's descriptor is three dependent memory round trips away from its first hash (count -> range -> hashes); walked
   // candidate by candidate that chain was most of a workgroup's life.  All descriptors of the fragment are fetched here, together
   // with the sketch.
+  const bool classA = s <= L2GeomA::kMaxS && a.allowFast != 2;          // as k_l2_ranges decides it
+  const int stateWords = classA ? L2GeomA::kStateWords : L2GeomB::kStateWords;
   auto fetch_cands = [&](int32_t base) {
     const int32_t c = base + (int32_t)threadIdx.x;
     if ((int)threadIdx.x < kL2CandBatch && c < cB) {
       const int32_t i = c - a.c0;
-      L2Range r = a.ranges[i];
-      if (a.codeCount[i] == 0) r.nEvents = -1;
-      cRange[threadIdx.x] = r; cOff[threadIdx.x] = a.codeOff[i];
+      const L2Range r = a.ranges[i];
+      L2Cand d;
+      d.nEv = a.codeCount[i] == 0 ? -1 : r.nEvents;
+      d.ent = (uint32_t)r.beg0; d.m = (uint32_t)(r.last - r.beg0); d.nInit = (uint32_t)(r.end0 - r.beg0);
+      // events = the inserts of [nInit - 1, m - 1) and the deletes of [0, nDel)
+      d.nDel = (uint32_t)r.nEvents + d.nInit - d.m;
+      d.oe = a.codeOff[i] + (uint32_t)(2 * stateWords);
+      cands[threadIdx.x] = d;
     }
   };
   fetch_cands(cA);
@@ -455,71 +470,61 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
   const int lane = threadIdx.x & (kWave - 1), wv = wave_uniform((int32_t)(threadIdx.x >> 6));
   uint32_t *hist = (uint32_t *)(stageAll + wv * kL2WaveWindow);
   uint16_t *stage = stageAll + wv * kL2WaveWindow + 2 * kL2HistWords;
-  const bool classA = s <= L2GeomA::kMaxS && a.allowFast != 2;          // as k_l2_ranges decides it
-  const int stateWords = classA ? L2GeomA::kStateWords : L2GeomB::kStateWords;
-  // a lane owns the counters of the state dwords `lane` and `lane + 64` (class B: 80 dwords): it clears them here, and again when it
-  // has read them; class A never touches the others (rank <= s <= 255)
-  for (int x = lane; x < stateWords; x += kWave) { hist[2 * x] = 0u; hist[2 * x + 1] = 0u; }
+  static_assert(L2GeomA::kStateWords == kWave, "class A: one state dword per lane");
+  // a lane owns the counters of the state dwords `lane` and `lane + 64` (class B: 80 dwords, a second round of 16 lanes): it clears
+  // them here, and again when it has read them; class A never touches the others (rank <= s <= 255)
+  hist[2 * lane] = 0u; hist[2 * lane + 1] = 0u;
+  if (lane + kWave < stateWords) { hist[2 * (lane + kWave)] = 0u; hist[2 * (lane + kWave) + 1] = 0u; }
   ANI_WAVE_SYNC();
-  // Work items of this wave = (candidate, pass of 4 * 64 entries), in order.  Everything in an item is wave-uniform and kept in
-  // scalar registers (wave_uniform): the item loop then branches on scalars and the per-entry bounds tests take scalar operands.
-  struct Item {
-    int32_t c; uint32_t jb;                          // candidate, first entry of the pass
-    char *ob; const char *hb, *wb;                   // wave-uniform bases: event stream, hashes, window links (32-bit byte offsets per lane)
-    uint32_t m, nInit, nInsAll, nDel, dump; bool staged, lastPass;
-    uint32_t K; int32_t beg0;                        // entries [0, K) = [beg0, end0 - 1) become state, not events
-  };
+  // A wave works through its candidates in passes of 4 * 64 entries.  The candidate is a handful of wave-uniform values in scalar
+  // registers (Cand: what L2Cand holds; everything else — K, the stream's address, staged, the last pass — is one or two scalar
+  // instructions from them where it is used) and stays where it is from pass to pass; only the pass's first entry moves.  The loads
+  // of the next pass, or of the next candidate's first, are in flight while the current pass is ranked.
+  struct Cand { int32_t c, nEv; uint32_t ent, m, nInit, nDel, oe; };
   constexpr uint32_t kPass = 4u * kWave;
   int32_t batch0 = cA, batch1 = cA + kL2CandBatch < cB ? cA + kL2CandBatch : cB;      // candidates whose descriptors are in LDS
-  auto open_cand = [&](int32_t c, Item &it) -> bool {          // first candidate >= c of this wave (within the batch) that has a stream
+  auto open_cand = [&](int32_t c, Cand &it) -> bool {          // first candidate >= c of this wave (within the batch) that has a stream
     for (; c < batch1; c += kTPB / kWave) {
-      L2Range r = cRange[c - batch0];
-      r.nEvents = wave_uniform(r.nEvents);
-      if (r.nEvents < 0) continue;
-      r.beg0 = wave_uniform(r.beg0); r.end0 = wave_uniform(r.end0); r.last = wave_uniform(r.last);
-      it.c = c; it.jb = 0;
-      it.ob = (char *)((uint16_t *)a.codes + wave_uniform(cOff[c - batch0]) + (uint64_t)(2 * stateWords));
-      it.hb = (const char *)(a.g.mHash + r.beg0); it.wb = (const char *)(a.g.mWin + r.beg0);
-      it.m = (uint32_t)(r.last - r.beg0);
-      it.nInit = (uint32_t)(r.end0 - r.beg0); it.nInsAll = it.m - 1;          // inserts (first window included) are the entries [0, m-1)
-      it.K = it.nInit - 1u; it.beg0 = r.beg0;
-      it.nDel = (uint32_t)r.nEvents + it.K - it.nInsAll;                      // deletes are the entries [0, nDel)
-      it.dump = (uint32_t)r.nEvents;                                          // pad slot
-      it.staged = (uint32_t)r.nEvents < (uint32_t)kL2StageEvents;
-      it.lastPass = kPass >= it.m;
+      const L2Cand d = cands[c - batch0];
+      const int32_t nEv = wave_uniform(d.nEv);
+      if (nEv < 0) continue;
+      it.c = c; it.nEv = nEv;
+      it.ent = wave_uniform(d.ent); it.m = wave_uniform(d.m); it.nInit = wave_uniform(d.nInit); it.nDel = wave_uniform(d.nDel);
+      it.oe = wave_uniform(d.oe);
       return true;
     }
     return false;
   };
-  auto next_item = [&](const Item &cur, Item &nx) -> bool {
-    if (!cur.lastPass) { nx = cur; nx.jb = cur.jb + kPass; nx.lastPass = nx.jb + kPass >= nx.m; return true; }
-    return open_cand(cur.c + kTPB / kWave, nx);
-  };
-  auto load_item = [&](const Item &it, uint32_t (&h)[4], uint32_t (&wl)[4]) {
+  auto load_pass = [&](uint32_t ent, uint32_t m, uint32_t jb, uint32_t (&h)[4], uint32_t (&wl)[4]) {
+    // wave-uniform bases, 32-bit byte offsets per lane
+    const char *hb = (const char *)(a.g.mHash + ent), *wb = (const char *)(a.g.mWin + ent);
+    const uint32_t last = m - 1u;                    // m >= 1: entries beyond the range read the last one
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      const uint32_t x = it.jb + lane + e * kWave;
-      const uint32_t off = (x < it.m ? x : it.m - 1) * 4u;
-      h[e] = *(const uint32_t *)(it.hb + off); wl[e] = *(const uint32_t *)(it.wb + off);
+      const uint32_t x = (jb + (uint32_t)(e * kWave)) + (uint32_t)lane;
+      const uint32_t off = (x < last ? x : last) * 4u;
+      h[e] = *(const uint32_t *)(hb + off); wl[e] = *(const uint32_t *)(wb + off);
     }
   };
-  Item cur, nxt;
+  Cand cur = {0, 0, 0u, 0u, 0u, 0u, 0u}, nxt = cur;
   for (;;) {
   bool have = open_cand(batch0 + wv, cur);
   uint32_t h[4], wl[4], hn[4], wn[4];
-  if (have) load_item(cur, h, wl);
+  if (have) load_pass(cur.ent, cur.m, 0u, h, wl);
+  uint32_t jb = 0u;                                  // first entry of the pass
   while (have) {
-    const bool haveNext = next_item(cur, nxt);
-    if (haveNext) load_item(nxt, hn, wn);
-    // A pass ranks up to four entries per lane; the last pass of a candidate takes only as many as are left (a candidate of the
-    // benchmark has ~600 entries: 256 + 256 + 92 — at four per lane whatever is left, a fifth of all the work was done on entries
-    // beyond the range).  E is wave-uniform: a scalar branch picks the variant.
-    auto pass_body = [&](auto eTag) {
+    // entries [0, K) become state, not events; the inserts of the stream are the entries [K, m - 1); the pad slot sits behind it
+    const uint32_t K = cur.nInit - 1u, nIns = cur.m - cur.nInit, dumpSlot = (uint32_t)cur.nEv;
+    const bool staged = (uint32_t)cur.nEv < (uint32_t)kL2StageEvents;
+    char *const ob = (char *)((uint16_t *)a.codes + cur.oe);
+    const bool lastPass = jb + kPass >= cur.m;
+    // what comes next: the candidate's next pass, or the first pass of the wave's next candidate; one place loads either
+    bool more = true;
+    if (lastPass) more = open_cand(cur.c + kTPB / kWave, nxt);
+    if (more) load_pass(lastPass ? nxt.ent : cur.ent, lastPass ? nxt.m : cur.m, lastPass ? 0u : jb + kPass, hn, wn);
+    // Rank = entries of the sketch below h (l2_rank_fast; the rare deep buckets behind a wave vote).
+    auto rank_all = [&](auto eTag, uint32_t (&rk)[4]) {
       constexpr int E = decltype(eTag)::value;
-      // Rank = entries of the sketch below h.  The two sketch entries at the bucket's start decide it unless the bucket holds more
-      // than two and both are below h: entries behind the bucket's own belong to later buckets, i.e. are larger than any hash of
-      // this bucket, so they need no "is it in the bucket" test (the sketch is followed by two 0xffffffff sentinels).
-      uint32_t rk[4];
       uint32_t deep = 0;
   #pragma unroll
       for (int e = 0; e < E; e++) rk[e] = l2_rank_fast(qs, st2, sh, h[e], deep);
@@ -527,97 +532,135 @@ static __global__ __launch_bounds__(kTPB) void k_l2_codes(L2FastArgs a)
   #pragma unroll
         for (int e = 0; e < E; e++) rk[e] = l2_rank_deep(qs, st2, sh, s, h[e], rk[e]);
       }
-      // entries of the first super-window (all but its last): into the histogram.  Wave-uniform branch; per-lane predicate — the
-      // window can end anywhere in a pass and span several.  An entry whose hash already sits in [beg0, it) adds nothing
-      // (slidingMap.hpp:150-154); those are rare and looked up behind a wave vote.
+    };
+    // The pass beyond the first super-window of a staged stream (jb >= K: in the benchmark two of a candidate's three passes).  No
+    // entry is handed over, so there is no histogram and no test per slot: both events of all E slots are computed and stored
+    // unconditionally; an event that does not exist (entries beyond the range, the never-inserted last entry, entries that never
+    // leave) goes to the pad slot.  The formulas are those of pass_general, which explains them.
+    auto pass_beyond = [&](auto eTag) {
+      constexpr int E = decltype(eTag)::value;
+      uint32_t rk[4];
+      rank_all(eTag, rk);
+  #pragma unroll
+      for (int e = 0; e < E; e++) {
+        const uint32_t x = (jb + (uint32_t)(e * kWave)) + (uint32_t)lane;
+        const uint32_t cd = rk[e] | ((wl[e] >> 21) & kL2DupBit);
+        const uint32_t mq = 0u - (rk[e] & 1u);
+        const int32_t db = (int32_t)x - (int32_t)(wl[e] & kWinMask) - 1;
+        const uint32_t pi = x - K < nIns ? x - K + (uint32_t)(db < 0 ? 0 : db) : dumpSlot;
+        const uint32_t ib = x + ((wl[e] >> kWinShiftA) & kWinMask);
+        const uint32_t pd = x < cur.nDel ? x + (ib < cur.nInit ? cur.nInit : ib) - K : dumpSlot;
+        stage[pi] = (uint16_t)((cd | kL2InsBit | (2u << kL2DeltaShift)) ^ (mq & (3u << kL2DeltaShift)));
+        stage[pd] = (uint16_t)(cd | ((wl[e] >> 18) & kL2NoEvalBit) | (6u << kL2DeltaShift) | (mq & (1u << kL2DeltaShift)));
+      }
+    };
+    // The general form: any pass, and the only one for passes that touch the first super-window (jb < K) or store directly.  A pass
+    // ranks up to four entries per lane; the last pass of a candidate takes only as many as are left.  E is wave-uniform: a scalar
+    // branch picks the variant.
+    auto pass_general = [&](auto eTag) {
+      constexpr int E = decltype(eTag)::value;
+      uint32_t rk[4];
+      rank_all(eTag, rk);
+      // entries of the first super-window (all but its last): into the histogram.  Per-lane predicate — the window can end anywhere
+      // in a pass and span several.  An entry whose hash already sits in [beg0, it) adds nothing (slidingMap.hpp:150-154); those are
+      // rare and looked up behind a wave vote.
       // The 64 entries of a slot e are all inside the window, all outside, or (one slot per candidate) split: wave-uniform tests.
-      if (cur.jb < cur.K) {
+      {
         uint32_t dl[4] = {0u, 0u, 0u, 0u}; uint32_t dupAny = 0;
   #pragma unroll
         for (int e = 0; e < E; e++) {
-          const uint32_t x0 = cur.jb + e * kWave;
-          if (x0 >= cur.K) continue;
+          const uint32_t x0 = jb + e * kWave;
+          if (x0 >= K) continue;
           const uint32_t d = 2u - (rk[e] & 1u);
-          if (x0 + kWave <= cur.K) { dl[e] = d; dupAny |= wl[e]; }
-          else { const bool in = x0 + lane < cur.K; dl[e] = in ? d : 0u; dupAny |= in ? wl[e] : 0u; }
+          if (x0 + kWave <= K) { dl[e] = d; dupAny |= wl[e]; }
+          else { const bool in = x0 + lane < K; dl[e] = in ? d : 0u; dupAny |= in ? wl[e] : 0u; }
         }
         if (__any((dupAny & kWinDupBit) != 0)) {
   #pragma unroll
           for (int e = 0; e < E; e++)
-            if (dl[e] && (wl[e] & kWinDupBit) && dup_prev(a.g.dup, (uint32_t)cur.beg0 + cur.jb + lane + e * kWave) >= cur.beg0) dl[e] = 0u;
+            if (dl[e] && (wl[e] & kWinDupBit) && dup_prev(a.g.dup, (cur.ent + jb + (uint32_t)(e * kWave)) + (uint32_t)lane) >= (int32_t)cur.ent) dl[e] = 0u;
         }
   #pragma unroll
         for (int e = 0; e < E; e++)                                                         // (adding 0 is cheaper than a branch around it)
-          if (cur.jb + e * kWave < cur.K) atomicAdd(&hist[rk[e] >> 2], dl[e] << ((rk[e] & 2u) << 3));
+          if (jb + e * kWave < K) atomicAdd(&hist[rk[e] >> 2], dl[e] << ((rk[e] & 2u) << 3));
       }
       // Two events per entry, stored without control flow: an event that does not exist (entries beyond the range, the never-inserted
       // last entry, entries that never leave, the inserts handed over as state) goes to the pad slot behind the stream (k_l2_ranges
       // reserves one).  Places are those of the merged stream less the K inserts in front of it.  A slot whose 64 entries are all
       // handed over (wave-uniform) has no insert events at all: neither computed nor stored.
-      uint32_t pi[4], pd[4]; uint16_t ci[4], cdl[4];
-      const uint32_t dumpSlot = cur.dump;
-  #pragma unroll
-      for (int e = 0; e < E; e++) {
-        const uint32_t x = cur.jb + lane + e * kWave;
+      // Each slot stores its events before the next one computes its own (the stores keep the slots apart: the live values of one
+      // slot at a time, not of four).
+      auto slot = [&](int e, auto directTag) {
+        constexpr bool DIRECT = decltype(directTag)::value;
+        const uint32_t x = (jb + (uint32_t)(e * kWave)) + (uint32_t)lane;
         const uint32_t cd = rk[e] | ((wl[e] >> 21) & kL2DupBit);                          // kWinDupBit (bit 31) -> kL2DupBit (bit 10)
         // field change of the event, 3-bit two's complement: insert +2 (010), of a query hash +1 (001); delete -2 (110) / -1 (111)
         const uint32_t mq = 0u - (rk[e] & 1u);                                            // all ones for a query hash
         // insert of entry x: after the inserts of the entries before it and the deletes of the entries up to x - B - 2
-        pi[e] = dumpSlot; ci[e] = 0;
-        if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) {
+        if (jb + (uint32_t)(e + 1) * kWave > K) {
           const int32_t db = (int32_t)x - (int32_t)(wl[e] & kWinMask) - 1;               // deletes that precede it
-          pi[e] = x - cur.K < cur.nInsAll - cur.K ? x - cur.K + (uint32_t)(db < 0 ? 0 : db) : dumpSlot;
-          ci[e] = (uint16_t)((cd | kL2InsBit | (2u << kL2DeltaShift)) ^ (mq & (3u << kL2DeltaShift)));
+          const uint32_t pi = x - K < nIns ? x - K + (uint32_t)(db < 0 ? 0 : db) : dumpSlot;
+          const uint16_t ci = (uint16_t)((cd | kL2InsBit | (2u << kL2DeltaShift)) ^ (mq & (3u << kL2DeltaShift)));
+          if constexpr (DIRECT) *(uint16_t *)(ob + pi * 2u) = ci; else stage[pi] = ci;
         }
         // delete of entry x: after the deletes of the entries before it and the inserts of the entries below x + A (at least the first
         // window's)
         const uint32_t ib = x + ((wl[e] >> kWinShiftA) & kWinMask);
-        pd[e] = x < cur.nDel ? x + (ib < cur.nInit ? cur.nInit : ib) - cur.K : dumpSlot;
+        const uint32_t pd = x < cur.nDel ? x + (ib < cur.nInit ? cur.nInit : ib) - K : dumpSlot;
         // kWinMoreBit (bit 30) -> kL2NoEvalBit (bit 12)
-        cdl[e] = (uint16_t)(cd | ((wl[e] >> 18) & kL2NoEvalBit) | (6u << kL2DeltaShift) | (mq & (1u << kL2DeltaShift)));
-      }
-      if (cur.staged) {                                                                   // wave-uniform choice
+        const uint16_t cdl = (uint16_t)(cd | ((wl[e] >> 18) & kL2NoEvalBit) | (6u << kL2DeltaShift) | (mq & (1u << kL2DeltaShift)));
+        if constexpr (DIRECT) *(uint16_t *)(ob + pd * 2u) = cdl; else stage[pd] = cdl;
+      };
+      if (staged) {                                                                       // wave-uniform choice
   #pragma unroll
-        for (int e = 0; e < E; e++) { if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) stage[pi[e]] = ci[e]; stage[pd[e]] = cdl[e]; }
+        for (int e = 0; e < E; e++) slot(e, std::false_type());
       } else {
   #pragma unroll
-        for (int e = 0; e < E; e++) { if (cur.jb + (uint32_t)(e + 1) * kWave > cur.K) *(uint16_t *)(cur.ob + pi[e] * 2u) = ci[e]; *(uint16_t *)(cur.ob + pd[e] * 2u) = cdl[e]; }
+        for (int e = 0; e < E; e++) slot(e, std::true_type());
       }
     };
     {
-      const uint32_t left = cur.m - cur.jb;          // entries from the first of this pass to the end of the range (>= 1)
-      if (left > 3u * kWave) pass_body(std::integral_constant<int, 4>());
-      else if (left > 2u * kWave) pass_body(std::integral_constant<int, 3>());
-      else if (left > (uint32_t)kWave) pass_body(std::integral_constant<int, 2>());
-      else pass_body(std::integral_constant<int, 1>());
+      const uint32_t left = cur.m - jb;              // entries from the first of this pass to the end of the range (>= 1)
+      if (jb >= K && staged) {
+        if (left > 3u * kWave) pass_beyond(std::integral_constant<int, 4>());
+        else if (left > 2u * kWave) pass_beyond(std::integral_constant<int, 3>());
+        else if (left > (uint32_t)kWave) pass_beyond(std::integral_constant<int, 2>());
+        else pass_beyond(std::integral_constant<int, 1>());
+      } else {                                       // ranges that end inside such a pass are short or very long: fewer copies of the larger form
+        if (left > 2u * kWave) pass_general(std::integral_constant<int, 4>());
+        else if (left > (uint32_t)kWave) pass_general(std::integral_constant<int, 2>());
+        else pass_general(std::integral_constant<int, 1>());
+      }
     }
     // the passes over the first super-window are done (once per candidate: the first pass that reaches entry K)
-    if (cur.jb + kPass >= cur.K && (cur.jb == 0u || cur.jb < cur.K)) {
+    if (jb + kPass >= K && (jb == 0u || jb < K)) {
       ANI_WAVE_SYNC();
-      uint32_t *state = (uint32_t *)cur.ob - stateWords;
-      uint32_t ovf = 0;
-      for (int x = lane; x < stateWords; x += kWave) {               // state dword x = fields 4x .. 4x+3; class B: a second round of 16 lanes
-        const uint32_t c0 = hist[2 * x], c1 = hist[2 * x + 1];
-        hist[2 * x] = 0u; hist[2 * x + 1] = 0u;                      // for the wave's next candidate
-        ovf |= (c0 | c1) & 0xff00ff00u;
-        state[x] = perm_b32(c1, c0, 0x06040200u);                    // the low bytes of the four counters
-      }
+      char *const state = ob - 4 * stateWords;       // wave-uniform base, 32-bit byte offsets per lane
+      // state dword x = fields 4x .. 4x+3
+      auto pack = [&](uint32_t x) -> uint32_t {
+        const uint32_t c0 = hist[2u * x], c1 = hist[2u * x + 1u];
+        hist[2u * x] = 0u; hist[2u * x + 1u] = 0u;                   // for the wave's next candidate
+        *(uint32_t *)(state + x * 4u) = perm_b32(c1, c0, 0x06040200u);      // the low bytes of the four counters
+        return (c0 | c1) & 0xff00ff00u;
+      };
+      uint32_t ovf = pack((uint32_t)lane);
+      if (lane + kWave < stateWords) ovf |= pack((uint32_t)(lane + kWave));       // class B: a second round of 16 lanes
       // the simulation would have overflowed this byte while the window fills
       if (__any(ovf != 0) && lane == 0) a.slowFlag[cur.c - a.c0] = 3;
       ANI_WAVE_SYNC();
     }
-    if (cur.staged && cur.lastPass) {                // the candidate's stream is complete in the window: write it out
-      ANI_WAVE_SYNC();
-      const uint32_t nOut = (cur.dump + 8u) & ~7u;   // = codeCount: the stream and its pad, whole 16-byte pieces
-      for (uint32_t o = (uint32_t)lane * 8u; o < nOut; o += kWave * 8u) *(uint4 *)(cur.ob + o * 2u) = *(const uint4 *)(stage + o);
-      ANI_WAVE_SYNC();                               // the window is reused by the next candidate
-    }
-    have = haveNext;
-    if (have) {
-      cur = nxt;
+    if (lastPass) {
+      if (staged) {                                  // the candidate's stream is complete in the window: write it out
+        ANI_WAVE_SYNC();
+        const uint32_t nOut = (dumpSlot + 8u) & ~7u; // = codeCount: the stream and its pad, whole 16-byte pieces
+        for (uint32_t o = (uint32_t)lane * 8u; o < nOut; o += kWave * 8u) *(uint4 *)(ob + o * 2u) = *(const uint4 *)(stage + o);
+        ANI_WAVE_SYNC();                             // the window is reused by the next candidate
+      }
+      have = more;
+      if (more) { cur = nxt; jb = 0u; }
+    } else jb += kPass;
 #pragma unroll
-      for (int e = 0; e < 4; e++) { h[e] = hn[e]; wl[e] = wn[e]; }
-    }
+    for (int e = 0; e < 4; e++) { h[e] = hn[e]; wl[e] = wn[e]; }
   }
   if (batch1 >= cB) break;                         // workgroup-uniform; fragments with more candidates than a batch are rare
   block_barrier();
