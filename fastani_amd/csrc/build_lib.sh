@@ -2,8 +2,9 @@
 # Builds libfastani_amd.so for gfx950 from its units (host/engine.hpp lists them), one hipcc per unit, in parallel.
 # (engine_l2 is compiled with its own scheduling strategy, see unit_flags below.)
 #
-# ANI_ASM_PEEPHOLE=1 routes the device code of engine_map.hip (the L2 simulation lives there) through a one-line assembly peephole
-# between hipcc's code generation and the assembler:
+# ANI_ASM_PEEPHOLE=1 routes the device code of engine_map.hip (L1, the L2 stage around its two main kernels, the reducer; k_l2_codes and
+# k_l2_sim are engine_l2.hip's now and are not touched) through a one-line assembly peephole between hipcc's code generation and the
+# assembler:
 #     v_cndmask_b32_e32 vD, a, vB, vcc   ->   v_cndmask_b32_e64 vD, a, vB, vcc
 # On MI355X two VOP2-encoded v_cndmask_b32 issued back to back on one SIMD cost ~18-22 cycles each instead of 4
 # (tools/ubench/valu.hip, profiles/r02_ubench_valu.txt: "1 v_cmp + 7 v_cndmask_e32" 16 cycles per instruction, the VOP3 encoding
@@ -15,7 +16,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 LLVM=${LLVM_BIN:-/opt/rocm/lib/llvm/bin}
 OUT=${1:-$HERE/libfastani_amd.so}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC ${ANI_EXTRA_FLAGS:-}"
-UNITS="engine_core engine_ingest engine_sketch engine_index engine_map engine_l2 sort_device prim_check"
+UNITS="engine_core engine_ingest engine_sketch engine_index engine_map engine_graph engine_sig engine_l2 sort_device prim_check"
 # per-unit flags: the L2 codes / simulation kernels with the max-ILP scheduler (engine_l2.hip says why); ANI_L2_UNIT_FLAGS="" builds them like the rest
 unit_flags() { if [ "$1" = "engine_l2" ]; then echo "${ANI_L2_UNIT_FLAGS--mllvm -amdgpu-sched-strategy=max-ilp}"; fi; }
 T=$(mktemp -d)

@@ -1,12 +1,8 @@
 // engine_map.hip — mapping and reduction: L1 seed lookup + candidate regions, L2 sliding MinHash, identity filter
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
-// src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets; and the greedy
-// clustering of the rows it produces (ani_cluster_greedy, kernels/cluster.hpp) and their trees: average linkage (ani_tree_average,
-// kernels/tree.hpp), neighbour joining (ani_tree_nj, kernels/nj.hpp) and single linkage with its minimum spanning tree (ani_tree_single,
-// kernels/single.hpp); and the whole-genome sketch estimate that fills the pairs the
-// mapping leaves without a row: signatures of the reference genomes and their all-pairs comparison (ani_sketch_signatures,
-// ani_signature_pairs, kernels/sigdist.hpp), with its streamed consumers: neighbours, screens, the greedy clustering of
-// ani_signature_cluster and ani_signature_cluster_contain (kernels/sigcluster.hpp) and the pair graph of ani_signature_graph (kernels/siggraph.hpp).
+// src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets, with the
+// record modes of the reducer (profile, fragment distributions, best hits, bootstrap intervals).  What works on the finished rows
+// (clustering, trees) is engine_graph.hip; the whole-genome sketch estimate is engine_sig.hip.
 #include <atomic>
 #include <thread>
 #include "host/engine.hpp"
@@ -17,17 +13,6 @@
 #include "kernels/fragdist.hpp"
 #include "kernels/ci.hpp"
 #include "kernels/hits.hpp"
-#include "kernels/cluster.hpp"
-#include "kernels/tree.hpp"
-#include "kernels/nj.hpp"
-#include "kernels/single.hpp"
-#include "kernels/sigdist.hpp"
-#include "kernels/sigstrip.hpp"
-#include "kernels/signeigh.hpp"
-#include "kernels/sigscreen.hpp"
-#include "kernels/sigcontain.hpp"
-#include "kernels/sigcluster.hpp"
-#include "kernels/siggraph.hpp"
 
 namespace anih {
 using namespace ani;
@@ -949,1316 +934,6 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   }
   return ANI_OK;
 }
-// ---- greedy clustering of the pair graph (ani_cluster_greedy) ----
-// Device memory per row: 20 (rows) + 2 x 12 (keys and positions) + 12 (the sort's ping-pong) bytes at the peak, the 12-byte edge list
-// after the sort's inputs are gone; per edge end 8 (CSR); per genome 40.  Every buffer is the pool's and goes back to it on return.
-int cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float minIdentity, int32_t *representative, float *identityToRep)
-{
-  for (int32_t i = 0; i < nG; i++) { representative[i] = i; identityToRep[i] = 0.0f; }
-  if (n == 0) return ANI_OK;
-  // every buffer goes back to the pool on return (the launches below take plain pointers, never the holder)
-  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, E_LO, E_HI, E_W, LOW, HIGH, DEG, FILL, OFF, NBR, NBR_W, STATE, REP, REP_W, FLAGS, SORT, NBUF };
-  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
-  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
-  hipStream_t st = ctx->stream;
-  int b = 1;
-  while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
-  const size_t V = (size_t)nG;
-  ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB, *flags, *off, *state; int32_t *lowDeg, *highDeg, *deg, *fill, *rep; float *repW;
-  TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
-  TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB)); TRY(buf(FLAGS, 64, (void **)&flags));
-  TRY(buf(LOW, V * 4, (void **)&lowDeg)); TRY(buf(HIGH, V * 4, (void **)&highDeg)); TRY(buf(DEG, V * 4, (void **)&deg));
-  TRY(buf(FILL, V * 8, (void **)&fill)); TRY(buf(OFF, V * 4 + 4, (void **)&off)); TRY(buf(STATE, V * 4, (void **)&state));
-  TRY(buf(REP, V * 4, (void **)&rep)); TRY(buf(REP_W, V * 4, (void **)&repW));
-  // flags: [0] a bad id, [1] the edge count, [2..3] the undecided counters of the rounds
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-
-  // one upload; keys; the stable sort puts the rows of a pair next to each other in the order given
-  HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-  HIP_TRY(hipMemsetAsync(lowDeg, 0, V * 4, st)); HIP_TRY(hipMemsetAsync(highDeg, 0, V * 4, st));
-  hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0]) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
-  size_t tb = 0;
-  int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
-  void *sortTmp = nullptr;
-  if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
-  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
-  B.b[SORT].release(); B.b[KEYS_A].release(); B.b[VALS_A].release();
-
-  // fold + threshold -> edge list (at most one edge per sorted row) and the degrees
-  int32_t *eLo, *eHi; float *eW;
-  TRY(buf(E_LO, n * 4, (void **)&eLo)); TRY(buf(E_HI, n * 4, (void **)&eHi)); TRY(buf(E_W, n * 4, (void **)&eW));
-  hipLaunchKernelGGL(k_cluster_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                     (uint64_t)n, b, minIdentity, flags + 1, eLo, eHi, eW, lowDeg, highDeg);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, flags + 1, 4, hipMemcpyDeviceToHost, st));
-  hipLaunchKernelGGL(k_cluster_degrees, dim3(grid_for(V)), dim3(256), 0, st, nG, (const int32_t *)lowDeg, (const int32_t *)highDeg, deg, fill);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  const uint32_t nE = host[0];
-  if (nE == 0) return ANI_OK;                          // no edge: every genome is its own representative
-  B.b[ROWS].release(); B.b[KEYS_B].release(); B.b[VALS_B].release();
-
-  // CSR over both directions: offsets = prefix sum of the degrees (device_scan: ANI_ERR_LIMIT beyond 2^32 - 16 entries)
-  uint64_t total = 0;
-  TRY(device_scan(ctx, deg, off, (uint32_t)V, &total));
-  const uint32_t tot32 = (uint32_t)total;
-  HIP_TRY(hipMemcpyAsync(off + V, &tot32, 4, hipMemcpyHostToDevice, st));
-  int32_t *nbr; float *nbrW;
-  TRY(buf(NBR, (size_t)total * 4, (void **)&nbr)); TRY(buf(NBR_W, (size_t)total * 4, (void **)&nbrW));
-  hipLaunchKernelGGL(k_cluster_scatter, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)eLo, (const int32_t *)eHi, (const float *)eW,
-                     (const uint32_t *)off, (const int32_t *)lowDeg, fill, nbr, nbrW);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(state, 0, V * 4, st));
-
-  // greedy rounds: batches of kRounds launches; the last launch of a batch counts the undecided vertices, the count is copied back
-  // asynchronously and read while the next batch runs (a batch after the last one with work only finds decided vertices)
-  constexpr int kRounds = 8;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-  if (hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(ANI_ERR_DEVICE, "hipEventCreate failed"); }
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } evGuard{ev};
-  const unsigned grid = grid_for(V, kTPB);
-  // every launch decides at least the lowest undecided vertex (its lower neighbours were all decided before the launch started)
-  const uint64_t maxBatches = V / kRounds + 3;
-  bool done = false;
-  for (uint64_t batch = 0; !done; batch++) {
-    if (batch > maxBatches) return fail(ANI_ERR_INTERNAL, "greedy rounds did not converge after %llu launches", (unsigned long long)(batch * kRounds));
-    const int slot = (int)(batch & 1);
-    uint32_t *und = flags + 2 + slot;
-    HIP_TRY(hipMemsetAsync(und, 0, 4, st));
-    for (int r = 0; r < kRounds; r++) {
-      uint32_t *count = r == kRounds - 1 ? und : nullptr;
-      hipLaunchKernelGGL(k_cluster_round, dim3(grid), dim3(kTPB), 0, st, nG, (const uint32_t *)off, (const int32_t *)lowDeg, (const int32_t *)nbr, state, count);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host + 2 + slot, und, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ev[slot], st));
-    if (batch > 0) { HIP_TRY(hipEventSynchronize(ev[slot ^ 1])); done = host[2 + (slot ^ 1)] == 0; }
-  }
-  hipLaunchKernelGGL(k_cluster_assign, dim3(grid), dim3(kTPB), 0, st, nG, (const uint32_t *)off, (const int32_t *)nbr, (const float *)nbrW,
-                     (const uint32_t *)state, rep, repW);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(representative, rep, V * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(identityToRep, repW, V * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return ANI_OK;
-}
-
-// ---- average-linkage (UPGMA) tree of the pair values (ani_tree_average) ----
-// Device memory: 4 bytes per matrix cell (n x ld, ld = n rounded up to 64) plus 40 per genome; per row 20 + 2 x 12 + 12 bytes while the
-// pairs are folded, all of it released before the merges.  The merges are a plain enqueue loop, one k_tree_merge per merge, each
-// reading its pair from device memory; the result is copied back once at the end.  Every buffer is the pool's and goes back on return.
-int tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height)
-{
-  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, DMAT, ROWMIN, STATE, PART, OUT, NBUF };
-  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
-  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG, M = V - 1;
-  const uint64_t ld = ((uint64_t)nG + 63) & ~63ull;
-  const unsigned G = grid_for(V, kTreeRows);
-  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
-  TreeArgs t;
-  uint32_t *flags, *state;
-  TRY(buf(DMAT, (size_t)ld * V * 4, (void **)&t.D));
-  TRY(buf(FLAGS, 64, (void **)&flags)); TRY(buf(ROWMIN, V * 8, (void **)&t.rowMin)); TRY(buf(STATE, V * 12 + 16, (void **)&state));
-  TRY(buf(PART, (size_t)G * 16, (void **)&t.part)); TRY(buf(OUT, M * 12, (void **)&t.children));
-  t.ld = ld; t.n = nG;
-  t.size = (int32_t *)state; t.id = (int32_t *)state + V; t.active = state + 2 * V; t.pick = (int32_t *)state + 3 * V;
-  t.arrived = flags + 1; t.height = (float *)(t.children + 2 * M);
-  // flags: [0] a bad id (1) or identity (2), [1] the arrival counter of k_tree_merge
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-  hipLaunchKernelGGL(k_tree_fill, dim3(nG), dim3(kTPB), 0, st, t.D, ld, nG, dMissing);
-  HIP_TRY(hipGetLastError());
-
-  if (n) {
-    // the pair values: keys and the stable sort as for the clustering, then one fold per pair into D
-    int b = 1;
-    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
-    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
-    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
-    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
-    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
-    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
-    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
-    size_t tb = 0;
-    int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
-    void *sortTmp = nullptr;
-    if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
-    if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
-    hipLaunchKernelGGL(k_tree_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                       (uint64_t)n, b, t.D, ld);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i : {ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, SORT}) B.b[i].release();
-  }
-
-  // row minima, the first pick, then one launch per merge (the last one picks nothing)
-  hipLaunchKernelGGL(k_tree_rowmin, dim3(nG), dim3(kTPB), 0, st, t);
-  hipLaunchKernelGGL(k_tree_first, dim3(1), dim3(kTPB), 0, st, t);
-  HIP_TRY(hipGetLastError());
-  for (int32_t s = 0; s + 1 < nG; s++) hipLaunchKernelGGL(k_tree_merge, dim3(G), dim3(kTPB), 0, st, t, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(children, t.children, M * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(height, t.height, M * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return ANI_OK;
-}
-
-// ---- neighbour-joining tree of the pair values (ani_tree_nj) ----
-// Device memory: 4 bytes per cell of the int32 matrix (n x ld, ld = n rounded up to 64) plus, beyond 64 genomes, the matrix the first
-// compaction writes (7/8 n on a side: 0.77 of the first); 40 bytes per genome; per row 20 + 2 x 12 + 12 bytes while the pairs are
-// folded, released before the joins.  The joins are a plain enqueue loop: per record one k_nj_scan, per join one k_nj_update, and
-// whenever an eighth of the matrix's positions is retired (the host knows when: one per join) a k_nj_map / k_nj_compact pair into
-// the other matrix.  Nothing is read back before the end.
-int tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *length)
-{
-  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, QMAT_A, QMAT_B, STATE_A, STATE_B, NEWPOS, PART, OUT, NBUF };
-  struct Bufs { DevBuf b[NBUF]; Bufs() = default; Bufs(const Bufs &) = delete; ~Bufs() { for (DevBuf &x : b) x.release(); } } B;
-  auto buf = [&](int i, size_t bytes, void **out) { const int rc = B.b[i].ensure(bytes); *out = B.b[i].p; return rc; };
-  auto round64 = [](uint64_t x) { return (x + 63) & ~63ull; };
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG, M = V - 1;
-  const uint64_t ld = round64(V);
-  const uint64_t second = nG > 64 ? V * 7 / 8 : 0;                // positions of the first compacted matrix
-  constexpr unsigned kMaxGrid = 2048;                              // workgroups of a scan: 8 per CU
-  const int32_t qMissing = (int32_t)rint((100.0 - (double)missingIdentity) * 16777216.0 / 100.0);
-  NjArgs t, u;                                                     // the matrix in use, the other one
-  uint32_t *flags, *newPos; char *state[2];
-  TRY(buf(QMAT_A, (size_t)ld * V * 4, (void **)&t.q));
-  u.q = nullptr;
-  if (second) TRY(buf(QMAT_B, (size_t)round64(second) * second * 4, (void **)&u.q));
-  TRY(buf(FLAGS, 64, (void **)&flags)); TRY(buf(NEWPOS, ld * 4, (void **)&newPos));
-  TRY(buf(STATE_A, ld * 16, (void **)&state[0])); TRY(buf(STATE_B, ld * 16, (void **)&state[1]));
-  TRY(buf(PART, (size_t)kMaxGrid * 12, (void **)&t.partQ)); TRY(buf(OUT, M * 16, (void **)&t.children));
-  t.ld = ld; t.n = nG; t.cur = nG;
-  t.partAB = (uint32_t *)(t.partQ + kMaxGrid); t.length = (float *)(t.children + 2 * M);
-  // flags: [0] a bad id (1) or identity (2), [1] the arrival counter of k_nj_scan, [4..6] the pick
-  t.arrived = flags + 1; t.pick = (int32_t *)flags + 4;
-  u = NjArgs{u.q, 0, nG, 0, nullptr, nullptr, nullptr, t.pick, t.partQ, t.partAB, t.arrived, t.children, t.length};
-  auto set_state = [&](NjArgs &x, int i) { x.R = (int64_t *)state[i]; x.id = (int32_t *)(state[i] + ld * 8); x.active = (uint32_t *)(state[i] + ld * 12); };
-  set_state(t, 0); set_state(u, 1);
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-  hipLaunchKernelGGL(k_nj_fill, dim3(nG), dim3(kTPB), 0, st, t.q, ld, nG, qMissing);
-  HIP_TRY(hipGetLastError());
-
-  if (n) {
-    // the pair values: keys and the stable sort as for the clustering, then one fold per pair into q
-    int b = 1;
-    while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++;          // bit width of the largest id
-    ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
-    TRY(buf(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(buf(KEYS_A, n * 8, (void **)&keysA)); TRY(buf(KEYS_B, n * 8, (void **)&keysB));
-    TRY(buf(VALS_A, n * 4, (void **)&valsA)); TRY(buf(VALS_B, n * 4, (void **)&valsB));
-    HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
-    hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
-    if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
-    size_t tb = 0;
-    int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
-    void *sortTmp = nullptr;
-    if (rc == 0) { TRY(buf(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
-    if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
-    hipLaunchKernelGGL(k_nj_fold, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                       (uint64_t)n, b, t.q, ld);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i : {ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, SORT}) B.b[i].release();
-  }
-
-  hipLaunchKernelGGL(k_nj_rowsum, dim3((unsigned)ld), dim3(kTPB), 0, st, t);
-  HIP_TRY(hipGetLastError());
-  for (int32_t s = 0; s + 1 < nG; s++) {
-    const uint32_t cur = (uint32_t)t.cur, rowsPerTile = cur <= 4096 ? 16 : 64;
-    const uint64_t tiles = (uint64_t)((cur + kNjCols - 1) / kNjCols) * ((cur + rowsPerTile - 1) / rowsPerTile);
-    hipLaunchKernelGGL(k_nj_scan, dim3((unsigned)std::min<uint64_t>(tiles, kMaxGrid)), dim3(kTPB), 0, st, t, s, rowsPerTile);
-    if (s + 2 == nG) break;                                        // the last record joins nothing
-    hipLaunchKernelGGL(k_nj_update, dim3(grid_for(cur, kTPB)), dim3(kTPB), 0, st, t);
-    const uint64_t m = (uint64_t)(nG - s - 1);                     // active positions now
-    if (cur > 64 && 8 * m <= 7 * (uint64_t)cur) {
-      u.cur = (int32_t)m; u.ld = round64(m);
-      hipLaunchKernelGGL(k_nj_map, dim3(1), dim3(kTPB), 0, st, t, u, newPos);
-      hipLaunchKernelGGL(k_nj_compact, dim3(cur), dim3(kTPB), 0, st, t, u, (const uint32_t *)newPos);
-      std::swap(t, u);
-    }
-    if ((s & 255) == 255) HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(children, t.children, M * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(length, t.length, M * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return ANI_OK;
-}
-
-// ---- single-linkage tree = minimum spanning forest of the pairs with rows (ani_tree_single) ----
-// Device memory per row: 20 (rows) + 2 x 12 (keys and positions) + 12 (the sort's ping-pong) = 56 bytes during the first sort, then
-// 20 + 12 + 4 (edge positions) per row and 20 per edge while the edges are compacted; per edge 44 during the second sort and 33 during the
-// rounds; per genome 12 (component, hook, best edge) and 13 per forest edge of the result.  Nothing is proportional to nGenomes^2.
-// One count is read back per round (the live edges), which also bounds the loop; every buffer is the pool's and goes back on return.
-// The pieces are shared with ani_tree_single_sketch (section 2.16), which folds further edges into the forest strip by strip.
-namespace {
-// edges on the device, every buffer the pool's: (lo, hi)-ordered with their sort input (dKey, idx), or ranked (lo, hi, d, src by rank)
-struct SingleEdges {
-  DevBuf lo, hi, dKey, idx, d, src; uint32_t n = 0;
-  SingleEdges() = default; SingleEdges(const SingleEdges &) = delete;
-  ~SingleEdges() { release(); }
-  void release() { for (DevBuf *x : {&lo, &hi, &dKey, &idx, &d, &src}) x->release(); n = 0; }
-  void swap(SingleEdges &o) { std::swap(lo, o.lo); std::swap(hi, o.hi); std::swap(dKey, o.dKey); std::swap(idx, o.idx); std::swap(d, o.d); std::swap(src, o.src); std::swap(n, o.n); }
-  ani::SingleList list() const { return ani::SingleList{lo.as<uint32_t>(), hi.as<uint32_t>(), d.as<uint32_t>(), src.as<uint8_t>(), n}; }
-};
-struct DevBufs {
-  std::vector<DevBuf> b;
-  explicit DevBufs(size_t n) : b(n) {}
-  DevBufs(const DevBufs &) = delete;
-  ~DevBufs() { for (DevBuf &x : b) x.release(); }
-  int get(int i, size_t bytes, void **out) { const int rc = b[(size_t)i].ensure(bytes ? bytes : 1); *out = b[(size_t)i].p; return rc; }
-};
-inline int id_bits(int32_t nG) { int b = 1; while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++; return b; }   // bit width of the largest id
-}  // namespace
-
-// The front half: the rows are uploaded and checked, the stable sort puts the rows of a pair next to each other in the order given, and
-// the pairs below d_missing come out as edges in (lo, hi) order with the input of the sort by distance.  pairKeys (may be null): the
-// sorted distinct keys lo << b | hi of every non-self pair with rows, whatever its distance.
-static int single_front(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, uint32_t dmBits, SingleEdges *edges, DevBuf *pairKeys, uint32_t *nKeys)
-{
-  enum { ROWS, KEYS_A, KEYS_B, VALS_A, VALS_B, FLAGS, SORT, FLAG, POS, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const int b = id_bits(nG);
-  edges->n = 0;
-  if (nKeys) *nKeys = 0;
-  if (!n) return ANI_OK;
-  // flags: [0] a bad id (1) or identity (2)
-  uint32_t *flags, *host = nullptr;
-  TRY(B.get(FLAGS, 64, (void **)&flags));
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-
-  // the pair values: keys and the stable sort as for the clustering
-  ani_cgi_t *dRows; uint64_t *keysA, *keysB; uint32_t *valsA, *valsB;
-  TRY(B.get(ROWS, n * sizeof(ani_cgi_t), (void **)&dRows)); TRY(B.get(KEYS_A, n * 8, (void **)&keysA)); TRY(B.get(KEYS_B, n * 8, (void **)&keysB));
-  TRY(B.get(VALS_A, n * 4, (void **)&valsA)); TRY(B.get(VALS_B, n * 4, (void **)&valsB));
-  HIP_TRY(hipMemcpyAsync(dRows, rows, n * sizeof(ani_cgi_t), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_tree_check, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, flags);
-  hipLaunchKernelGGL(k_cluster_keys, dim3(grid_for(n)), dim3(256), 0, st, (const ani_cgi_t *)dRows, (uint64_t)n, nG, b, keysA, valsA, flags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, flags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a row names a genome outside [0, %d)", nG);
-  if (host[0] & 2u) return fail(ANI_ERR_ARG, "a row has an identity outside (0, 100]");
-  if (dmBits == 0) return ANI_OK;                                  // (d_missing = 0: no pair lies below it, and nothing is left to mask)
-  size_t tb = 0;
-  int rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, nullptr, &tb, st);
-  void *sortTmp = nullptr;
-  if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(keysA, keysB, valsA, valsB, n, 2 * b, sortTmp, &tb, st); }
-  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair keys failed (%d)", rc);
-  for (int i : {SORT, KEYS_A, VALS_A}) B.b[(size_t)i].release();
-  int32_t *flag; uint32_t *pos;
-  TRY(B.get(FLAG, n * 4, (void **)&flag)); TRY(B.get(POS, n * 4, (void **)&pos));
-  if (pairKeys) {
-    hipLaunchKernelGGL(k_single_keyflag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (uint64_t)n, b, flag);
-    HIP_TRY(hipGetLastError());
-    uint64_t nK = 0;
-    TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nK));
-    TRY(pairKeys->ensure(nK ? (size_t)nK * 8 : 8));
-    hipLaunchKernelGGL(k_single_keys, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (uint64_t)n, (const int32_t *)flag, (const uint32_t *)pos,
-                       pairKeys->as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    *nKeys = (uint32_t)nK;
-  }
-  // the edges (pairs below d_missing), compacted in (lo, hi) order
-  hipLaunchKernelGGL(k_single_flag, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                     (uint64_t)n, b, dmBits, flag);
-  HIP_TRY(hipGetLastError());
-  uint64_t nE64 = 0;
-  TRY(device_scan(ctx, flag, pos, (uint32_t)n, &nE64));
-  B.b[FLAG].release();
-  const uint32_t nE = (uint32_t)nE64;
-  if (!nE) { HIP_TRY(hipStreamSynchronize(st)); return ANI_OK; }
-  TRY(edges->lo.ensure((size_t)nE * 4)); TRY(edges->hi.ensure((size_t)nE * 4)); TRY(edges->dKey.ensure((size_t)nE * 8)); TRY(edges->idx.ensure((size_t)nE * 4));
-  hipLaunchKernelGGL(k_single_pairs, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t *)keysB, (const uint32_t *)valsB, (const ani_cgi_t *)dRows,
-                     (uint64_t)n, b, dmBits, (const uint32_t *)pos, edges->lo.as<uint32_t>(), edges->hi.as<uint32_t>(), edges->dKey.as<uint64_t>(),
-                     edges->idx.as<uint32_t>());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  edges->n = nE;
-  return ANI_OK;
-}
-
-// Rule 3's order: a stable sort over the bits of d leaves equal distances in (lo, hi) order, so an edge's position is its rank.  Takes
-// edges in (lo, hi) order (lo, hi, dKey, idx) and leaves them ranked (lo, hi, d, src), every one with the source byte given.
-static int single_rank(ani_ctx *ctx, SingleEdges *e, uint8_t source)
-{
-  if (!e->n) return ANI_OK;
-  hipStream_t st = ctx->stream;
-  const size_t nE = e->n;
-  enum { DKEY_B, IDX_B, SORT, NBUF };
-  DevBufs B(NBUF);
-  uint64_t *dKeyB; uint32_t *idxB;
-  TRY(B.get(DKEY_B, nE * 8, (void **)&dKeyB)); TRY(B.get(IDX_B, nE * 4, (void **)&idxB));
-  size_t tb = 0;
-  int rc = ani_sort_pairs_u64_u32(e->dKey.as<uint64_t>(), dKeyB, e->idx.as<uint32_t>(), idxB, nE, 32, nullptr, &tb, st);
-  void *sortTmp = nullptr;
-  if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_pairs_u64_u32(e->dKey.as<uint64_t>(), dKeyB, e->idx.as<uint32_t>(), idxB, nE, 32, sortTmp, &tb, st); }
-  if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the pair distances failed (%d)", rc);
-  B.b[SORT].release(); e->dKey.release(); e->idx.release();
-  SingleEdges r;
-  TRY(r.lo.ensure(nE * 4)); TRY(r.hi.ensure(nE * 4)); TRY(r.d.ensure(nE * 4)); TRY(r.src.ensure(nE));
-  const ani::SingleList out = r.list();                            // (the launches take plain pointers, never the holder)
-  hipLaunchKernelGGL(k_single_rank, dim3(grid_for(nE)), dim3(256), 0, st, (uint32_t)nE, (const uint32_t *)idxB, (const uint32_t *)e->lo.as<uint32_t>(),
-                     (const uint32_t *)e->hi.as<uint32_t>(), (const uint64_t *)dKeyB, source, (uint32_t *)out.lo, (uint32_t *)out.hi, (uint32_t *)out.d,
-                     (uint8_t *)out.src);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  r.n = (uint32_t)nE;
-  e->swap(r);
-  return ANI_OK;
-}
-
-// Two ranked lists that share no edge -> one, in `x`; `y` is emptied.
-static int single_merge(ani_ctx *ctx, SingleEdges *x, SingleEdges *y)
-{
-  if (!y->n) return ANI_OK;
-  if (!x->n) { x->swap(*y); y->release(); return ANI_OK; }
-  const uint64_t nE = (uint64_t)x->n + y->n;
-  if (nE > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%llu edges in one fold: the forest stage takes fewer than 2^32 - 16", (unsigned long long)nE);
-  SingleEdges r;
-  TRY(r.lo.ensure((size_t)nE * 4)); TRY(r.hi.ensure((size_t)nE * 4)); TRY(r.d.ensure((size_t)nE * 4)); TRY(r.src.ensure((size_t)nE));
-  const ani::SingleList out = r.list();
-  hipLaunchKernelGGL(k_single_merge, dim3(grid_for((size_t)nE)), dim3(256), 0, ctx->stream, x->list(), y->list(), (uint32_t *)out.lo, (uint32_t *)out.hi,
-                     (uint32_t *)out.d, (uint8_t *)out.src);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  r.n = (uint32_t)nE;
-  x->swap(r);
-  y->release();
-  return ANI_OK;
-}
-
-// The forest stage: Boruvka rounds over a ranked edge list; the chosen edges stay, in rank order (a ranked list again).  A round in
-// which e edges join two components hooks every component that has one, so the components with edges at least halve: ceil(log2 V) rounds
-// with live edges, and one more that finds none.  The rounds are added to ctx->treeSingleRounds.
-static int single_forest(ani_ctx *ctx, int32_t nG, SingleEdges *e)
-{
-  if (!e->n) return ANI_OK;
-  enum { FLAGS, CHOSEN, LIVE_A, LIVE_B, COMP, PAR, BEST, POS, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG;
-  const uint32_t nE = e->n;
-  const int b = id_bits(nG);
-  // flags: [1] the live edges of a round, [2] a hook path that did not end
-  uint32_t *flags, *host = nullptr;
-  TRY(B.get(FLAGS, 64, (void **)&flags));
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(flags, 0, 64, st));
-  const uint32_t *uLo = e->lo.as<uint32_t>(), *uHi = e->hi.as<uint32_t>();
-  uint32_t *live[2], *comp, *par, *best; int32_t *chosen;
-  TRY(B.get(CHOSEN, (size_t)nE * 4, (void **)&chosen));
-  TRY(B.get(LIVE_A, (size_t)nE * 4, (void **)&live[0])); TRY(B.get(LIVE_B, (size_t)nE * 4, (void **)&live[1]));
-  TRY(B.get(COMP, V * 4, (void **)&comp)); TRY(B.get(PAR, V * 4, (void **)&par)); TRY(B.get(BEST, V * 4, (void **)&best));
-  HIP_TRY(hipMemsetAsync(chosen, 0, (size_t)nE * 4, st));
-  const unsigned gridV = grid_for(V);
-  hipLaunchKernelGGL(k_single_init, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, best);
-  HIP_TRY(hipGetLastError());
-  const int maxRounds = b + 3;
-  const uint32_t *liveIn = nullptr; uint32_t nLive = nE;
-  for (int round = 0; nLive; round++) {
-    if (round >= maxRounds) return fail(ANI_ERR_INTERNAL, "the spanning forest did not converge after %d rounds", round);
-    uint32_t *liveOut = live[round & 1];
-    HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
-    hipLaunchKernelGGL(k_single_best, dim3(grid_for(nLive)), dim3(256), 0, st, liveIn, nLive, uLo, uHi, (const uint32_t *)comp, best, liveOut, flags + 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, flags + 1, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (host[1]) return fail(ANI_ERR_INTERNAL, "the hooks of round %d hold a cycle", round - 1);
-    if (host[0] > nLive) return fail(ANI_ERR_INTERNAL, "the live edges grew from %u to %u", nLive, host[0]);
-    ctx->treeSingleRounds++;
-    liveIn = liveOut; nLive = host[0];
-    if (!nLive) break;
-    hipLaunchKernelGGL(k_single_hook, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, (const uint32_t *)best, uLo, uHi, par, chosen);
-    hipLaunchKernelGGL(k_single_jump, dim3(gridV), dim3(256), 0, st, (uint32_t)V, (const uint32_t *)comp, par, flags + 2);
-    hipLaunchKernelGGL(k_single_label, dim3(gridV), dim3(256), 0, st, (uint32_t)V, comp, (const uint32_t *)par, best);
-    HIP_TRY(hipGetLastError());
-  }
-  for (int i : {LIVE_A, LIVE_B, COMP, PAR, BEST}) B.b[(size_t)i].release();
-
-  // the chosen edges, compacted in rank order
-  uint32_t *cpos;
-  TRY(B.get(POS, (size_t)nE * 4, (void **)&cpos));
-  uint64_t nRec = 0;
-  TRY(device_scan(ctx, chosen, cpos, nE, &nRec));
-  if (nRec > V - 1) return fail(ANI_ERR_INTERNAL, "%llu forest edges over %d genomes", (unsigned long long)nRec, nG);
-  SingleEdges f;
-  if (nRec) {
-    TRY(f.lo.ensure((size_t)nRec * 4)); TRY(f.hi.ensure((size_t)nRec * 4)); TRY(f.d.ensure((size_t)nRec * 4)); TRY(f.src.ensure((size_t)nRec));
-    const ani::SingleList out = f.list();
-    hipLaunchKernelGGL(k_single_records, dim3(grid_for(nE)), dim3(256), 0, st, nE, (const int32_t *)chosen, (const uint32_t *)cpos, uLo, uHi,
-                       (const uint32_t *)e->d.as<uint32_t>(), (const uint8_t *)e->src.as<uint8_t>(), (uint32_t *)out.lo, (uint32_t *)out.hi, (uint32_t *)out.d,
-                       (uint8_t *)out.src);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    f.n = (uint32_t)nRec;
-  }
-  e->swap(f);
-  return ANI_OK;
-}
-
-// The linkage: the forest edges (brought back from the device) in rank order through a union-find, then rule 5's joins to leaf 0 (a
-// cluster not yet joined when its smallest leaf k comes up: every smaller leaf is with leaf 0 by then).  source (may be null): per merge
-// the forest edge's source byte, 2 for a join to leaf 0.
-static int single_finish(ani_ctx *ctx, const SingleEdges &forest, int32_t nG, float dMissing, int32_t *children, float *height, int32_t *edges, uint8_t *source)
-{
-  const size_t V = (size_t)nG, M = V - 1, nF = forest.n;
-  std::vector<uint32_t> lo(nF), hi(nF), dist(nF); std::vector<uint8_t> src(nF);
-  if (nF) {
-    hipStream_t st = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(lo.data(), forest.lo.p, nF * 4, hipMemcpyDeviceToHost, st)); HIP_TRY(hipMemcpyAsync(hi.data(), forest.hi.p, nF * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dist.data(), forest.d.p, nF * 4, hipMemcpyDeviceToHost, st)); HIP_TRY(hipMemcpyAsync(src.data(), forest.src.p, nF, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  std::vector<int32_t> up(V), id(V);
-  for (size_t i = 0; i < V; i++) { up[i] = (int32_t)i; id[i] = (int32_t)i; }
-  auto find = [&](int32_t x) { while (up[(size_t)x] != x) { up[(size_t)x] = up[(size_t)up[(size_t)x]]; x = up[(size_t)x]; } return x; };
-  size_t s = 0;
-  auto merge = [&](int32_t a, int32_t c, float d, uint8_t from) {
-    const int32_t ra = find(a), rb = find(c);
-    if (ra == rb) return false;
-    const int32_t ia = id[(size_t)ra], ib = id[(size_t)rb];
-    children[2 * s] = ia < ib ? ia : ib; children[2 * s + 1] = ia < ib ? ib : ia;
-    height[s] = d;
-    if (edges) { edges[2 * s] = a; edges[2 * s + 1] = c; }
-    if (source) source[s] = from;
-    up[(size_t)rb] = ra; id[(size_t)ra] = (int32_t)(V + s);
-    s++;
-    return true;
-  };
-  for (size_t r = 0; r < nF; r++) {
-    float d; memcpy(&d, &dist[r], 4);
-    if (lo[r] >= V || hi[r] >= V || !merge((int32_t)lo[r], (int32_t)hi[r], d, src[r])) return fail(ANI_ERR_INTERNAL, "the forest edges hold a cycle");
-  }
-  for (size_t k = 1; k < V; k++) (void)merge(0, (int32_t)k, dMissing, 2);
-  if (s != M) return fail(ANI_ERR_INTERNAL, "%zu merges over %d genomes", s, nG);
-  return ANI_OK;
-}
-
-int tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, int32_t *children, float *height, int32_t *edges)
-{
-  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
-  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
-  ctx->treeSingleRounds = 0;
-  SingleEdges e;
-  TRY(single_front(ctx, rows, n, nG, dmBits, &e, nullptr, nullptr));
-  TRY(single_rank(ctx, &e, 0));
-  TRY(single_forest(ctx, nG, &e));
-  return single_finish(ctx, e, nG, dMissing, children, height, edges, nullptr);
-}
-
-// ---- whole-genome sketch ANI (ani_sketch_signatures, ani_signature_pairs) ----
-// Per index chunk, from whichever form of its records is at hand (the index arrays of a resident chunk, else the 12-byte records a
-// streamed set keeps: nothing is rebuilt).  Round 1 keeps the records at or below a per-genome hash threshold that lets about
-// 2 size + 64 k-mers of the genome through (a k-mer that small is a window minimizer almost surely), sorts those few keys and numbers
-// the distinct ones; a genome that yields fewer than `size` that way (repeats, a short genome) goes through round 2 with every record.
-// Device memory: 8 bytes per genome, 4 + 4 per block of 2048 records, 2 x 8 bytes per kept record plus the sort's workspace,
-// 4 (size + 1) per genome for the result.
-int sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
-{
-  enum { THR, CNT, OFF, KEYS_A, KEYS_B, SORT, SIG, LEN, NBUF };
-  DevBufs B(NBUF);
-  ani_ctx *ctx = sk->ctx;
-  hipStream_t st = ctx->stream;
-  const int64_t kAll = 0xffffffffll;
-  for (const IndexChunk *ch : sk->chunks) {
-    const int32_t nG = ch->nGenomes;
-    if (nG <= 0) continue;
-    std::vector<SigSource> src;
-    if (ch->n) {
-      if (ch->resident) src.push_back(SigSource{ch->mHash, ch->mSeq, 1u, 0, (uint64_t)ch->n});
-      else for (const RecordPiece &pc : ch->pieces) if (pc.n) src.push_back(SigSource{pc.rec, (const int32_t *)pc.rec + 1, 3u, ch->c0, (uint64_t)pc.n});
-      if (src.empty()) return fail(ANI_ERR_INTERNAL, "index chunk of genomes [%d, %d) holds neither index arrays nor records", ch->g0, ch->g0 + nG);
-    }
-    uint64_t nBlocks = 0;
-    for (const SigSource &s : src) nBlocks += (s.n + kSigBlock - 1) / kSigBlock;
-    std::vector<int64_t> thr((size_t)nG);
-    const uint64_t want = 2 * (uint64_t)size + 64;
-    for (int32_t g = 0; g < nG; g++) {
-      uint64_t bases = 0;
-      for (int32_t c = sk->genomeContigStart[(size_t)(ch->g0 + g)]; c < sk->genomeContigStart[(size_t)(ch->g0 + g) + 1]; c++) bases += (uint64_t)sk->contigLen[(size_t)c];
-      const uint64_t recs = sk->genomeRecStart[(size_t)(ch->g0 + g) + 1] - sk->genomeRecStart[(size_t)(ch->g0 + g)];
-      thr[(size_t)g] = (bases <= want || recs <= want) ? kAll : (int64_t)std::min<uint64_t>((uint64_t)kAll, (want << 32) / bases);
-    }
-    int64_t *dThr; int32_t *dCnt, *dLen; uint32_t *dOff, *dSig;
-    TRY(B.get(THR, (size_t)nG * 8, (void **)&dThr)); TRY(B.get(CNT, nBlocks * 4, (void **)&dCnt)); TRY(B.get(OFF, nBlocks * 4, (void **)&dOff));
-    TRY(B.get(SIG, (size_t)nG * (size_t)size * 4, (void **)&dSig)); TRY(B.get(LEN, (size_t)nG * 4, (void **)&dLen));
-    std::vector<int32_t> hostLen((size_t)nG);
-    int bits = 1;
-    while (bits < 31 && ((uint32_t)(nG - 1) >> bits) != 0) bits++;
-    for (int round = 0; round < 2; round++) {
-      HIP_TRY(hipMemcpyAsync(dThr, thr.data(), (size_t)nG * 8, hipMemcpyHostToDevice, st));
-      uint64_t total = 0, at = 0;
-      for (const SigSource &s : src) {
-        const uint64_t nb = (s.n + kSigBlock - 1) / kSigBlock;
-        hipLaunchKernelGGL(k_sig_count, dim3((unsigned)nb), dim3(kTPB), 0, st, s, (const int32_t *)ch->contigGenome, (const int64_t *)dThr, dCnt + at);
-        at += nb;
-      }
-      HIP_TRY(hipGetLastError());
-      if (nBlocks) TRY(device_scan(ctx, dCnt, dOff, (uint32_t)nBlocks, &total));
-      uint64_t *keysA, *keysB;
-      TRY(B.get(KEYS_A, (size_t)total * 8, (void **)&keysA)); TRY(B.get(KEYS_B, (size_t)total * 8, (void **)&keysB));
-      if (total) {
-        at = 0;
-        for (const SigSource &s : src) {
-          const uint64_t nb = (s.n + kSigBlock - 1) / kSigBlock;
-          hipLaunchKernelGGL(k_sig_keys, dim3((unsigned)nb), dim3(kTPB), 0, st, s, (const int32_t *)ch->contigGenome, (const int64_t *)dThr,
-                             (const uint32_t *)dOff + at, keysA);
-          at += nb;
-        }
-        HIP_TRY(hipGetLastError());
-        size_t tb = 0;
-        int rc = ani_sort_keys_u64_bits(keysA, keysB, (size_t)total, 32 + bits, nullptr, &tb, st);
-        void *sortTmp = nullptr;
-        if (rc == 0) { TRY(B.get(SORT, tb + 256, &sortTmp)); rc = ani_sort_keys_u64_bits(keysA, keysB, (size_t)total, 32 + bits, sortTmp, &tb, st); }
-        if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of the signature keys failed (%d)", rc);
-      }
-      hipLaunchKernelGGL(k_sig_emit, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint64_t *)keysB, (uint32_t)total, (const int64_t *)dThr, size, dSig, dLen);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(hostLen.data(), dLen, (size_t)nG * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      bool again = false;
-      for (int32_t g = 0; g < nG && round == 0; g++) {
-        const bool more = hostLen[(size_t)g] < size && thr[(size_t)g] >= 0 && thr[(size_t)g] != kAll;
-        thr[(size_t)g] = more ? kAll : -1;
-        again = again || more;
-      }
-      if (!again) break;
-    }
-    HIP_TRY(hipMemcpyAsync(sig + (size_t)ch->g0 * (size_t)size, dSig, (size_t)nG * (size_t)size * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(len + ch->g0, hostLen.data(), (size_t)nG * 4);
-  }
-  return ANI_OK;
-}
-
-// identity of a pair from its exact integers (ani_abi.h): one double expression, rounded once
-static inline float sig_identity(int32_t shared, int32_t size, int32_t kmerSize)
-{
-  if (shared == 0) return 0.0f;
-  double id = 100.0 * (1.0 + log(2.0 * (double)shared / (double)(size + shared)) / (double)kmerSize);
-  if (id < 0.0) id = 0.0;
-  if (id > 100.0) id = 100.0;
-  return (float)id;
-}
-
-// the merge tiles by row pitch: T x T pairs per workgroup, 2 T rows of `pitch` words in LDS
-static void sigpair_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, int32_t n, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld)
-{
-  auto tiles = [&](int t) { return dim3((unsigned)((n + t - 1) / t), (unsigned)((n + t - 1) / t)); };
-  if (pitch <= 256) hipLaunchKernelGGL((k_sigpair_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, pitch, size, mat, ld);
-  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigpair_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, pitch, size, mat, ld);
-  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigpair_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, pitch, size, mat, ld);
-  else hipLaunchKernelGGL((k_sigpair_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, pitch, size, mat, ld);
-}
-
-// The rows are staged and validated first, then the matrix is taken.  Device memory: the rows twice (as given and at a pitch of whole quads), 4 bytes per cell of the n x n result matrix (its upper
-// triangle is used), 8 bytes per genome, 16 bytes per row returned.  Everything goes back to the pool on return.
-int signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared,
-                    ani_sigpair_t **rows, size_t *n)
-{
-  enum { RAW, LEN, SIG, FLAGS, MAT, CNT, OFF, OUT, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG;
-  const int32_t pitch = (size + 3) & ~3;
-  const uint64_t ld = (V + 3) & ~(uint64_t)3;
-  uint32_t *dRaw, *dSig, *dFlags, *dMat, *dOff; int32_t *dLen, *dCnt;
-  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
-  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  TRY(B.get(CNT, V * 4, (void **)&dCnt)); TRY(B.get(OFF, V * 4, (void **)&dOff));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  B.b[RAW].release();
-  TRY(B.get(MAT, (size_t)ld * V * 4, (void **)&dMat));                 // (after the rows are known to be good: a bad row is ANI_ERR_ARG whatever the size)
-  sigpair_launch(st, dSig, dLen, nG, pitch, size, dMat, ld);
-  hipLaunchKernelGGL(k_sigpair_count, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, nG, minShared, dCnt);
-  HIP_TRY(hipGetLastError());
-  uint64_t total = 0;
-  TRY(device_scan(ctx, dCnt, dOff, (uint32_t)nG, &total));
-  ani_sigpair_t *out = (ani_sigpair_t *)malloc((total ? total : 1) * sizeof(ani_sigpair_t));
-  if (!out) return fail(ANI_ERR_NOMEM, "host allocation of %llu pair rows failed", (unsigned long long)total);
-  struct Guard { ani_sigpair_t *p; ~Guard() { free(p); } } guard{out};
-  if (total) {
-    uint4 *dOut;
-    TRY(B.get(OUT, (size_t)total * 16, (void **)&dOut));
-    hipLaunchKernelGGL(k_sigpair_write, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, nG, minShared, (const uint32_t *)dOff, dOut);
-    HIP_TRY(hipGetLastError());
-    // back through page-locked staging in pieces; the identities are host arithmetic (ani_abi.h)
-    const size_t piece = (size_t)1 << 21;
-    int32_t *stage = nullptr;
-    TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)total) * 16, (void **)&stage));
-    for (size_t r0 = 0; r0 < (size_t)total; r0 += piece) {
-      const size_t m = std::min<size_t>(piece, (size_t)total - r0);
-      HIP_TRY(hipMemcpyAsync(stage, dOut + r0, m * 16, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      const size_t step = 8192;
-      parallel_for((m + step - 1) / step, (uint64_t)m * 64, [&](size_t blk) {
-        for (size_t i = blk * step; i < std::min(m, (blk + 1) * step); i++) {
-          const int32_t *q = stage + 4 * i;
-          out[r0 + i] = ani_sigpair_t{q[0], q[1], q[2], q[3], sig_identity(q[2], q[3], kmerSize)};
-        }
-      });
-    }
-  }
-  guard.p = nullptr;
-  *rows = out; *n = (size_t)total;
-  return ANI_OK;
-}
-
-// the strip tiles by row pitch, as sigpair_launch: rows [r0, r1), columns from r0 on
-static void sigstrip_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
-                            uint64_t ld)
-{
-  auto tiles = [&](uint32_t t) { return dim3((n - r0 + t - 1) / t, (r1 - r0 + t - 1) / t); };
-  if (pitch <= 256) hipLaunchKernelGGL((k_sigstrip_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigstrip_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigstrip_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else hipLaunchKernelGGL((k_sigstrip_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-}
-
-// ---- single-linkage tree of the rows plus the sketch estimates of the pairs without rows (ani_tree_single_sketch) ----
-// Forest 0 is ani_tree_single's forest of the pairs with rows.  The sketch pairs then come a strip of rows at a time: the strip's cells,
-// the cells that are edges (kSigStripShare of the free device memory bounds a strip: 4 bytes per cell, and 44 per edge while a strip's
-// edges are sorted, as if every cell were one), the edges ranked, merged with the forest so far, and the forest stage over the two.
-// Device memory: ani_tree_single's for the rows, the signatures twice while they are staged and once after, 4 s (s + 1) / 2 bytes of
-// distances, 8 bytes per pair with rows, and one strip.  Nothing follows nGenomes^2.
-constexpr double kSigStripShare = 0.5;
-
-int tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, float missingIdentity, const uint32_t *sig, const int32_t *len, int32_t size,
-                       int32_t kmerSize, int32_t minShared, int32_t *children, float *height, int32_t *edges, uint8_t *source)
-{
-  const float dMissing = (float)(1.0 - (double)missingIdentity / 100.0);
-  uint32_t dmBits; memcpy(&dmBits, &dMissing, 4);
-  ctx->treeSingleRounds = 0; ctx->sigStripEdges.clear();
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG;
-  const int b = id_bits(nG);
-  SingleEdges forest;
-  DevBuf pairKeys; uint32_t nKeys = 0;
-  struct KeyGuard { DevBuf *k; ~KeyGuard() { k->release(); } } keyGuard{&pairKeys};
-  TRY(single_front(ctx, rows, n, nG, dmBits, &forest, &pairKeys, &nKeys));
-  TRY(single_rank(ctx, &forest, 0));
-  TRY(single_forest(ctx, nG, &forest));
-
-  // the signatures, staged and validated as for ani_signature_pairs
-  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, CNT, OFF, NBUF };
-  DevBufs B(NBUF);
-  const int32_t pitch = (size + 3) & ~3;
-  const uint64_t ld = (V + 3) & ~(uint64_t)3;
-  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat, *dOff; int32_t *dLen, *dCnt;
-  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
-  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  B.b[RAW].release();
-
-  if (dmBits != 0) {                                                 // (d_missing = 0: no pair lies below it)
-    // bits(d) of every (shared, size'): rule 3's identity in double on the host, then ani_tree_single's rule 2
-    const size_t S = (size_t)size;
-    std::vector<uint32_t> table(S * (S + 1) / 2);
-    parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
-      const int32_t sz = (int32_t)i + 1;
-      for (int32_t sh = 1; sh <= sz; sh++) {
-        const float w = sig_identity(sh, sz, kmerSize);
-        float d = (float)(1.0 - (double)w / 100.0);
-        if (!(d < dMissing)) d = dMissing;
-        memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &d, 4);
-      }
-    });
-    TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
-    HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-
-    // strip height: a cell and, as if every cell were an edge, the 44 bytes of an edge in its sort, inside a share of what is free now
-    size_t freeB = 0, totalB = 0;
-    TRY(ani_device_memory(ctx, &freeB, &totalB));
-    uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (48.0 * (double)ld));
-    h = std::min<uint64_t>(h, 0xfffffff0ull / ld);                   // (the edges of a strip are numbered in 32 bits)
-    if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
-    h = std::max<uint64_t>(1, std::min<uint64_t>(h, V - 1));
-    TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat)); TRY(B.get(CNT, (size_t)h * 4, (void **)&dCnt)); TRY(B.get(OFF, (size_t)h * 4, (void **)&dOff));
-    const uint64_t *realKeys = pairKeys.as<uint64_t>();
-    for (uint64_t r0 = 0; r0 + 1 < V; r0 += h) {                     // (the last genome has no pair b > a)
-      const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V - 1), rows1 = r1 - (uint32_t)r0;
-      sigstrip_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
-      hipLaunchKernelGGL(k_sigstrip_count, dim3(rows1), dim3(kTPB), 0, st, dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared, (const uint32_t *)dTable, dmBits,
-                         realKeys, nKeys, b, dCnt);
-      HIP_TRY(hipGetLastError());
-      uint64_t nE = 0;
-      TRY(device_scan(ctx, dCnt, dOff, rows1, &nE));
-      ctx->sigStripEdges.push_back(nE);
-      if (!nE) continue;
-      SingleEdges e;
-      TRY(e.lo.ensure((size_t)nE * 4)); TRY(e.hi.ensure((size_t)nE * 4)); TRY(e.dKey.ensure((size_t)nE * 8)); TRY(e.idx.ensure((size_t)nE * 4));
-      uint32_t *eLo = e.lo.as<uint32_t>(), *eHi = e.hi.as<uint32_t>(), *idx = e.idx.as<uint32_t>(); uint64_t *dKey = e.dKey.as<uint64_t>();
-      hipLaunchKernelGGL(k_sigstrip_write, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, (const uint32_t *)dOff,
-                         eLo, eHi, dKey, idx);
-      HIP_TRY(hipGetLastError());
-      e.n = (uint32_t)nE;
-      TRY(single_rank(ctx, &e, 1));
-      TRY(single_merge(ctx, &forest, &e));
-      TRY(single_forest(ctx, nG, &forest));
-    }
-  }
-  return single_finish(ctx, forest, nG, dMissing, children, height, edges, source);
-}
-
-// ---- nearest neighbours under the sketch estimate (ani_signature_neighbors) ----
-// bits(identity) of every (shared, size') with 1 <= shared <= size' <= size: rule 3 in double on the host
-static std::vector<uint32_t> sig_identity_table(int32_t size, int32_t kmerSize)
-{
-  const size_t S = (size_t)size;
-  std::vector<uint32_t> table(S * (S + 1) / 2);
-  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
-    const int32_t sz = (int32_t)i + 1;
-    for (int32_t sh = 1; sh <= sz; sh++) {
-      const float w = sig_identity(sh, sz, kmerSize);
-      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)sz)], &w, 4);
-    }
-  });
-  return table;
-}
-
-// identity of a pair under the containment estimate from its exact integers (ani_signature_screen_contain, rule 5): one double
-// expression, rounded once
-static inline float sig_contain_identity(int32_t shared, int32_t d, int32_t kmerSize)
-{
-  if (shared == 0) return 0.0f;
-  double id = 100.0 * pow((double)shared / (double)d, 1.0 / (double)kmerSize);
-  if (id < 0.0) id = 0.0;
-  if (id > 100.0) id = 100.0;
-  return (float)id;
-}
-
-// bits(identity) of every (shared, d) with 1 <= shared <= d <= size under the containment estimate, in the same triangular layout
-static std::vector<uint32_t> sig_contain_table(int32_t size, int32_t kmerSize)
-{
-  const size_t S = (size_t)size;
-  std::vector<uint32_t> table(S * (S + 1) / 2);
-  parallel_for(S, (uint64_t)table.size() * 64, [&](size_t i) {
-    const int32_t d = (int32_t)i + 1;
-    for (int32_t sh = 1; sh <= d; sh++) {
-      const float w = sig_contain_identity(sh, d, kmerSize);
-      memcpy(&table[ani::sigstrip_entry((uint32_t)sh, (uint32_t)d)], &w, 4);
-    }
-  });
-  return table;
-}
-
-// the rectangular tiles by row pitch, as sigpair_launch: rows [r0, r1), all columns
-static void signeigh_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t n, uint32_t r0, uint32_t r1, int32_t pitch, int32_t size, uint32_t *mat,
-                            uint64_t ld)
-{
-  auto tiles = [&](uint32_t t) { return dim3((n + t - 1) / t, (r1 - r0 + t - 1) / t); };
-  if (pitch <= 256) hipLaunchKernelGGL((k_signeigh_merge<16, 8192>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else if (pitch <= 1024) hipLaunchKernelGGL((k_signeigh_merge<16, kSigTileWords>), tiles(16), dim3(256), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else if (pitch <= 2048) hipLaunchKernelGGL((k_signeigh_merge<8, kSigTileWords>), tiles(8), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-  else hipLaunchKernelGGL((k_signeigh_merge<4, kSigTileWords>), tiles(4), dim3(64), 0, st, sig, len, n, r0, r1, pitch, size, mat, ld);
-}
-
-// The signatures are staged and validated as for ani_signature_pairs, the identity bits of every (shared, size') come from the host, and
-// the rows of the range go through the device a strip at a time: the strip's cells against every genome, then the k nearest of each row,
-// written into the row's place of the range's output and copied back through page-locked staging.  Every pair is merged once from
-// each of its ends.  Device memory: the signatures twice while they are staged and once after, 2 s (s + 1) bytes of identities,
-// 16 k + 4 bytes per row of the range, and one strip (kSigStripShare of what is free then, 4 bytes per cell).  Nothing follows nGenomes^2.
-int signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
-                        int32_t k, int32_t rowBegin, int32_t rowEnd, ani_signeighbor_t *out, int32_t *count)
-{
-  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, OUT, CNT, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG, R = (size_t)(rowEnd - rowBegin);
-  const int32_t pitch = (size + 3) & ~3;
-  const uint64_t ld = (V + 3) & ~(uint64_t)3;
-  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat; int32_t *dLen, *dCnt; uint4 *dOut;
-  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
-  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  B.b[RAW].release();
-
-  const std::vector<uint32_t> table = sig_identity_table(size, kmerSize);
-  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
-  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
-  uint32_t minBits; memcpy(&minBits, &lowest, 4);
-
-  TRY(B.get(OUT, R * (size_t)k * 16, (void **)&dOut)); TRY(B.get(CNT, R * 4, (void **)&dCnt));
-  // strip height: 4 bytes per cell inside a share of what is free now; the grid of the 4 x 4 tiles bounds it too
-  size_t freeB = 0, totalB = 0;
-  TRY(ani_device_memory(ctx, &freeB, &totalB));
-  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)ld));
-  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
-  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, R), 4 * 65535));
-  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat));
-  const size_t piece = std::max<size_t>(1, ((size_t)1 << 21) / (size_t)k);      // rows per copy: 32 MiB of staging at the most
-  ani_signeighbor_t *stage = nullptr; int32_t *stageCnt = nullptr;
-  TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)h) * (size_t)k * 16, (void **)&stage));
-  TRY(pinned_buffer(ctx, 1, (size_t)h * 4, (void **)&stageCnt));
-  for (uint64_t r0 = (uint64_t)rowBegin; r0 < (uint64_t)rowEnd; r0 += h) {
-    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, (uint64_t)rowEnd), rows1 = r1 - (uint32_t)r0;
-    const size_t at = (size_t)(r0 - (uint64_t)rowBegin);
-    signeigh_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
-    hipLaunchKernelGGL(k_signeigh_select, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)rowBegin, (uint32_t)nG, minShared,
-                       (const uint32_t *)dTable, minBits, k, dOut, dCnt);
-    HIP_TRY(hipGetLastError());
-    ctx->sigNeighStrips++;
-    HIP_TRY(hipMemcpyAsync(stageCnt, dCnt + at, (size_t)rows1 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(count + at, stageCnt, (size_t)rows1 * 4);
-    for (size_t p0 = 0; p0 < rows1; p0 += piece) {
-      const size_t m = std::min<size_t>(piece, rows1 - p0) * (size_t)k;
-      HIP_TRY(hipMemcpyAsync(stage, dOut + (at + p0) * (size_t)k, m * 16, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      memcpy(out + (at + p0) * (size_t)k, stage, m * 16);
-    }
-  }
-  return ANI_OK;
-}
-
-// ---- the nearest references of every query under the sketch estimate (ani_signature_screen) ----
-// The tile by strip height and row pitch.  A strip of at least T queries, T the edge of the pair tiles at this pitch, takes the square
-// tile; a lower one the thin tile of one query and 64 references, whose LDS is the query row alone.  ANI_TEST_SIG_SCREEN_SHAPE = square or
-// thin (tests, tools/sketch_probe.py) forces a shape.  shape[0 .. 2) = TQ, TR of the tile taken.  mode < 0: the Mash merge of
-// k_sigscreen_merge; otherwise the containment walk of k_sigcontain_merge in that mode, in the same shapes, the
-// square tiles with kSigContainPad more words of LDS for their row pitch there.
-static void sigscreen_launch(hipStream_t st, const uint32_t *refSig, const int32_t *refLen, uint32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, uint32_t q0,
-                             uint32_t q1, int32_t pitch, int32_t size, int32_t mode, uint32_t *mat, uint64_t ld, int32_t *shape)
-{
-  const uint32_t T = pitch <= 1024 ? 16u : pitch <= 2048 ? 8u : 4u;
-  bool thin = q1 - q0 < T;
-  if (const char *ev = getenv("ANI_TEST_SIG_SCREEN_SHAPE")) { if (!strcmp(ev, "square")) thin = false; else if (!strcmp(ev, "thin")) thin = true; }
-  auto tiles = [&](uint32_t tq, uint32_t tr) { return dim3((nRef + tr - 1) / tr, (q1 - q0 + tq - 1) / tq); };
-#define ANI_SCREEN(TQ, TR, WORDS, LANES) do { \
-    if (mode < 0) hipLaunchKernelGGL((k_sigscreen_merge<TQ, TR, WORDS>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, qryLen, q0, q1, pitch, size, \
-                                     mat, ld); \
-    else hipLaunchKernelGGL((k_sigcontain_merge<TQ, TR, (TQ > 1 ? WORDS + kSigContainPad : WORDS)>), tiles(TQ, TR), dim3(LANES), 0, st, refSig, refLen, nRef, qrySig, \
-                            qryLen, q0, q1, pitch, size, mode, mat, ld); } while (0)
-  if (thin) {
-    if (pitch <= 1024) ANI_SCREEN(1, kSigScreenThinRefs, 1024, 64);
-    else ANI_SCREEN(1, kSigScreenThinRefs, kSigMaxSize, 64);
-  }
-  else if (pitch <= 256) ANI_SCREEN(16, 16, 8192, 256);
-  else if (pitch <= 1024) ANI_SCREEN(16, 16, kSigTileWords, 256);
-  else if (pitch <= 2048) ANI_SCREEN(8, 8, kSigTileWords, 64);
-  else ANI_SCREEN(4, 4, kSigTileWords, 64);
-#undef ANI_SCREEN
-  shape[0] = thin ? 1 : (int32_t)T; shape[1] = thin ? kSigScreenThinRefs : (int32_t)T;
-}
-
-// one set of signatures to the device: as given, then at a pitch of whole quads by k_sigpair_stage, which flags a row that does not ascend
-static int sigscreen_stage(ani_ctx *ctx, DevBuf &raw, DevBuf &staged, DevBuf &lens, const uint32_t *sig, const int32_t *len, size_t n, int32_t size, int32_t pitch,
-                           uint32_t *dFlags)
-{
-  hipStream_t st = ctx->stream;
-  TRY(raw.ensure(n * (size_t)size * 4)); TRY(staged.ensure(n * (size_t)pitch * 4)); TRY(lens.ensure(n * 4));
-  HIP_TRY(hipMemcpyAsync(raw.p, sig, n * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(lens.p, len, n * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)n), dim3(kTPB), 0, st, (const uint32_t *)raw.p, (const int32_t *)lens.p, size, pitch, staged.as<uint32_t>(), dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));                                   // (sig and len are the caller's pageable memory)
-  raw.release();
-  return ANI_OK;
-}
-
-// Both sets are staged and validated as for ani_signature_pairs, the references once; the identity bits of every (shared, size') come
-// from the host; the queries go through the device a strip at a time: the strip's cells against every reference, then the k nearest of
-// each query, written into the query's place of the output and copied back through page-locked staging.  Device memory: either set
-// twice while it is staged and once after, 2 s (s + 1) bytes of identities, 16 k + 4 bytes per query, and one strip (kSigStripShare of
-// what is free then, 4 bytes per cell).  Nothing follows nRef * nQry.
-// Shared by the two estimates: mode < 0 is ani_signature_screen (the Mash merge, sig_identity_table), mode 0 .. 2 is
-// ani_signature_screen_contain (the containment walk in that mode, sig_contain_table); everything else is the same code.
-static int screen_run(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                      int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out, int32_t *count)
-{
-  enum { RRAW, RLEN, RSIG, QRAW, QLEN, QSIG, FLAGS, TABLE, MAT, OUT, CNT, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t R = (size_t)nRef, Q = (size_t)nQry;
-  const int32_t pitch = (size + 3) & ~3;
-  const uint64_t ld = (R + 3) & ~(uint64_t)3;
-  uint32_t *dFlags, *dTable, *dMat; int32_t *dCnt; uint4 *dOut;
-  TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  if (R) { TRY(sigscreen_stage(ctx, B.b[RRAW], B.b[RSIG], B.b[RLEN], refSig, refLen, R, size, pitch, dFlags)); }
-  TRY(sigscreen_stage(ctx, B.b[QRAW], B.b[QSIG], B.b[QLEN], qrySig, qryLen, Q, size, pitch, dFlags));
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  if (!R) {                                                            // no references: every list is empty
-    for (size_t i = 0; i < Q * (size_t)k; i++) out[i] = ani_signeighbor_t{-1, 0, 0, 0.0f};
-    std::fill(count, count + Q, 0);
-    return ANI_OK;
-  }
-  const uint32_t *dRefSig = B.b[RSIG].as<uint32_t>(), *dQrySig = B.b[QSIG].as<uint32_t>();
-  const int32_t *dRefLen = B.b[RLEN].as<int32_t>(), *dQryLen = B.b[QLEN].as<int32_t>();
-
-  const std::vector<uint32_t> table = mode < 0 ? sig_identity_table(size, kmerSize) : sig_contain_table(size, kmerSize);
-  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
-  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
-  uint32_t minBits; memcpy(&minBits, &lowest, 4);
-
-  TRY(B.get(OUT, Q * (size_t)k * 16, (void **)&dOut)); TRY(B.get(CNT, Q * 4, (void **)&dCnt));
-  // strip height: 4 bytes per cell inside a share of what is free now; the grid of the 4 x 4 tiles bounds it too
-  size_t freeB = 0, totalB = 0;
-  TRY(ani_device_memory(ctx, &freeB, &totalB));
-  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)ld));
-  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
-  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, Q), 65535));
-  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat));
-  const size_t piece = std::max<size_t>(1, ((size_t)1 << 21) / (size_t)k);      // queries per copy: 32 MiB of staging at the most
-  ani_signeighbor_t *stage = nullptr; int32_t *stageCnt = nullptr;
-  TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)h) * (size_t)k * 16, (void **)&stage));
-  TRY(pinned_buffer(ctx, 1, (size_t)h * 4, (void **)&stageCnt));
-  for (uint64_t q0 = 0; q0 < Q; q0 += h) {
-    const uint32_t q1 = (uint32_t)std::min<uint64_t>(q0 + h, Q), rows1 = q1 - (uint32_t)q0;
-    sigscreen_launch(st, dRefSig, dRefLen, (uint32_t)nRef, dQrySig, dQryLen, (uint32_t)q0, q1, pitch, size, mode, dMat, ld, ctx->sigScreenTile);
-    hipLaunchKernelGGL(k_sigscreen_select, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)q0, (uint32_t)nRef, minShared,
-                       (const uint32_t *)dTable, minBits, k, dOut, dCnt);
-    HIP_TRY(hipGetLastError());
-    ctx->sigScreenStrips++;
-    HIP_TRY(hipMemcpyAsync(stageCnt, dCnt + q0, (size_t)rows1 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(count + q0, stageCnt, (size_t)rows1 * 4);
-    for (size_t p0 = 0; p0 < rows1; p0 += piece) {
-      const size_t m = std::min<size_t>(piece, rows1 - p0) * (size_t)k;
-      HIP_TRY(hipMemcpyAsync(stage, dOut + ((size_t)q0 + p0) * (size_t)k, m * 16, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      memcpy(out + ((size_t)q0 + p0) * (size_t)k, stage, m * 16);
-    }
-  }
-  return ANI_OK;
-}
-
-int signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                     int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
-{
-  return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, -1, out, count);
-}
-
-// ---- the same under the containment estimate (ani_signature_screen_contain) ----
-int signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                             int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out, int32_t *count)
-{
-  return screen_run(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
-}
-
-// ---- the pair graph under either sketch estimate, streamed (ani_signature_graph) ----
-// The signatures are staged and validated as for ani_signature_neighbors and the identity bits of every (shared, size-or-d) come from
-// the host.  The rows of the range go through the device a strip at a time: the strip's cells right of the diagonal (the triangular
-// Mash tiles of k_sigstrip_merge, or the containment walk in mode MAX with the strip as the queries and the genomes from r0 on as the
-// references, its cell pointer moved r0 columns so that both leave cell (a, b) at row a - r0, column b), the kept cells of every row
-// counted and scanned, then written as records behind the row's offset and copied back through page-locked staging.  The host does no
-// arithmetic on them.  Device memory: the signatures twice while they are staged and once after, 2 s (s + 1) bytes of identities, one
-// strip (kSigStripShare of what is free then, at 24 bytes per cell: the cell and, as if every cell were kept, its record) with 8 bytes
-// per row, 20 bytes per kept pair of the strip.  Host: 20 bytes per kept pair of the range.  Nothing follows nGenomes^2.
-// A strip holds at most kSigGraphMaxPairs cells (a forced height included), so the 32-bit sums of its kept cells are exact.
-constexpr uint64_t kSigGraphMaxPairs = 0xfffffff0ull;
-
-int signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
-                    int32_t estimate, int32_t rowBegin, int32_t rowEnd, ani_sigpair_t **rows, size_t *n)
-{
-  enum { RAW, LEN, SIG, FLAGS, TABLE, MAT, CNT, OFF, OUT, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG, R = (size_t)(rowEnd - rowBegin);
-  const int32_t pitch = (size + 3) & ~3;
-  const uint64_t ld = (V + 3) & ~(uint64_t)3;
-  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dMat, *dOff, *dOut; int32_t *dLen, *dCnt;
-  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
-  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  B.b[RAW].release();
-
-  const bool contain = estimate == ANI_GRAPH_CONTAIN_MAX;
-  const std::vector<uint32_t> table = contain ? sig_contain_table(size, kmerSize) : sig_identity_table(size, kmerSize);
-  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
-  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const float lowest = minIdentity == 0.0f ? 0.0f : minIdentity;      // (-0.0 is 0)
-  uint32_t minBits; memcpy(&minBits, &lowest, 4);
-
-  // strip height: a cell and, as if every cell were kept, its record, inside a share of what is free now; the grid of the thin tile
-  // (one row of queries per workgroup) bounds it too, and so do the 32 bits in which device_scan sums the kept cells of a strip: a strip
-  // of at most 2^32 - 16 cells cannot wrap them, whatever is kept, so the limit check below sees every strip's true count
-  size_t freeB = 0, totalB = 0;
-  TRY(ani_device_memory(ctx, &freeB, &totalB));
-  uint64_t h = (uint64_t)((double)freeB * kSigStripShare / (24.0 * (double)ld));
-  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
-  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(h, R), 65535), kSigGraphMaxPairs / ld));
-  TRY(B.get(MAT, (size_t)(h * ld) * 4, (void **)&dMat)); TRY(B.get(CNT, (size_t)h * 4, (void **)&dCnt)); TRY(B.get(OFF, (size_t)h * 4, (void **)&dOff));
-
-  const size_t piece = (size_t)1 << 20;                                // records per copy: 20 MiB of staging
-  ani_sigpair_t *stage = nullptr;
-  ani_sigpair_t *out = nullptr;
-  size_t have = 0, cap = 0;
-  struct Guard { ani_sigpair_t **p; ~Guard() { free(*p); } } guard{&out};
-  for (uint64_t r0 = (uint64_t)rowBegin; r0 < (uint64_t)rowEnd; r0 += h) {
-    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, (uint64_t)rowEnd), rows1 = r1 - (uint32_t)r0;
-    if (contain) {
-      int32_t shape[2];
-      sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, (uint32_t)(V - r0), dSig, dLen, (uint32_t)r0, r1, pitch, size, ANI_CONTAIN_MAX,
-                       dMat + r0, ld, shape);
-    }
-    else sigstrip_launch(st, dSig, dLen, (uint32_t)nG, (uint32_t)r0, r1, pitch, size, dMat, ld);
-    hipLaunchKernelGGL(k_siggraph_count, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared,
-                       (const uint32_t *)dTable, minBits, dCnt);
-    HIP_TRY(hipGetLastError());
-    ctx->sigGraphStrips++;
-    uint64_t nE = 0;
-    TRY(device_scan(ctx, dCnt, dOff, rows1, &nE, kSigGraphMaxPairs));
-    if ((uint64_t)have + nE > kSigGraphMaxPairs)                       // (before anything of the strip is written)
-      return fail(ANI_ERR_LIMIT, "more than %llu kept pairs in rows [%d, %d): split the range", (unsigned long long)kSigGraphMaxPairs, rowBegin, rowEnd);
-    if (!nE) continue;
-    if (have + (size_t)nE > cap) {
-      const size_t want = std::max<size_t>(have + (size_t)nE, cap + cap / 2);
-      ani_sigpair_t *grown = (ani_sigpair_t *)realloc(out, want * sizeof(ani_sigpair_t));
-      if (!grown) return fail(ANI_ERR_NOMEM, "host allocation of %llu pair rows failed", (unsigned long long)want);
-      out = grown; cap = want;
-    }
-    TRY(B.get(OUT, (size_t)nE * sizeof(ani_sigpair_t), (void **)&dOut));
-    hipLaunchKernelGGL(k_siggraph_write, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, (uint32_t)nG, minShared,
-                       (const uint32_t *)dTable, minBits, (const uint32_t *)dOff, dOut);
-    HIP_TRY(hipGetLastError());
-    TRY(pinned_buffer(ctx, 0, std::min<size_t>(piece, (size_t)nE) * sizeof(ani_sigpair_t), (void **)&stage));
-    for (size_t p0 = 0; p0 < (size_t)nE; p0 += piece) {
-      const size_t m = std::min<size_t>(piece, (size_t)nE - p0);
-      HIP_TRY(hipMemcpyAsync(stage, dOut + p0 * kSigGraphRecordWords, m * sizeof(ani_sigpair_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      memcpy(out + have + p0, stage, m * sizeof(ani_sigpair_t));
-    }
-    have += (size_t)nE;
-  }
-  *rows = out; *n = have;
-  out = nullptr;
-  return ANI_OK;
-}
-
-// ---- greedy representative clustering under the sketch estimate (ani_signature_cluster) ----
-// Strip height at the most, by genome count: the strip's own rows x rows block is merged whether greedy clustering needs its pairs or
-// not, so the blocks together (n h cells) stay at a sixteenth of the n^2 / 2 pairs of the composition, within [256, 4096] rows: below
-// 256 the resolve workgroup's lanes idle and the launches of a strip outweigh its cells, above kSigClusterMaxStrip the covered words
-// of a strip do not fit the LDS the resolve kernel declares.
-static uint64_t sigcluster_strip_cap(uint64_t n) { return std::min<uint64_t>(std::max<uint64_t>(n / 32, 256), (uint64_t)kSigClusterMaxStrip); }
-
-// The strip's own rows x rows block under the containment estimate in mode MAX, from its upper triangle (k_sigcontain_tri, DESIGN.md
-// section 2.22): the square tile of the row pitch at every strip height.  A strip lower than the tile is one diagonal tile, which stages
-// the strip's rows once, so the thin tile of sigscreen_launch has nothing to save here and ANI_TEST_SIG_SCREEN_SHAPE does not act.
-static void sigcontain_tri_launch(hipStream_t st, const uint32_t *sig, const int32_t *len, uint32_t h, int32_t pitch, int32_t size, uint32_t *mat, uint64_t ld)
-{
-  auto tiles = [&](uint32_t t) { const uint32_t n = (h + t - 1) / t; return dim3(n * (n + 1) / 2); };
-  if (pitch <= 256) hipLaunchKernelGGL((k_sigcontain_tri<16, 8192 + kSigContainPad>), tiles(16), dim3(256), 0, st, sig, len, h, pitch, size, mat, ld);
-  else if (pitch <= 1024) hipLaunchKernelGGL((k_sigcontain_tri<16, kSigTileWords + kSigContainPad>), tiles(16), dim3(256), 0, st, sig, len, h, pitch, size, mat, ld);
-  else if (pitch <= 2048) hipLaunchKernelGGL((k_sigcontain_tri<8, kSigTileWords + kSigContainPad>), tiles(8), dim3(64), 0, st, sig, len, h, pitch, size, mat, ld);
-  else hipLaunchKernelGGL((k_sigcontain_tri<4, kSigTileWords + kSigContainPad>), tiles(4), dim3(64), 0, st, sig, len, h, pitch, size, mat, ld);
-}
-
-// The signatures are staged and validated as for ani_signature_pairs and the identity bits of every (shared, size') come from the host.
-// First sweep, strips in id order: the strip against the representatives found before it (k_sigscreen_merge with the representatives'
-// rows as the references, then k_sigcluster_best), the strip against itself and k_sigcluster_resolve, which names the strip's
-// representatives; k_sigcluster_gather appends their rows.  Second sweep: the members of every strip against the representatives found
-// after it.  Every (genome, representative) pair is merged once, and besides them only the pairs inside a strip.  The host waits once
-// per strip of the first sweep, for the count of representatives, which sizes the next launches.  Device memory: the signatures twice
-// while they are staged and once after, the representatives' rows (room for every genome: one more copy at the most), 2 s (s + 1) bytes
-// of identities, 28 bytes per genome, and one strip of rows x max(representatives, rows) 4-byte cells.  Nothing follows nGenomes^2.
-// Shared by the two estimates: mode < 0 is ani_signature_cluster (the Mash merge, sig_identity_table); mode ANI_CONTAIN_MAX is
-// ani_signature_cluster_contain: the containment walk in the rectangular launches, sig_contain_table, and the
-// strip's own block from its upper triangle, whose cells are symmetric in that mode, unless ANI_TEST_SIG_CLUSTER_TRI = 0 (tests,
-// tools/sketch_probe.py) sends it through the full rows x rows launch as well.  stats[2] counts the cells walked: rows (rows - 1) / 2 for
-// a triangular launch.
-static int cluster_run(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
-                       int32_t mode, int32_t *representative, ani_signeighbor_t *link)
-{
-  enum { RAW, LEN, SIG, FLAGS, TABLE, REPSIG, REPLEN, REPID, REPCNT, BEST, CELL, MEMLEN, MAT, NBUF };
-  DevBufs B(NBUF);
-  hipStream_t st = ctx->stream;
-  const size_t V = (size_t)nG;
-  const int32_t pitch = (size + 3) & ~3;
-  auto quads = [](uint64_t x) { return (x + 3) & ~(uint64_t)3; };
-  uint32_t *dRaw, *dSig, *dFlags, *dTable, *dRepSig, *dRepId, *dRepCnt, *dCell, *dMat; int32_t *dLen, *dRepLen, *dMemLen; uint64_t *dBest;
-  TRY(B.get(RAW, V * (size_t)size * 4, (void **)&dRaw)); TRY(B.get(SIG, V * (size_t)pitch * 4, (void **)&dSig));
-  TRY(B.get(LEN, V * 4, (void **)&dLen)); TRY(B.get(FLAGS, 64, (void **)&dFlags));
-  uint32_t *host = nullptr;
-  TRY(pinned_buffer(ctx, 1, 64, (void **)&host));
-  HIP_TRY(hipMemsetAsync(dFlags, 0, 64, st));
-  HIP_TRY(hipMemcpyAsync(dRaw, sig, V * (size_t)size * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(dLen, len, V * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_sigpair_stage, dim3((unsigned)nG), dim3(kTPB), 0, st, (const uint32_t *)dRaw, (const int32_t *)dLen, size, pitch, dSig, dFlags);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(host, dFlags, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (host[0] & 1u) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-  B.b[RAW].release();
-
-  const std::vector<uint32_t> table = mode < 0 ? sig_identity_table(size, kmerSize) : sig_contain_table(size, kmerSize);
-  TRY(B.get(TABLE, table.size() * 4, (void **)&dTable));
-  HIP_TRY(hipMemcpyAsync(dTable, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  uint32_t minBits; memcpy(&minBits, &minIdentity, 4);                 // (> 0: a running best of 0 is "no edge")
-  bool tri = mode >= 0;
-  if (const char *ev = getenv("ANI_TEST_SIG_CLUSTER_TRI")) { if (!strcmp(ev, "0")) tri = false; }
-
-  TRY(B.get(REPSIG, V * (size_t)pitch * 4, (void **)&dRepSig)); TRY(B.get(REPLEN, V * 4, (void **)&dRepLen)); TRY(B.get(REPID, V * 4, (void **)&dRepId));
-  TRY(B.get(REPCNT, 64, (void **)&dRepCnt)); TRY(B.get(BEST, V * 8, (void **)&dBest)); TRY(B.get(CELL, V * 4, (void **)&dCell));
-  TRY(B.get(MEMLEN, V * 4, (void **)&dMemLen));
-  HIP_TRY(hipMemsetAsync(dBest, 0, V * 8, st)); HIP_TRY(hipMemsetAsync(dCell, 0, V * 4, st));
-  // strip height: 4 bytes per cell of a strip against every genome (all of them may be representatives) inside a share of what is free
-  // now, and the cap by genome count
-  size_t freeB = 0, totalB = 0;
-  TRY(ani_device_memory(ctx, &freeB, &totalB));
-  uint64_t h = std::min<uint64_t>((uint64_t)((double)freeB * kSigStripShare / (4.0 * (double)quads(V))), sigcluster_strip_cap(V));
-  if (const char *ev = getenv("ANI_TEST_SIG_STRIP_ROWS")) { const long long v = atoll(ev); if (v >= 1) h = (uint64_t)v; }
-  h = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(h, V), (uint64_t)kSigClusterMaxStrip));
-  uint64_t *stats = ctx->sigClusterStats;
-  int32_t shape[2];
-
-  // first sweep.  repAt[s]: the representatives after strip s; members[s]: its rows that are none
-  std::vector<uint32_t> repAt, members;
-  uint32_t nRep = 0;
-  for (uint64_t r0 = 0; r0 < V; r0 += h) {
-    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V), rows1 = r1 - (uint32_t)r0;
-    // (the stream is idle here: the buffer may move.  Twice the representatives, so that it moves a logarithmic number of times)
-    TRY(B.get(MAT, (size_t)rows1 * (size_t)quads(std::max<uint64_t>(std::min<uint64_t>(2 * (uint64_t)nRep, V), h)) * 4, (void **)&dMat));
-    if (nRep) {
-      const uint64_t ld = quads(nRep);
-      sigscreen_launch(st, dRepSig, dRepLen, nRep, dSig, dLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
-      hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, nRep, (const uint32_t *)dRepId, minShared,
-                         (const uint32_t *)dTable, minBits, dBest, dCell);
-      stats[2] += (uint64_t)rows1 * nRep;
-    }
-    const uint64_t ld = quads(rows1);
-    if (tri) sigcontain_tri_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, pitch, size, dMat, ld);
-    else sigscreen_launch(st, dSig + (size_t)r0 * (size_t)pitch, dLen + r0, rows1, dSig, dLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
-    hipLaunchKernelGGL(k_sigcluster_resolve, dim3(1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, rows1, nRep, minShared, (const uint32_t *)dTable,
-                       minBits, (const int32_t *)dLen, dBest, dCell, dMemLen, dRepId, dRepCnt);
-    HIP_TRY(hipGetLastError());
-    stats[2] += tri ? (uint64_t)rows1 * (rows1 - 1) / 2 : (uint64_t)rows1 * rows1;
-    HIP_TRY(hipMemcpyAsync(host, dRepCnt, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t found = host[0] - nRep;
-    if (found) {
-      hipLaunchKernelGGL(k_sigcluster_gather, dim3(found), dim3(kTPB), 0, st, (const uint32_t *)dSig, (const int32_t *)dLen, (const uint32_t *)dRepId, nRep, pitch,
-                         dRepSig, dRepLen);
-      HIP_TRY(hipGetLastError());
-    }
-    stats[3] += (uint64_t)found * ((rows1 + kTPB - 1) / kTPB);
-    nRep += found;
-    repAt.push_back(nRep); members.push_back(rows1 - found);
-    stats[0]++;
-  }
-  stats[1] = nRep;
-
-  // second sweep: the members of a strip against the representatives found after it (a representative's length is 0 in dMemLen)
-  uint64_t cells = 0;
-  for (size_t s = 0; s < repAt.size(); s++)
-    if (members[s]) cells = std::max<uint64_t>(cells, std::min<uint64_t>(h, V - s * h) * quads(nRep - repAt[s]));
-  HIP_TRY(hipStreamSynchronize(st));                                   // (the last gather; the buffer may move)
-  if (cells) { TRY(B.get(MAT, (size_t)cells * 4, (void **)&dMat)); }
-  for (size_t s = 0; s < repAt.size(); s++) {
-    const uint32_t later = nRep - repAt[s];
-    if (!later || !members[s]) continue;
-    const uint64_t r0 = s * h, ld = quads(later);
-    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + h, V), rows1 = r1 - (uint32_t)r0;
-    sigscreen_launch(st, dRepSig + (size_t)repAt[s] * (size_t)pitch, dRepLen + repAt[s], later, dSig, dMemLen, (uint32_t)r0, r1, pitch, size, mode, dMat, ld, shape);
-    hipLaunchKernelGGL(k_sigcluster_best, dim3(rows1), dim3(kTPB), 0, st, (const uint32_t *)dMat, ld, (uint32_t)r0, later, (const uint32_t *)dRepId + repAt[s],
-                       minShared, (const uint32_t *)dTable, minBits, dBest, dCell);
-    HIP_TRY(hipGetLastError());
-    stats[2] += (uint64_t)rows1 * later;
-  }
-
-  // the keys back, decoded on the host; the identities are host arithmetic (ani_abi.h)
-  std::vector<uint64_t> best(V); std::vector<uint32_t> cell(V);
-  HIP_TRY(hipMemcpyAsync(best.data(), dBest, V * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(cell.data(), dCell, V * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const size_t step = 8192;
-  parallel_for((V + step - 1) / step, (uint64_t)V * 64, [&](size_t blk) {
-    for (size_t i = blk * step; i < std::min(V, (blk + 1) * step); i++) {
-      if (!best[i]) { representative[i] = (int32_t)i; link[i] = ani_signeighbor_t{-1, 0, 0, 0.0f}; continue; }
-      const int32_t rep = (int32_t)(0xffffffffu - (uint32_t)best[i]), sh = (int32_t)(cell[i] >> 16), sz = (int32_t)(cell[i] & 0xffffu);
-      representative[i] = rep;
-      link[i] = ani_signeighbor_t{rep, sh, sz, mode < 0 ? sig_identity(sh, sz, kmerSize) : sig_contain_identity(sh, sz, kmerSize)};
-    }
-  });
-  return ANI_OK;
-}
-
-int signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity,
-                      int32_t *representative, ani_signeighbor_t *link)
-{
-  return cluster_run(ctx, sig, len, nG, size, kmerSize, minShared, minIdentity, -1, representative, link);
-}
-
-// ---- the same under the containment estimate (ani_signature_cluster_contain) ----
-int signature_cluster_contain(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nG, int32_t size, int32_t kmerSize, int32_t minShared,
-                              float minIdentity, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
-{
-  return cluster_run(ctx, sig, len, nG, size, kmerSize, minShared, minIdentity, mode, representative, link);
-}
 
 }  // namespace anih
 
@@ -2795,259 +1470,12 @@ int ani_sketch_ci_end(ani_sketch *sk)
   return ANI_OK;
 }
 
-int ani_cluster_greedy(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float minIdentity, int32_t *representative, float *identityToRep)
-{
-  if (!ctx || (n && !rows) || (nGenomes > 0 && (!representative || !identityToRep))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (!(minIdentity > 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside (0, 100]", (double)minIdentity);
-  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
-  HIP_TRY(hipSetDevice(ctx->device));
-  return cluster_greedy(ctx, rows, n, nGenomes, minIdentity, representative, identityToRep);
-}
-
-int ani_tree_average(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *height)
-{
-  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
-  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the tree takes at most 65536", nGenomes);
-  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
-  if (nGenomes <= 1) return ANI_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return tree_average(ctx, rows, n, nGenomes, missingIdentity, children, height);
-}
-
-int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *length)
-{
-  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !length))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
-  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the tree takes at most 65536", nGenomes);
-  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
-  if (nGenomes <= 1) return ANI_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return tree_nj(ctx, rows, n, nGenomes, missingIdentity, children, length);
-}
-
-int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, int32_t *children, float *height,
-                    int32_t *edges)
-{
-  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
-  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the cluster ids of the tree take at most 2^30", nGenomes);
-  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
-  if (nGenomes <= 1) return ANI_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  try { return tree_single(ctx, rows, n, nGenomes, missingIdentity, children, height, edges); }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_tree_single_rounds(const ani_ctx *ctx) { return ctx ? ctx->treeSingleRounds : 0; }
-
-int ani_tree_single_sketch(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity, const uint32_t *sig, const int32_t *len,
-                           int32_t size, int32_t kmerSize, int32_t minShared, int32_t *children, float *height, int32_t *edges, uint8_t *source)
-{
-  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !height || !sig || !len))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
-  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the cluster ids of the tree take at most 2^30", nGenomes);
-  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
-  if (nGenomes <= 1) return ANI_OK;
-  for (int32_t g = 0; g < nGenomes; g++)
-    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
-  HIP_TRY(hipSetDevice(ctx->device));
-  try { return tree_single_sketch(ctx, rows, n, nGenomes, missingIdentity, sig, len, size, kmerSize, minShared, children, height, edges, source); }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_tree_single_sketch_strips(const ani_ctx *ctx, uint64_t *edgesPerStrip, size_t cap)
-{
-  if (!ctx) return 0;
-  for (size_t i = 0; i < ctx->sigStripEdges.size() && i < cap && edgesPerStrip; i++) edgesPerStrip[i] = ctx->sigStripEdges[i];
-  return (int)ctx->sigStripEdges.size();
-}
-
-int ani_sketch_signatures(const ani_sketch *sk, int32_t size, uint32_t *sig, int32_t *len)
-{
-  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (sk->nGenomes > 0 && (!sig || !len)) return fail(ANI_ERR_ARG, "null argument");
-  if (sk->nGenomes <= 0) return ANI_OK;
-  HIP_TRY(hipSetDevice(sk->device));
-  return sketch_signatures(sk, size, sig, len);
-}
-
-int ani_signature_pairs(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                        ani_sigpair_t **rows, size_t *n)
-{
-  if (!ctx || !rows || !n || (nGenomes > 0 && (!sig || !len))) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 0) return fail(ANI_ERR_ARG, "negative minShared");
-  if (nGenomes > 65536) return fail(ANI_ERR_LIMIT, "%d genomes: the pair step takes at most 65536", nGenomes);
-  for (int32_t g = 0; g < nGenomes; g++)
-    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
-  if (nGenomes <= 1) {                                                 // nothing to compare; a lone row is still checked
-    for (int32_t r = 1; nGenomes == 1 && r < len[0]; r++)
-      if (sig[r - 1] >= sig[r]) return fail(ANI_ERR_ARG, "a signature does not ascend strictly");
-    *rows = (ani_sigpair_t *)malloc(sizeof(ani_sigpair_t)); *n = 0;
-    return *rows ? ANI_OK : fail(ANI_ERR_NOMEM, "host allocation failed");
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  return signature_pairs(ctx, sig, len, nGenomes, size, kmerSize, minShared, rows, n);
-}
-
-
-int ani_signature_neighbors(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                            float minIdentity, int32_t k, int32_t rowBegin, int32_t rowEnd, ani_signeighbor_t *out, int32_t *count)
-{
-  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
-  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
-  if (k < 1 || k > ani::kSigNeighMaxK) return fail(ANI_ERR_ARG, "k %d outside [1, %d]", k, ani::kSigNeighMaxK);
-  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the neighbour lists take at most 2^30", nGenomes);
-  if (rowBegin < 0 || rowBegin > rowEnd || rowEnd > nGenomes) return fail(ANI_ERR_ARG, "rows [%d, %d) outside [0, %d]", rowBegin, rowEnd, nGenomes);
-  ctx->sigNeighStrips = 0;
-  if (nGenomes == 0 || rowBegin == rowEnd) return ANI_OK;
-  if (!sig || !len || !out || !count) return fail(ANI_ERR_ARG, "null argument");
-  for (int32_t g = 0; g < nGenomes; g++)
-    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
-  HIP_TRY(hipSetDevice(ctx->device));
-  try { return signature_neighbors(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, k, rowBegin, rowEnd, out, count); }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_signature_neighbors_strips(const ani_ctx *ctx) { return ctx ? ctx->sigNeighStrips : 0; }
-
-int ani_signature_graph(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                        float minIdentity, int32_t estimate, int32_t rowBegin, int32_t rowEnd, ani_sigpair_t **rows, size_t *n)
-{
-  if (!ctx || !rows || !n) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
-  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
-  if (estimate < ANI_GRAPH_MASH || estimate > ANI_GRAPH_CONTAIN_MAX) return fail(ANI_ERR_ARG, "estimate %d outside [0, 1]", estimate);
-  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the pair graph takes at most 2^30", nGenomes);
-  if (rowBegin < 0 || rowBegin > rowEnd || rowEnd > nGenomes) return fail(ANI_ERR_ARG, "rows [%d, %d) outside [0, %d]", rowBegin, rowEnd, nGenomes);
-  ctx->sigGraphStrips = 0;
-  *rows = nullptr; *n = 0;
-  if (nGenomes <= 1 || rowBegin == rowEnd) return ANI_OK;
-  if (!sig || !len) return fail(ANI_ERR_ARG, "null argument");
-  for (int32_t g = 0; g < nGenomes; g++)
-    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
-  HIP_TRY(hipSetDevice(ctx->device));
-  try { return signature_graph(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, estimate, rowBegin, rowEnd, rows, n); }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_signature_graph_strips(const ani_ctx *ctx) { return ctx ? ctx->sigGraphStrips : 0; }
-
-// the two screen calls: the checks of ani_signature_screen's rules 4 - 6 and, with `contain`, of ani_signature_screen_contain's rule 7,
-// then the call; without `contain` it is ani_signature_screen and the mode plays no part
-static int screen_entry(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                        int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, bool contain, int32_t mode, ani_signeighbor_t *out,
-                        int32_t *count)
-{
-  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
-  if (nRef < 0 || nQry < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
-  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
-  if (k < 1 || k > ani::kSigNeighMaxK) return fail(ANI_ERR_ARG, "k %d outside [1, %d]", k, ani::kSigNeighMaxK);
-  if (contain && (mode < ANI_CONTAIN_QUERY || mode > ANI_CONTAIN_MAX)) return fail(ANI_ERR_ARG, "containment mode %d outside [0, 2]", mode);
-  if (nRef > (1 << 30) || nQry > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d references, %d queries: the screen takes at most 2^30 of either", nRef, nQry);
-  ctx->sigScreenStrips = 0; ctx->sigScreenTile[0] = ctx->sigScreenTile[1] = 0;
-  if (nQry == 0) return ANI_OK;
-  if (!qrySig || !qryLen || !out || !count || (nRef > 0 && (!refSig || !refLen))) return fail(ANI_ERR_ARG, "null argument");
-  for (int32_t g = 0; g < nRef; g++)
-    if (refLen[g] < 0 || refLen[g] > size) return fail(ANI_ERR_ARG, "reference signature %d has length %d outside [0, %d]", g, refLen[g], size);
-  for (int32_t g = 0; g < nQry; g++)
-    if (qryLen[g] < 0 || qryLen[g] > size) return fail(ANI_ERR_ARG, "query signature %d has length %d outside [0, %d]", g, qryLen[g], size);
-  HIP_TRY(hipSetDevice(ctx->device));
-  try {
-    if (contain) return signature_screen_contain(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, mode, out, count);
-    return signature_screen(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, out, count);
-  }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_signature_screen(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen, int32_t nQry,
-                         int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, ani_signeighbor_t *out, int32_t *count)
-{
-  return screen_entry(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, false, -1, out, count);
-}
-
-int ani_signature_screen_contain(ani_ctx *ctx, const uint32_t *refSig, const int32_t *refLen, int32_t nRef, const uint32_t *qrySig, const int32_t *qryLen,
-                                 int32_t nQry, int32_t size, int32_t kmerSize, int32_t minShared, float minIdentity, int32_t k, int32_t mode, ani_signeighbor_t *out,
-                                 int32_t *count)
-{
-  return screen_entry(ctx, refSig, refLen, nRef, qrySig, qryLen, nQry, size, kmerSize, minShared, minIdentity, k, true, mode, out, count);
-}
-
-int ani_signature_screen_strips(const ani_ctx *ctx) { return ctx ? ctx->sigScreenStrips : 0; }
-
-void ani_signature_screen_tile(const ani_ctx *ctx, int32_t *tileQueries, int32_t *tileRefs)
-{
-  if (tileQueries) *tileQueries = ctx ? ctx->sigScreenTile[0] : 0;
-  if (tileRefs) *tileRefs = ctx ? ctx->sigScreenTile[1] : 0;
-}
-
-// the two cluster calls: the checks of ani_signature_cluster's rules 6 - 8 and, with `contain`, of the mode, then the call; without
-// `contain` it is ani_signature_cluster and the mode plays no part
-static int cluster_entry(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                         float minIdentity, bool contain, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
-{
-  if (!ctx) return fail(ANI_ERR_ARG, "null argument");
-  if (nGenomes < 0) return fail(ANI_ERR_ARG, "negative genome count");
-  if (size < 1 || size > kSigMaxSize) return fail(ANI_ERR_ARG, "signature size %d outside [1, %d]", size, kSigMaxSize);
-  if (kmerSize < 1 || kmerSize > 16) return fail(ANI_ERR_ARG, "kmerSize %d outside [1, 16]", kmerSize);
-  if (minShared < 1) return fail(ANI_ERR_ARG, "minShared %d below 1", minShared);
-  if (!(minIdentity > 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside (0, 100]", (double)minIdentity);
-  if (contain && (mode < ANI_CONTAIN_QUERY || mode > ANI_CONTAIN_MAX)) return fail(ANI_ERR_ARG, "containment mode %d outside [0, 2]", mode);
-  if (contain && mode != ANI_CONTAIN_MAX)
-    return fail(ANI_ERR_ARG, "containment mode %d: the greedy rule needs a symmetric estimate, ANI_CONTAIN_MAX", mode);
-  if (nGenomes > (1 << 30)) return fail(ANI_ERR_LIMIT, "%d genomes: the clustering takes at most 2^30", nGenomes);
-  for (uint64_t &x : ctx->sigClusterStats) x = 0;
-  if (nGenomes == 0) return ANI_OK;
-  if (!sig || !len || !representative || !link) return fail(ANI_ERR_ARG, "null argument");
-  for (int32_t g = 0; g < nGenomes; g++)
-    if (len[g] < 0 || len[g] > size) return fail(ANI_ERR_ARG, "signature %d has length %d outside [0, %d]", g, len[g], size);
-  HIP_TRY(hipSetDevice(ctx->device));
-  try {
-    if (contain) return signature_cluster_contain(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, mode, representative, link);
-    return signature_cluster(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, representative, link);
-  }
-  catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
-}
-
-int ani_signature_cluster(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                          float minIdentity, int32_t *representative, ani_signeighbor_t *link)
-{
-  return cluster_entry(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, false, -1, representative, link);
-}
-
-int ani_signature_cluster_contain(ani_ctx *ctx, const uint32_t *sig, const int32_t *len, int32_t nGenomes, int32_t size, int32_t kmerSize, int32_t minShared,
-                                  float minIdentity, int32_t mode, int32_t *representative, ani_signeighbor_t *link)
-{
-  return cluster_entry(ctx, sig, len, nGenomes, size, kmerSize, minShared, minIdentity, true, mode, representative, link);
-}
-
-int ani_signature_cluster_stats(const ani_ctx *ctx, uint64_t out[4])
-{
-  if (!out) return fail(ANI_ERR_ARG, "null argument");
-  for (int i = 0; i < 4; i++) out[i] = ctx ? ctx->sigClusterStats[i] : 0;
-  return ANI_OK;
-}
-
 }  // extern "C"
+
+// tests/emu/Makefile compiles every unit on its own and says so with ANI_EMU_UNITS_SPLIT.  A tests/ directory from before
+// engine_graph.hip and engine_sig.hip existed (an older suite run over this tree) lists neither and defines nothing: for that Makefile
+// alone the two units that came out of this one are compiled with it.  hipcc never takes this branch (build_lib.sh).
+#if defined(ANI_HIP_EMU) && !defined(ANI_EMU_UNITS_SPLIT)
+#include "engine_graph.hip"
+#include "engine_sig.hip"
+#endif

@@ -4,7 +4,9 @@
 //   engine_ingest.hip  sequence batches: classify, 2-bit pack, upload                                  
 //   engine_sketch.hip  minimizer records and fragment sketches (≙ Sketch::build, Map::doL1Mapping's sketch), kept fragment sets + wire format
 //   engine_index.hip   index chunks (≙ Sketch::index), chunk streaming, sketch file                    (winSketch.hpp:181-193; section 8 f3)
-// engine_map.hip     L1 + L2 + identity + reducer (≙ Map::mapQuery ... cgi::computeCGI)              (computeMap.hpp:112-545, computeCoreIdentity.hpp:166-298)
+//   engine_map.hip     L1 + L2 + identity + reducer (≙ Map::mapQuery ... cgi::computeCGI)              (computeMap.hpp:112-545, computeCoreIdentity.hpp:166-298)
+//   engine_graph.hip   what works on finished ANI rows: greedy clustering, the average-linkage, neighbour-joining and single-linkage trees
+//   engine_sig.hip     the whole-genome sketch estimate: signatures, all pairs, and the streamed calls (tree fill, neighbours, screens, graph, clustering)
 //   engine_l2.hip      the launches of k_l2_codes / k_l2_sim (a unit of its own for its compiler flags: build_lib.sh)
 //   sort_device.hip    the radix sort
 //   prim_check.hip     test infrastructure: the primitives of kernels/common.hpp and the prefix sum, callable on their own
@@ -756,6 +758,29 @@ ani_sketch *new_sketch(ani_ctx *ctx, const ani_params_t *p, const int32_t *conti
 int ensure_chunk(ani_sketch *sk, size_t i, int pin = -1);
 int add_chunks(ani_ctx *ctx, ani_sketch *sk, std::vector<RecordPart> &parts);
 int exact_unique(ani_sketch *sk);
+// ---- engine_graph.hip: the pieces of ani_tree_single, which ani_tree_single_sketch (engine_sig.hip) runs strip by strip ----
+// edges on the device, every buffer the pool's: (lo, hi)-ordered with their sort input (dKey, idx), or ranked (lo, hi, d, src by rank)
+struct SingleEdges {
+  DevBuf lo, hi, dKey, idx, d, src; uint32_t n = 0;
+  SingleEdges() = default; SingleEdges(const SingleEdges &) = delete;
+  ~SingleEdges() { release(); }
+  void release() { for (DevBuf *x : {&lo, &hi, &dKey, &idx, &d, &src}) x->release(); n = 0; }
+  void swap(SingleEdges &o) { std::swap(lo, o.lo); std::swap(hi, o.hi); std::swap(dKey, o.dKey); std::swap(idx, o.idx); std::swap(d, o.d); std::swap(src, o.src); std::swap(n, o.n); }
+};
+// the device buffers of one call: every one the pool's, all released on return
+struct DevBufs {
+  std::vector<DevBuf> b;
+  explicit DevBufs(size_t n) : b(n) {}
+  DevBufs(const DevBufs &) = delete;
+  ~DevBufs() { for (DevBuf &x : b) x.release(); }
+  int get(int i, size_t bytes, void **out) { const int rc = b[(size_t)i].ensure(bytes ? bytes : 1); *out = b[(size_t)i].p; return rc; }
+};
+inline int id_bits(int32_t nG) { int b = 1; while (b < 31 && ((uint32_t)(nG - 1) >> b) != 0) b++; return b; }   // bit width of the largest id
+int single_front(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nG, uint32_t dmBits, SingleEdges *edges, DevBuf *pairKeys, uint32_t *nKeys);
+int single_rank(ani_ctx *ctx, SingleEdges *e, uint8_t source);
+int single_merge(ani_ctx *ctx, SingleEdges *x, SingleEdges *y);
+int single_forest(ani_ctx *ctx, int32_t nG, SingleEdges *e);
+int single_finish(ani_ctx *ctx, const SingleEdges &forest, int32_t nG, float dMissing, int32_t *children, float *height, int32_t *edges, uint8_t *source);
 
 template <class T> int to_host_malloc(const std::vector<T> &v, T **out, size_t *n)
 {

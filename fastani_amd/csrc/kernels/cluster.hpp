@@ -1,5 +1,5 @@
 // cluster.hpp — greedy ANI clustering of the pair graph (ani_cluster_greedy; no counterpart in the reference, which stops at the
-// rows and the .matrix file).  DESIGN.md section 2.11 states the algorithm; the host side is cluster_greedy in engine_map.hip.
+// rows and the .matrix file).  DESIGN.md section 2.11 states the algorithm; the host side is cluster_greedy in engine_graph.hip.
 //
 //   k_cluster_keys     row -> key min << b | max (b = bit width of the genome ids) and its position; ids checked
 //   (stable radix sort of the keys: the rows of one pair end up adjacent, in the order they were given)

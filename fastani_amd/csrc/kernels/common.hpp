@@ -20,6 +20,9 @@ namespace ani {
 constexpr int kWave = 64;
 constexpr int kTPB = 256;             // threads per workgroup for all cooperative kernels (4 waves)
 constexpr uint32_t kMurmurSeed = 42;  // commonFunc.hpp:32
+// single.hpp: no best edge (ranks are below 2^32 - 16); sigstrip.hpp: a cell that is no edge.  Here because the two are compiled in
+// different units (engine_graph.hip, engine_sig.hip), and a header's plain kernels are emitted by every unit that includes it.
+constexpr uint32_t kSingleNone = 0xffffffffu;
 
 // Statistics counters (sums only, never cursors) are striped over kStatStripes copies of the counter block so that the
 // per-wave atomics of a large grid do not serialise on one address; the host adds the stripes up.

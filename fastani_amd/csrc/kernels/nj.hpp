@@ -1,5 +1,5 @@
 // nj.hpp — neighbour-joining tree of the genomes (ani_tree_nj; no counterpart in the reference, which stops at the rows and the
-// .matrix file).  include/ani_abi.h states the semantics, DESIGN.md section 2.13 the algorithm; the host side is tree_nj in engine_map.hip.
+// .matrix file).  include/ani_abi.h states the semantics, DESIGN.md section 2.13 the algorithm; the host side is tree_nj in engine_graph.hip.
 //
 //   (k_tree_check, k_cluster_keys and the stable radix sort of the keys: as for the average-linkage tree — tree.hpp, cluster.hpp)
 //   k_nj_fill      the dense matrix q (n rows of ld int32, ld = n rounded up to 64): q_missing, the sentinel on the diagonal and in the padding

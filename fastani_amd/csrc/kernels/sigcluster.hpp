@@ -1,5 +1,5 @@
 // sigcluster.hpp — greedy representative clustering of the genomes under the whole-genome sketch estimate (ani_signature_cluster; no
-// counterpart in the reference).  DESIGN.md section 2.20 states the algorithm; the host side is signature_cluster in engine_map.hip.
+// counterpart in the reference).  DESIGN.md section 2.20 states the algorithm; the host side is signature_cluster in engine_sig.hip.
 // The signatures are staged by k_sigpair_stage (sigdist.hpp) and the cells come from k_sigscreen_merge (sigscreen.hpp), launched as it
 // is: the strip's rows are its queries, and its references are either the signature rows of the representatives, kept contiguous in an
 // array of their own, or the strip itself.  For the rows [r0, r1) of a strip:

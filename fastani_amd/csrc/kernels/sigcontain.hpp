@@ -1,6 +1,6 @@
 // sigcontain.hpp — the nearest references of every query genome under the containment estimate (ani_signature_screen_contain; no
 // counterpart in the reference).  DESIGN.md section 2.19 states the algorithm; the host side is signature_screen_contain in
-// engine_map.hip.  Staging, strips, tile shapes and the select are those of sigscreen.hpp; what differs is the walk of a pair and what
+// engine_sig.hip.  Staging, strips, tile shapes and the select are those of sigscreen.hpp; what differs is the walk of a pair and what
 // its cell holds:
 //
 //   k_sigcontain_merge  one tile of TQ queries x TR references per workgroup, one walk per lane; cell (q - q0, r) of a (q1 - q0) x ld

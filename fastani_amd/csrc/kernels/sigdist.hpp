@@ -1,6 +1,6 @@
 // sigdist.hpp — whole-genome sketch ANI: bottom-s signatures of the reference genomes out of their minimizer records, and the
 // all-pairs comparison of signatures (ani_sketch_signatures, ani_signature_pairs; no counterpart in the reference, which knows no
-// genome-level sketch).  DESIGN.md section 2.14 states the algorithm; the host side is in engine_map.hip.
+// genome-level sketch).  DESIGN.md section 2.14 states the algorithm; the host side is in engine_sig.hip.
 //
 //   signatures, per index chunk (records = the chunk's index arrays, or the 12-byte records a streamed set keeps):
 //   k_sig_count     per block of kSigBlock records, the records whose hash is at or below their genome's threshold
@@ -126,7 +126,7 @@ static __global__ __launch_bounds__(kTPB) void k_sigpair_stage(const uint32_t *_
 // `size` elements of U or when a row is used up; from there U only has the other row's tail, which shares nothing:
 //   size(a, b) = min(size, steps + what is left of either row),   shared(a, b) = ties among the steps.
 // Integers only and one lane per pair: no atomics, no dependence on any order.  T and the LDS words are chosen by the host from the
-// row pitch (sigpair_launch in engine_map.hip); pairs with b <= a, and genomes beyond n, are skipped.
+// row pitch (sigpair_launch in engine_sig.hip); pairs with b <= a, and genomes beyond n, are skipped.
 // sigpair_tile is the tile itself, shared with the strip kernel (sigstrip.hpp): tile coordinates count from genome `base`, rows end at
 // rowEnd, and the cell of (a, b) is mat[(a - base) * ld + b].  The whole matrix is base = 0, rowEnd = n.
 // the merge of one pair, rows A and B of lengths la and lb (in LDS): shared << 16 | size

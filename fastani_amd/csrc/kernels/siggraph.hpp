@@ -1,5 +1,5 @@
 // siggraph.hpp — the pair graph of the genomes under the whole-genome sketch estimates, streamed (ani_signature_graph; no counterpart in
-// the reference).  DESIGN.md section 2.21 states the algorithm; the host side is signature_graph in engine_map.hip.  The signatures are
+// the reference).  DESIGN.md section 2.21 states the algorithm; the host side is signature_graph in engine_sig.hip.  The signatures are
 // staged by k_sigpair_stage (sigdist.hpp); for the rows [r0, r1) of the pair matrix:
 //
 //   (cells)           Mash: k_sigstrip_merge (sigstrip.hpp), the triangular tiles counted from genome r0.  Containment:

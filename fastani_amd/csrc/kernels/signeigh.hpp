@@ -1,5 +1,5 @@
 // signeigh.hpp — the nearest neighbours of every genome under the whole-genome sketch estimate (ani_signature_neighbors; no counterpart
-// in the reference).  DESIGN.md section 2.17 states the algorithm; the host side is signature_neighbors in engine_map.hip.  The
+// in the reference).  DESIGN.md section 2.17 states the algorithm; the host side is signature_neighbors in engine_sig.hip.  The
 // signatures are staged by k_sigpair_stage (sigdist.hpp); for the rows [r0, r1) of the pair matrix:
 //
 //   k_signeigh_merge   the rectangular form of the merge tile: row tiles count from genome r0, column tiles from genome 0, every tile

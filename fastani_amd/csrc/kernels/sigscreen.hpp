@@ -1,5 +1,5 @@
 // sigscreen.hpp — the nearest references of every query genome under the whole-genome sketch estimate (ani_signature_screen; no
-// counterpart in the reference).  DESIGN.md section 2.18 states the algorithm; the host side is signature_screen in engine_map.hip.
+// counterpart in the reference).  DESIGN.md section 2.18 states the algorithm; the host side is signature_screen in engine_sig.hip.
 // Both sets are staged by k_sigpair_stage (sigdist.hpp) into arrays of their own; for the queries [q0, q1) of a strip:
 //
 //   k_sigscreen_merge   one tile of TQ queries x TR references per workgroup, one merge per lane; cell (q - q0, r) of a (q1 - q0) x ld

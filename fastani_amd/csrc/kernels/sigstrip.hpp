@@ -1,5 +1,5 @@
 // sigstrip.hpp — the sketch pairs of a strip of genomes as edges of the single-linkage forest (ani_tree_single_sketch; no counterpart in
-// the reference).  DESIGN.md section 2.16 states the algorithm; the host side is tree_single_sketch in engine_map.hip.  The signatures are
+// the reference).  DESIGN.md section 2.16 states the algorithm; the host side is tree_single_sketch in engine_sig.hip.  The signatures are
 // staged by k_sigpair_stage (sigdist.hpp); for the rows [r0, r1) of the pair matrix:
 //
 //   k_sigstrip_merge  the tiles of sigdist.hpp (sigpair_tile) counted from genome r0: cell (a, b > a) of an (r1 - r0) x ld strip,
@@ -16,7 +16,6 @@
 #include "../../../include/ani_abi.h"
 #include "common.hpp"
 #include "sigdist.hpp"
-#include "single.hpp"
 
 namespace ani {
 

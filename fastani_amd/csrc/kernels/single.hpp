@@ -1,6 +1,6 @@
 // single.hpp — single-linkage tree of the genomes = the minimum spanning forest of the pair graph (ani_tree_single; no counterpart in the
 // reference, which stops at the rows and the .matrix file).  DESIGN.md section 2.15 states the algorithm; the host side is tree_single
-// in engine_map.hip.
+// in engine_graph.hip.
 //
 //   (k_tree_check, k_cluster_keys and the stable radix sort of the keys: the rows of a pair adjacent, in the order given)
 //   k_single_flag     per sorted position: 1 where a pair starts whose folded d lies below d_missing (an edge), else 0
@@ -8,7 +8,7 @@
 //   k_single_pairs    the edges, compacted: lo, hi, and bits(d) as the key of the second sort with the edge's position as its payload
 //   (stable radix sort over the 32 bits of d: position r of the result is the edge of rank r in the order (bits(d), lo, hi))
 //   k_single_rank     lo, hi, bits(d) and a source byte of every edge by rank: a ranked edge list
-//   (the forest stage, single_forest in engine_map.hip, over a ranked edge list:)
+//   (the forest stage, single_forest in engine_graph.hip, over a ranked edge list:)
 //   k_single_init     every vertex its own component, no best edge
 //   per round (Boruvka):
 //   k_single_best     a live edge whose ends lie in two components offers its rank to both (atomicMin) and stays live
@@ -36,8 +36,6 @@
 #include "tree.hpp"
 
 namespace ani {
-
-constexpr uint32_t kSingleNone = 0xffffffffu;          // no best edge (ranks are below 2^32 - 16)
 
 static __global__ void k_single_flag(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, const ani_cgi_t *__restrict__ rows,
                                      uint64_t n, int b, uint32_t dmBits, int32_t *__restrict__ flag)

@@ -1,5 +1,5 @@
 // tree.hpp — average-linkage (UPGMA) tree of the genomes (ani_tree_average; no counterpart in the reference, which stops at the rows
-// and the .matrix file).  DESIGN.md section 2.12 states the algorithm; the host side is tree_average in engine_map.hip.
+// and the .matrix file).  DESIGN.md section 2.12 states the algorithm; the host side is tree_average in engine_graph.hip.
 //
 //   k_tree_check   a row identity outside (0, 100] (NaN included) sets a flag
 //   (k_cluster_keys and the stable radix sort of the keys: the rows of a pair adjacent, in the order given — cluster.hpp)

@@ -16,7 +16,7 @@ def main():
     else:
         td = tempfile.mkdtemp()
         paths = []
-        for u in ("engine_core", "engine_ingest", "engine_sketch", "engine_index", "engine_map", "sort_device"):
+        for u in ("engine_core", "engine_ingest", "engine_sketch", "engine_index", "engine_map", "engine_graph", "engine_sig", "sort_device"):
             path = os.path.join(td, u + ".s")
             subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", path,
                                    os.path.join(ROOT, "fastani_amd", "csrc", u + ".hip")], stderr=subprocess.DEVNULL)

@@ -62,7 +62,7 @@ def hub_rows(m):
 
 
 def nj_scan_bytes(n):
-    """what the scans of one ani_tree_nj call read, by the host loop of tree_nj (engine_map.hip): record s scans the tiles of 256
+    """what the scans of one ani_tree_nj call read, by the host loop of tree_nj (engine_graph.hip): record s scans the tiles of 256
     columns x 16 or 64 rows that reach above the diagonal of the current matrix, 4 bytes per cell, and the matrix is compacted to the
     active positions whenever an eighth of its positions is retired -> (bytes, cells of the active upper triangles: the n^3 / 6)"""
     cur, total, ideal = n, 0, 0
