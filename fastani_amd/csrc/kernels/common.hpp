@@ -78,15 +78,25 @@ __host__ __device__ __forceinline__ uint64_t fmix64(uint64_t z)
   return xorshr33(z);
 }
 
+// x * 5 + c (c < 2^63) on the dword halves: the low product carries into the high dword through one v_mad_u64_u32, the high dword is
+// 32-bit arithmetic.  The plain 64-bit expression compiles to two v_mad_u64_u32 of which the second is used for its low dword only, and
+// as 64-bit operands sit in even-aligned register pairs each of them costs a v_mov_b32 into and one out of a pair: four moves per hash,
+// all the moves the hash block had (profiles/r13_sketch_diet_isa.txt).
+__host__ __device__ __forceinline__ uint64_t mul5_add(uint64_t x, uint32_t c)
+{
+  const uint64_t addend = ((uint64_t)((uint32_t)(x >> 32) * 5u) << 32) | c;
+  return (uint64_t)(uint32_t)x * 5u + addend;
+}
+
 // k == 16: exactly one body block, empty tail (murmur3.h:245-254, :290-298)
 __host__ __device__ __forceinline__ uint32_t murmur32_k16(uint64_t k1, uint64_t k2)
 {
   const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
   uint64_t h1 = kMurmurSeed, h2 = kMurmurSeed;
   k1 *= c1; k1 = rotl64(k1, 31); k1 *= c2; h1 ^= k1;
-  h1 = rotl64(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
+  h1 = rotl64(h1, 27); h1 = mul5_add(h1, 5u * kMurmurSeed + 0x52dce729u);   // h1 += h2 (still the seed); h1 = h1 * 5 + 0x52dce729
   k2 *= c2; k2 = rotl64(k2, 33); k2 *= c1; h2 ^= k2;
-  h2 = rotl64(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
+  h2 = rotl64(h2, 31); h2 += h1; h2 = mul5_add(h2, 0x38495ab5);
   h1 ^= 16; h2 ^= 16;
   h1 += h2; h2 += h1;
   h1 = fmix64(h1); h2 = fmix64(h2);
@@ -179,6 +189,40 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v)
 #endif
 }
 
+// Inclusive max- and min-scans over the same six DPP steps.  Lanes without a source and the rows a step leaves out take the identity
+// of the operation (`old`), which also lets the compiler fold each step into one v_max_i32_dpp / v_min_i32_dpp; lane 63 ends with the
+// maximum / minimum of the wave.
+__device__ __forceinline__ int wave_incl_maxscan_dpp(int v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int lowest = (int)0x80000000;
+#define ANI_DPP_MAX_STEP(ctrl, rows) { const int o = __builtin_amdgcn_update_dpp(lowest, v, ctrl, rows, 0xf, false); v = o > v ? o : v; }
+  ANI_DPP_MAX_STEP(0x111, 0xf) ANI_DPP_MAX_STEP(0x112, 0xf) ANI_DPP_MAX_STEP(0x114, 0xf) ANI_DPP_MAX_STEP(0x118, 0xf)
+  ANI_DPP_MAX_STEP(0x142, 0xa) ANI_DPP_MAX_STEP(0x143, 0xc)
+#undef ANI_DPP_MAX_STEP
+  return v;
+#else
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int d = 1; d < kWave; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v = o > v ? o : v; }
+  return v;
+#endif
+}
+__device__ __forceinline__ int wave_incl_minscan_dpp(int v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int highest = 0x7fffffff;
+#define ANI_DPP_MIN_STEP(ctrl, rows) { const int o = __builtin_amdgcn_update_dpp(highest, v, ctrl, rows, 0xf, false); v = o < v ? o : v; }
+  ANI_DPP_MIN_STEP(0x111, 0xf) ANI_DPP_MIN_STEP(0x112, 0xf) ANI_DPP_MIN_STEP(0x114, 0xf) ANI_DPP_MIN_STEP(0x118, 0xf)
+  ANI_DPP_MIN_STEP(0x142, 0xa) ANI_DPP_MIN_STEP(0x143, 0xc)
+#undef ANI_DPP_MIN_STEP
+  return v;
+#else
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int d = 1; d < kWave; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v = o < v ? o : v; }
+  return v;
+#endif
+}
+
 // Workgroup barrier.  HIP's __syncthreads() is fence(release) + s_barrier + fence(acquire), and the compiler of ROCm 7.2 was seen
 // to drop the s_waitcnt lgkmcnt(0) that the release fence needs in front of a barrier at a loop header (the back edge of the bitonic
 // sort's pass loop: four ds_write_b64 in flight, then s_barrier): a wave then passes the barrier with its LDS writes still queued
@@ -226,7 +270,7 @@ __device__ __forceinline__ uint64_t wave_uniform(uint64_t x) { return (uint64_t)
 __device__ __forceinline__ int block_excl_scan(int v, int *ws, int *total)
 {
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
-  int incl = wave_incl_scan(v);
+  int incl = wave_incl_scan_dpp(v);      // six v_add_u32_dpp; the shuffle form is six ds_bpermute round trips, each with a wait, a select and an add
   block_barrier();                       // protect ws against a previous use
   if (lane == kWave - 1) ws[wv] = incl;
   block_barrier();

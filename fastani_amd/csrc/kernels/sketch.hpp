@@ -153,20 +153,19 @@ __device__ __forceinline__ void hash_positions(const void *seq, int64_t off, int
 // ------------------------------------------------------------------------------------------------
 // Tile core: hashes + window minimum + emission flags.  All 256 threads of the workgroup call it.
 //   keys : LDS, kTile uint64
-//   ws   : LDS scratch, >= kTPB + 8 ints
+//   ws   : LDS scratch, >= 16 ints
 // Outputs per thread: em[j] (emit at own position j), W[j] (window-min key), and block-wide first/last P.
 // ------------------------------------------------------------------------------------------------
 // key[] = this thread's kPer position keys (hash_positions).  lo = first local position that exists for this pass (keys below
 // it must be kSkipKey: a query fragment is winnowed in isolation), windows are evaluated where they end at local positions in
-// [lo + w - 1, hiEmit) and at k-mer starts below nPos.
-__device__ __forceinline__ void tile_winnow_keys(const uint64_t (&key)[kPer], int32_t B, int32_t nPos, int w, int lo, int hiEmit,
+// [lo + w - 1, hiEmit) and at k-mer starts the contig has (beyond them hash_positions gives kSkipKey).
+__device__ __forceinline__ void tile_winnow_keys(const uint64_t (&key)[kPer], int32_t B, int w, int lo, int hiEmit,
                                                  uint64_t *keys, int *ws,
                                                  uint64_t (&W)[kPer], bool (&em)[kPer], int &tileFirstP, int &tileLastP)
 {
   const int t = threadIdx.x;
   const int local0 = t * kPer;
   bool own_ok[kPer];
-  if (t == 0) ws[kTPB + 8] = -1;                   // slot of the tile's first valid P (read after the barriers below)
   if (w >= kPer && w <= 4 * kPer) {
     // ---- window minimum over (i-w, i], w >= kPer: the window of own position j is the own prefix [0, j], a whole number of
     // earlier threads' blocks and a suffix of one more block.  Prefix minima stay in registers, every thread publishes its suffix
@@ -222,38 +221,43 @@ __device__ __forceinline__ void tile_winnow_keys(const uint64_t (&key)[kPer], in
   }
 
   // ---- emission: argmin positions are monotone, so "previous P" is a running maximum ----
-  int P[kPer]; bool val[kPer];
-  int myMax = -1, myFirst = -1;
+  // P = -1 where no window is evaluated; the valid P of a thread do not decrease, so its last is their maximum, its first their
+  // minimum (as unsigned numbers, which puts -1 above them), and "differs from the previous one" is "exceeds the running maximum".
+  // (A k-mer start at or beyond the contig's last one holds kSkipKey, hash_positions: own_ok covers that test.)
+  int P[kPer];
+  int myMax = -1; uint32_t firstU = ~0u;
 #pragma unroll
   for (int j = 0; j < kPer; j++) {
     const int l = local0 + j;
-    val[j] = own_ok[j] && l >= lo + w - 1 && l < hiEmit && (B + l) < nPos;
-    P[j] = val[j] ? (kTile - 1 - (int)(uint32_t)W[j]) : -1;
-    if (val[j]) { if (myFirst < 0) myFirst = P[j]; myMax = P[j]; }
+    const bool val = own_ok[j] && l >= lo + w - 1 && l < hiEmit;
+    P[j] = val ? (kTile - 1 - (int)(uint32_t)W[j]) : -1;
+    myMax = P[j] > myMax ? P[j] : myMax;
+    firstU = (uint32_t)P[j] < firstU ? (uint32_t)P[j] : firstU;
   }
-  // max P over all earlier threads: wave scan by shuffles, one barrier for the wave totals
+  const int myFirst = (int)(firstU & 0x7fffffffu);     // no valid position: 0x7fffffff
+  // max P over all earlier threads and the tile's first valid P (the minimum over the threads): two wave scans over the DPP path and
+  // ONE barrier for the wave results of both
   const int lane = t & (kWave - 1), wv = t >> 6;
-  int v = myMax;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v = o > v ? o : v; }
+  const int v = wave_incl_maxscan_dpp(myMax), vF = wave_incl_minscan_dpp(myFirst);
   int prev = __shfl_up(v, 1); if (lane == 0) prev = -1;
-  if (lane == kWave - 1) ws[wv] = v;
+  if (lane == kWave - 1) { ws[wv] = v; ws[8 + wv] = vF; }
   block_barrier();
-  int lastAll = -1;
+  int lastAll = -1, firstAll = 0x7fffffff;
 #pragma unroll
-  for (int i = 0; i < kTPB / kWave; i++) { const int x = ws[i]; if (i < wv) prev = x > prev ? x : prev; lastAll = x > lastAll ? x : lastAll; }
-  // first valid P in the tile: the thread whose predecessor max is -1 and that has a valid position (exactly one, if any)
-  if (myFirst >= 0 && prev < 0) ws[kTPB + 8] = myFirst;
-  block_barrier();
-  const int firstAll = ws[kTPB + 8];
+  for (int i = 0; i < kTPB / kWave; i++) {
+    const int x = ws[i], y = ws[8 + i];
+    if (i < wv) prev = x > prev ? x : prev;
+    lastAll = x > lastAll ? x : lastAll; firstAll = y < firstAll ? y : firstAll;
+  }
 #pragma unroll
   for (int j = 0; j < kPer; j++) {
-    em[j] = val[j] && P[j] != prev;
-    if (val[j]) prev = P[j];
+    em[j] = P[j] > prev;
+    prev = P[j] > prev ? P[j] : prev;
   }
-  tileFirstP = firstAll >= 0 ? B + firstAll : -1;
+  tileFirstP = firstAll != 0x7fffffff ? B + firstAll : -1;
   tileLastP = lastAll >= 0 ? B + lastAll : -1;
-  block_barrier();
+  // no barrier here: `ws` and `keys` have been read, and whoever writes them next does so behind a barrier of its own (every caller
+  // goes on to block_excl_scan, which opens with one)
 }
 
 template <bool PACKED>
@@ -263,7 +267,7 @@ __device__ __forceinline__ void tile_winnow(const void *seq, int64_t off, int32_
 {
   uint64_t key[kPer];
   hash_positions<PACKED>(seq, off, len, B + (int)threadIdx.x * kPer, (int)threadIdx.x * kPer, k, key);
-  tile_winnow_keys(key, B, len - k + 1, w, 0, kTile, keys, ws, W, em, tileFirstP, tileLastP);
+  tile_winnow_keys(key, B, w, 0, kTile, keys, ws, W, em, tileFirstP, tileLastP);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -292,14 +296,18 @@ static __global__ __launch_bounds__(kTPB) void k_sketch_tiles(const uint32_t *__
   int total; int rank = block_excl_scan(cnt, ws, &total);
   if (threadIdx.x == 0) sBase = pool_take(poolCount, poolCap, (unsigned long long)total);
   block_barrier();
-  const unsigned long long base = sBase & ~kPoolOverflowBit;
-  if (!(sBase & kPoolOverflowBit)) {
+  const unsigned long long sb = wave_uniform((uint64_t)sBase);           // a scalar base and 32-bit byte offsets, as in fused_tile_body
+  const unsigned long long base = sb & ~kPoolOverflowBit;
+  if (!(sb & kPoolOverflowBit)) {
+    char *const hp = (char *)(poolHash + base), *const wp = (char *)(poolWpos + base);
+    uint32_t ob = (uint32_t)rank * 4u;
+    const int32_t wpos0 = td.firstPos + (int)threadIdx.x * kPer - w + 1;
 #pragma unroll
     for (int j = 0; j < kPer; j++)
       if (em[j]) {
-        poolHash[base + rank] = (uint32_t)(W[j] >> 32);
-        poolWpos[base + rank] = td.firstPos + (int)threadIdx.x * kPer + j - w + 1;     // currentWindowId, commonFunc.hpp:124
-        rank++;
+        *(uint32_t *)(hp + ob) = (uint32_t)(W[j] >> 32);
+        *(int32_t *)(wp + ob) = wpos0 + j;                                 // currentWindowId, commonFunc.hpp:124
+        ob += 4u;
       }
   }
   if (threadIdx.x == 0) {
@@ -575,7 +583,7 @@ __device__ __forceinline__ void fused_tile_body(const void *__restrict__ seq, in
   hash_positions<PACKED>(seq, off, len, td.firstPos + local0, local0, k, key);
   uint64_t W[kPer]; bool em[kPer]; int firstP, lastP;
   // ---- reference minimizers (as k_sketch_tiles, windows ending below emitEnd) ----
-  tile_winnow_keys(key, td.firstPos, len - k + 1, w, 0, fi.emitEnd, keys, ws, W, em, firstP, lastP);
+  tile_winnow_keys(key, td.firstPos, w, 0, fi.emitEnd, keys, ws, W, em, firstP, lastP);
   {
     int cnt = 0;
 #pragma unroll
@@ -583,14 +591,20 @@ __device__ __forceinline__ void fused_tile_body(const void *__restrict__ seq, in
     int total; int rank = block_excl_scan(cnt, ws, &total);
     if (threadIdx.x == 0) *sBasePtr = pool_take(poolCount, poolCap, (unsigned long long)total);
     block_barrier();
-    const unsigned long long base = *sBasePtr & ~kPoolOverflowBit;
-    if (!(*sBasePtr & kPoolOverflowBit)) {
+    // the workgroup's place in the pool as a scalar: the records then leave through two scalar bases and one 32-bit byte offset
+    // (global_store_dword v, v, s[..]) instead of two 64-bit addresses built per record
+    const unsigned long long sb = wave_uniform((uint64_t)*sBasePtr);
+    const unsigned long long base = sb & ~kPoolOverflowBit;
+    if (!(sb & kPoolOverflowBit)) {
+      char *const hp = (char *)(poolHash + base), *const wp = (char *)(poolWpos + base);
+      uint32_t ob = (uint32_t)rank * 4u;                                  // below 4 * kTile
+      const int32_t wpos0 = td.firstPos + local0 - w + 1;
 #pragma unroll
       for (int j = 0; j < kPer; j++)
         if (em[j]) {
-          poolHash[base + rank] = (uint32_t)(W[j] >> 32);
-          poolWpos[base + rank] = td.firstPos + local0 + j - w + 1;     // currentWindowId, commonFunc.hpp:124
-          rank++;
+          *(uint32_t *)(hp + ob) = (uint32_t)(W[j] >> 32);
+          *(int32_t *)(wp + ob) = wpos0 + j;                              // currentWindowId, commonFunc.hpp:124
+          ob += 4u;
         }
     }
     if (threadIdx.x == 0) { TileMeta m; m.off = (uint32_t)base; m.cnt = total; m.firstP = firstP; m.lastP = lastP; meta[blockIdx.x] = m; }
@@ -602,32 +616,44 @@ __device__ __forceinline__ void fused_tile_body(const void *__restrict__ seq, in
   // window's" is the same decision too, except at the fragment's first window, which always emits (commonFunc.hpp:152-161: the
   // deque starts empty).  So: the fragment's minimizers = the reference minimizers emitted in that range + its first window's.
   const int f0 = fi.fragLocal0, fEnd = f0 + fragLen - k;     // last k-mer start inside the fragment (local)
-  bool inR[kPer]; int myFirst = 0x7fffffff;
+  // The fragment's minimizers are sorted before they are used, so their order in the staging buffer is free: the emitted ones take
+  // the places a scan gives them and the first window's hash, where that window did not emit, goes behind them.  The scan needs
+  // nothing of the first window then, and its wave totals share one exchange with the wave minima that locate that window.
+  bool inR[kPer]; int myFirst = 0x7fffffff, cnt = 0;
 #pragma unroll
   for (int j = 0; j < kPer; j++) {
     const int l = local0 + j;
     inR[j] = key[j] != kSkipKey && l >= f0 + w - 1 && l <= fEnd;
     if (inR[j] && l < myFirst) myFirst = l;
+    cnt += inR[j] && em[j];
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) { const int o = __shfl_down(myFirst, d); myFirst = o < myFirst ? o : myFirst; }
-  block_barrier();                                  // the reference pass is done with ws / sBasePtr
-  if ((threadIdx.x & (kWave - 1)) == 0) ws[threadIdx.x >> 6] = myFirst;
+  const int lane = (int)threadIdx.x & (kWave - 1), wv = (int)threadIdx.x >> 6;
+  const int incl = wave_incl_scan_dpp(cnt), vF = wave_incl_minscan_dpp(myFirst);
+  // (the reference pass is done with ws: its last reads lie before the barrier that published sBasePtr)
+  if (lane == kWave - 1) { ws[wv] = incl; ws[8 + wv] = vF; }
+  if (threadIdx.x == 0) ws[16] = 0;                 // set below: the first window's hash was added
   block_barrier();
-  int firstL = 0x7fffffff;
+  int rank = incl - cnt, emitted = 0, firstL = 0x7fffffff;
 #pragma unroll
-  for (int i = 0; i < kTPB / kWave; i++) { const int x = ws[i]; firstL = x < firstL ? x : firstL; }
+  for (int i = 0; i < kTPB / kWave; i++) {
+    const int x = ws[i], y = ws[8 + i];
+    if (i < wv) rank += x;
+    emitted += x; firstL = y < firstL ? y : firstL;
+  }
+  emitted = wave_uniform(emitted);
   uint32_t *hbuf = (uint32_t *)keys;                // dead once the tile is winnowed (kFragHashCap * 4 <= kTile * 8)
-  int cnt = 0;
-#pragma unroll
-  for (int j = 0; j < kPer; j++) { inR[j] = inR[j] && (em[j] || local0 + j == firstL); cnt += inR[j]; }
-  int total; int rank = block_excl_scan(cnt, ws, &total);
 #pragma unroll
   for (int j = 0; j < kPer; j++)
-    if (inR[j]) { if (rank < kFragHashCap) hbuf[rank] = (uint32_t)(W[j] >> 32); rank++; }
-  const bool overflow = total > kFragHashCap;
+    if (inR[j] && em[j]) hbuf[rank++] = (uint32_t)(W[j] >> 32);
+  if (myFirst == firstL && firstL != 0x7fffffff) {  // the one thread that owns the fragment's first window
+#pragma unroll
+    for (int j = 0; j < kPer; j++)
+      if (local0 + j == firstL && !em[j]) { hbuf[emitted] = (uint32_t)(W[j] >> 32); ws[16] = 1; }
+  }
   block_barrier();
-  fragment_finish(hbuf, overflow ? kFragHashCap : total, overflow, fi.frag, qPool, qCap, qCount, fragOff, fragS, maxS, ws, sBasePtr);
+  static_assert(kTile <= kFragHashCap, "one tile's positions cannot overflow the staging buffer");
+  const int total = emitted + wave_uniform(ws[16]);
+  fragment_finish(hbuf, total, false, fi.frag, qPool, qCap, qCount, fragOff, fragS, maxS, ws, sBasePtr);
 }
 
 static __global__ __launch_bounds__(kTPB, 3) void k_sketch_fused(const uint32_t *__restrict__ packed, const uint8_t *__restrict__ ascii,
