@@ -1203,6 +1203,50 @@ int ani_l1_check(ani_ctx *ctx, const ani_sketch *skc, int32_t chunk, const ani_f
   return ANI_OK;
 }
 
+// TEST INFRASTRUCTURE (declared in host/engine.hpp, not part of include/ani_abi.h, no product code calls it): map_stage's two calls —
+// l1_stage and, if it left candidates, l2_stage — run once for the kept fragment set `f` against index chunk `chunk`, prepared and
+// checked as ani_l1_check prepares and checks.  info = {nFrag, nCand, and this call's increase of l2FastCandidates, l2SlowCandidates,
+// l2SlowLimit, l2SlowDup, l2SlowOverflow, l2Steps, l2WindowEntries, l2QueryHashes, l2WindowEntriesB, l2Launches, l2ChunkHalvings};
+// *out = one malloc'ed block of 9 nCand 32-bit words (ani_free releases it):
+//   ocFrag, ocSeq, ocStart, ocEnd, l2Best, l2First, l2Last, refStart, idBits [nCand each].
+// tests/test_l2.py holds them to the from-scratch definition of computeL2MappedRegions (tests/l2_cases.py).
+int ani_l2_check(ani_ctx *ctx, const ani_sketch *skc, int32_t chunk, const ani_fragset *f, uint64_t *info, int32_t **out, size_t *words)
+{
+  if (!ctx || !skc || !f || !info || !out || !words || skc->ctx != ctx) return fail(ANI_ERR_ARG, "ani_l2_check: bad argument");
+  if (f->device != ctx->device) return fail(ANI_ERR_ARG, "ani_l2_check: fragment set lives on device %d, context on %d", f->device, ctx->device);
+  ani_sketch *sk = const_cast<ani_sketch *>(skc);
+  if (chunk < 0 || (size_t)chunk >= sk->chunks.size()) return fail(ANI_ERR_ARG, "ani_l2_check: chunk %d of %zu", chunk, sk->chunks.size());
+  if (f->params.kmerSize != sk->params.kmerSize || f->params.windowSize != sk->params.windowSize || f->params.fragLen != sk->params.fragLen)
+    return fail(ANI_ERR_ARG, "ani_l2_check: fragment set and sketch were built with different parameters");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FragSet &fs = f->fs;
+  TRY(upload_luts(sk, fs.maxS));
+  if (ensure_chunk(sk, (size_t)chunk) != ANI_OK || !sk->chunks[chunk]->resident)
+    return fail(ANI_ERR_ARG, "ani_l2_check: the index arrays of chunk %d cannot be made resident", chunk);
+  const ani_counters_t &c = ctx->counters;
+  const uint64_t before[11] = {c.l2FastCandidates, c.l2SlowCandidates, c.l2SlowLimit, c.l2SlowDup, c.l2SlowOverflow, c.l2Steps, c.l2WindowEntries,
+                               c.l2QueryHashes, c.l2WindowEntriesB, c.l2Launches, c.l2ChunkHalvings};
+  const int32_t *fragOrder = nullptr; int32_t nCand = 0;
+  TRY(l1_stage(ctx, sk, sk->chunks[chunk], fs, &fragOrder, &nCand));
+  if (nCand) TRY(l2_stage(ctx, sk, sk->chunks[chunk], fs, fragOrder, (uint64_t)nCand));
+  const size_t nC = (size_t)nCand, total = 9 * nC;
+  int32_t *host = (int32_t *)malloc((total ? total : 1) * 4);
+  if (!host) return fail(ANI_ERR_NOMEM, "host allocation failed");
+  hipError_t e = hipSuccess;
+  const void *src[9] = {ctx->ocFrag.p, ctx->ocSeq.p, ctx->ocStart.p, ctx->ocEnd.p, ctx->l2Best.p, ctx->l2First.p, ctx->l2Last.p, ctx->refStart.p,
+                        ctx->idBits.p};
+  for (int i = 0; i < 9; i++)
+    if (nC && e == hipSuccess) e = hipMemcpyAsync(host + i * nC, src[i], nC * 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { free(host); HIP_TRY(e); }
+  const uint64_t after[11] = {c.l2FastCandidates, c.l2SlowCandidates, c.l2SlowLimit, c.l2SlowDup, c.l2SlowOverflow, c.l2Steps, c.l2WindowEntries,
+                              c.l2QueryHashes, c.l2WindowEntriesB, c.l2Launches, c.l2ChunkHalvings};
+  info[0] = (uint64_t)fs.nFrag; info[1] = nC;
+  for (int i = 0; i < 11; i++) info[2 + i] = after[i] - before[i];
+  *out = host; *words = total;
+  return ANI_OK;
+}
+
 int ani_map_cgi_batch(ani_ctx *ctx, const ani_sketch *skc, const ani_seq_batch_t *queries, int32_t firstQueryId, ani_cgi_t **out, size_t *m)
 {
   if (!ctx || !skc || !out || !m) return fail(ANI_ERR_ARG, "null argument");

@@ -94,6 +94,16 @@ extern "C" int ani_index_links_check(ani_ctx *ctx, const ani_sketch *sk, int32_t
 // ANI_ERR_ARG.  tests/test_l1.py holds the arrays to the sequential definition of computeMap.hpp:283-354.
 struct ani_fragset;
 extern "C" int ani_l1_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const ani_fragset *f, uint64_t *info, int32_t **out, size_t *words);
+// TEST INFRASTRUCTURE (engine_map.hip, beside ani_l1_check; not part of include/ani_abi.h, no product code calls it): both halves of
+// map_stage — l1_stage and, if it left candidates, l2_stage: k_l2_ranges, the length ordering, k_l2_codes, the two simulation classes,
+// the collection of the leftovers, the general kernel k_l2 and k_finish_candidates — run once for the kept fragment set `f` against
+// index chunk `chunk` of `sk`, with the argument checks and the preparation of ani_l1_check.
+//   info[13] = {nFrag, nCand, then this call's increase of the counters l2FastCandidates, l2SlowCandidates, l2SlowLimit, l2SlowDup,
+//               l2SlowOverflow, l2Steps, l2WindowEntries, l2QueryHashes, l2WindowEntriesB, l2Launches, l2ChunkHalvings}
+//   *out     = malloc'ed 32-bit words (ani_free), *words = 9 nCand of them: ocFrag, ocSeq, ocStart, ocEnd, l2Best, l2First, l2Last,
+//              refStart, idBits [nCand each]
+// tests/test_l2.py holds the arrays and the counters to the from-scratch definition of computeL2MappedRegions (tests/l2_cases.py).
+extern "C" int ani_l2_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, const ani_fragset *f, uint64_t *info, int32_t **out, size_t *words);
 
 namespace ani { struct TableSlot; }
 

@@ -184,7 +184,8 @@ __host__ __device__ inline L2Result l2_candidate(const uint32_t *q, int s,
 //   k_l2_sim     one lane per candidate: loads the first super-window's state, then applies the events in order, one per loop pass,
 //                8 events per 16-byte load, no position arithmetic and no second cursor.  State in LDS: one byte per sketch rank (7-bit gap counter + presence bit),
 //                byte-interleaved over the wave.  Entries flagged nearDup consult the same-hash links (exact set semantics,
-//                slidingMap.hpp:150-154,:178).  A gap counter that would pass 127 sends the candidate to k_l2.
+//                slidingMap.hpp:150-154,:178).  A gap counter that would pass 127 sends the candidate to k_l2 (gap s does not count a
+//                reference hash 0xffffffff that is not in the sketch: see l2_rank_fast).
 // ------------------------------------------------------------------------------------------------
 struct L2Args {
   // candidates (SoA)
@@ -315,6 +316,8 @@ static __global__ __launch_bounds__(kTPB) void k_l2_ranges(L2FastArgs a)
   if (fast && nEv == 0) {                            // the window never fits: the loop of :455 does not run, nothing is evaluated
     a.g.outBest[c] = 0; a.g.outFirst[c] = 0; a.g.outLast[c] = 0;
     a.codeCount[i] = 0; a.slowFlag[i] = 16;          // done
+    // no other kernel sees this candidate: its share of Σ m_c and Σ s (l2WindowEntries, l2QueryHashes) is counted here, as k_l2 counts it
+    atomicAdd(stat_slot(a.g.sumEntries), (unsigned long long)m); atomicAdd(stat_slot(a.g.sumQ), (unsigned long long)s);
     return;
   }
   const bool classA = s <= L2GeomA::kMaxS && a.allowFast != 2;
@@ -367,6 +370,15 @@ __device__ __forceinline__ void l2_rank_table(const uint32_t *__restrict__ q, in
 // bucket's start decide it unless the bucket holds more than two and both are below h (`deep`: the caller's wave vote sends those to
 // l2_rank_deep); entries behind the bucket's own belong to later buckets, i.e. are larger than any hash of this bucket, so they need
 // no "is it in the bucket" test (the sketch is followed by two 0xffffffff sentinels).
+// One hash meets a sentinel: a reference hash 0xffffffff that is NOT a sketch hash comes back as "sketch hash at index s".  Its events
+// then change field s by 1, not by 2: they set and clear the presence bit that field has to spare (b[s+1] does not exist) and leave the
+// counter of gap s alone.  No result depends on it: an event of index s is never below the pivot (iStar <= s), and the bit of field s
+// would be read only by a pivot that moves beyond rank s, which l2_apply rules out (delete at iStar = s: tot + 1 + n[s] > s).  What it
+// changes is the hand-over: THE FAST PATH'S COUNTER OF GAP s DOES NOT COUNT A REFERENCE-ONLY 0xffffffff, so 128 distinct hashes above
+// the sketch, one of them 0xffffffff, stay on the fast path (field s = 127 << 1 | 1) and 129 go to k_l2.  Ranking it as a non-query
+// hash (rk -= rk == (s << 1 | 1), two vector instructions per entry) was measured: k_l2_codes 54.45 -> 55.22 ms, L2 stage 68.65 ->
+// 69.48 ms per benchmark step, every run of it above every run without (profiles/r14_l2_rank_ff_ab.txt) - for a value that the minimum
+// of w k-mer hashes does not take.  tests/test_l2.py (gap_counter_top) holds the rule as stated here.
 __device__ __forceinline__ uint32_t l2_rank_fast(const uint32_t *qs, const uint32_t *st2, int sh, uint32_t h, uint32_t &deep)
 {
   const uint32_t sp = st2[l2_rank_bucket(h, sh)];                   // first sketch entry of the bucket | entries in it << 16
