@@ -10,7 +10,7 @@ using namespace ani;
 // the index arrays of a chunk (not its reducer tables): dropped when the chunk is evicted in streaming mode
 void free_chunk_index(IndexChunk *ch)
 {
-  void **ptrs[] = {(void **)&ch->mWin, (void **)&ch->sSW, (void **)&ch->dupBits, (void **)&ch->dupList, (void **)&ch->mHash, (void **)&ch->mSeq,
+  void **ptrs[] = {(void **)&ch->mWin, (void **)&ch->sPos, (void **)&ch->dupBits, (void **)&ch->dupList, (void **)&ch->mHash, (void **)&ch->mSeq,
       (void **)&ch->mWpos,
                    (void **)&ch->sHash, (void **)&ch->table, (void **)&ch->contigFirstMin, (void **)&ch->posSample};
   for (void **q : ptrs) if (*q) { pool_free(*q); *q = nullptr; }
@@ -122,7 +122,7 @@ int build_chunk_index(ani_ctx *ctx, const ani_params_t *p, IndexChunk *sk)
   const size_t n4 = (n ? n : 1) * 4;
   const size_t bitWords = (n + 31) / 32 + 1;
   SK_HIP(pool_malloc((void **)&sk->mHash, n4)); SK_HIP(pool_malloc((void **)&sk->mSeq, n4)); SK_HIP(pool_malloc((void **)&sk->mWpos, n4));
-  SK_HIP(pool_malloc((void **)&sk->sHash, n4)); SK_HIP(pool_malloc((void **)&sk->sSW, 2 * n4));
+  SK_HIP(pool_malloc((void **)&sk->sHash, n4)); SK_HIP(pool_malloc((void **)&sk->sPos, n4));
   SK_HIP(pool_malloc((void **)&sk->mWin, n4)); SK_HIP(pool_malloc((void **)&sk->dupBits, bitWords * 4));
   SK_HIP(pool_malloc((void **)&sk->contigFirstMin, ((size_t)nContigs + 1) * 4));
   SK_HIP(pool_malloc((void **)&sk->posSample, ((size_t)sk->totalPosBins + 1) * 4));
@@ -131,9 +131,9 @@ int build_chunk_index(ani_ctx *ctx, const ani_params_t *p, IndexChunk *sk)
     const int32_t cmw = p->fragLen - (p->windowSize - 1) - (p->kmerSize - 1);
     // otherwise the L2 fast path is off (map_stage) and the window links are never read
     const bool winLinks = n && cmw >= 1 && cmw + 2 <= (int32_t)kWinMask;
-    uint32_t *tmpK = nullptr; uint64_t *tmpV = nullptr;
+    uint32_t *tmpK = nullptr, *tmpV = nullptr;
     SK_HIP(pool_malloc((void **)&tmpK, n4));
-    { const hipError_t ev = pool_malloc((void **)&tmpV, 2 * n4); if (ev != hipSuccess) { pool_free(tmpK); SK_HIP(ev); } }
+    { const hipError_t ev = pool_malloc((void **)&tmpV, n4); if (ev != hipSuccess) { pool_free(tmpK); SK_HIP(ev); } }
     SK_HIP(hipMemsetAsync(sk->dupBits, 0, bitWords * 4, ctx->stream));
     // Main stream: the index sort (radix.hpp: its histogram read of the records writes the position-ordered SoA arrays), then the
     // same-hash links and the probe table.  Side stream: what needs positions only — the window links of the L2 event stream (binary
@@ -145,11 +145,11 @@ int build_chunk_index(ani_ctx *ctx, const ani_params_t *p, IndexChunk *sk)
       std::vector<const void *> recs; std::vector<size_t> cnts;
       for (const RecordPiece &pc : sk->pieces) if (pc.n) { recs.push_back(pc.rec); cnts.push_back(pc.n); }
       size_t tb = 0;
-      int rc = ani_sort_index(recs.data(), cnts.data(), (int)recs.size(), (uint32_t)c0, n, sk->mHash, sk->mSeq, sk->mWpos, tmpK, tmpV, sk->sHash, sk->sSW,
+      int rc = ani_sort_index_pos(recs.data(), cnts.data(), (int)recs.size(), (uint32_t)c0, n, sk->mHash, sk->mSeq, sk->mWpos, tmpK, tmpV, sk->sHash, sk->sPos,
           nullptr, &tb, ctx->stream, nullptr, nullptr);
       if (rc == 0) { rc = ctx->sortTmp.ensure(tb + 256);
-        if (rc == ANI_OK) rc = ani_sort_index(recs.data(), cnts.data(), (int)recs.size(), (uint32_t)c0, n, sk->mHash, sk->mSeq, sk->mWpos, tmpK, tmpV,
-          sk->sHash, sk->sSW, ctx->sortTmp.p, &tb, ctx->stream, nullptr, nullptr); }
+        if (rc == ANI_OK) rc = ani_sort_index_pos(recs.data(), cnts.data(), (int)recs.size(), (uint32_t)c0, n, sk->mHash, sk->mSeq, sk->mWpos, tmpK, tmpV,
+          sk->sHash, sk->sPos, ctx->sortTmp.p, &tb, ctx->stream, nullptr, nullptr); }
       if (rc != 0) { pool_free(tmpK); pool_free(tmpV);
         return bail(rc < 0 && rc >= ANI_ERR_INTERNAL ? rc : fail(rc > 9000 ? ANI_ERR_INTERNAL : ANI_ERR_DEVICE, "radix sort of the index failed (%d)", rc)); }
     }
@@ -187,8 +187,8 @@ int build_chunk_index(ani_ctx *ctx, const ani_params_t *p, IndexChunk *sk)
         uint64_t *pairs = nullptr;
         SK_HIP(pool_malloc((void **)&pairs, (size_t)pairCap * 16));
         { const int rz = zero_counters(ctx); if (rz != ANI_OK) { pool_free(pairs); return bail(rz); } }
-        hipLaunchKernelGGL(k_index_links, dim3(grid_for(n, 256, 8192)), dim3(256), 0, ctx->stream, sk->sHash, (const uint64_t *)sk->sSW, (uint32_t)n,
-            sk->mWpos, sk->contigFirstMin,
+        hipLaunchKernelGGL(k_index_links, dim3(grid_for(n, 256, 8192)), dim3(256), 0, ctx->stream, sk->sHash, (const uint32_t *)sk->sPos, (uint32_t)n,
+            (const int32_t *)sk->mSeq, (const int32_t *)sk->mWpos,
                            cmw, pairs, pairCap, (unsigned int *)cnt_ptr(ctx,
                                CNT_NEG), sk->dupBits, (uint32_t *)nullptr /* k_index_mark_dups sets the window links' flags */, cnt_ptr(ctx, CNT_UNIQ));
         if (attempt == 0) {
@@ -359,8 +359,8 @@ int add_chunks(ani_ctx *ctx, ani_sketch *sk, std::vector<RecordPart> &parts)
   for (int32_t g = 0; g < sk->nGenomes; g++) if (genomePart[g] < 0) return fail(ANI_ERR_INTERNAL, "genome %d is in no record part", g);
   sk->genomeRecStart.assign((size_t)sk->nGenomes + 1, 0);
   for (int32_t g = 0; g < sk->nGenomes; g++) sk->genomeRecStart[g + 1] = sk->genomeRecStart[g] + genomeRecs[g];
-  // Resident or streamed?  The index takes ~36 bytes per minimizer and its build another ~13 of transient
-  // arrays; a set that does not fit beside a working-set reserve keeps its 12-byte records instead and at most `maxResident`
+  // Resident or streamed?  The index takes ~32 bytes per minimizer and its build another ~9 of transient
+  // arrays (both 4 less since the hash-ordered payload is a 32-bit rank); a set that does not fit beside a working-set reserve keeps its 12-byte records instead and at most `maxResident`
   // chunks' arrays (ANI_MAX_RESIDENT_CHUNKS forces a limit: the tests stream tiny sets that way).
   uint64_t maxN = std::min<uint64_t>(ctx->maxIndexMinimizers, 0x7fffffe0ull);
   int32_t resident = ctx->maxResidentChunks;
@@ -374,7 +374,7 @@ int add_chunks(ani_ctx *ctx, ani_sketch *sk, std::vector<RecordPart> &parts)
       // (Streamed chunks of a fixed 10^9 minimizers.  Measured: chunks as large as the free memory allows — 4 instead of 5 for
       // 10 000 x 5 Mbp — save a probe pass, but more fragments then have > 2048 seed hits per chunk and move to LDS class M:
       // the 10 000 x 10 000 step stayed at 6.1 s.)
-      if (36 * total + 14 * largest + reserve > avail) { resident = 1; maxN = std::min<uint64_t>(maxN, ctx->streamChunkMinimizers); }
+      if (32 * total + 10 * largest + reserve > avail) { resident = 1; maxN = std::min<uint64_t>(maxN, ctx->streamChunkMinimizers); }
     }
   }
   // balanced chunk sizes: ceil(total / max) chunks of about total / that
@@ -498,8 +498,8 @@ extern "C" {
 // (4.03 x 10^8 minimizers; profiles/r06a_e2e_pool_trace.txt, r06s_e2e_slow_box.txt): the slices' records and fragment sets take 16 bytes
 // per minimizer and the contexts' workspaces 2 GB, asked for in pieces of < 300 MB while the input is read — reserved as 1 GiB segments,
 // first, 22 bytes per minimizer in all, so that the first slice waits for one of them only (with 17 the eighth GiB was missing and the
-// compute threads waited 0.67 s for the index segment behind it on a 30 us/MB box); the index build takes 41 bytes per minimizer at its peak
-// (28 n of arrays that stay, then 12 n of sort buffers or — in the same place, the sort buffers are free by then — link candidates and the
+// compute threads waited 0.67 s for the index segment behind it on a 30 us/MB box); the index build takes 37 bytes per minimizer at its peak
+// (24 n of arrays that stay, then 8 n of sort buffers or — in the same place, the sort buffers are free by then — link candidates and the
 // probe table) within a few milliseconds — reserved as ONE segment, from which the build's requests are cut one after the other and
 // into which its transient arrays go back for the mapping buffers.
 int ani_pool_prewarm_index(ani_ctx *ctx, uint64_t nMinimizers)
@@ -510,7 +510,7 @@ int ani_pool_prewarm_index(ani_ctx *ctx, uint64_t nMinimizers)
   HIP_TRY(hipSetDevice(ctx->device));
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-  const size_t sketchBytes = (size_t)nMinimizers * 22, indexBytes = (size_t)nMinimizers * 43;
+  const size_t sketchBytes = (size_t)nMinimizers * 22, indexBytes = (size_t)nMinimizers * 39;
   if (sketchBytes + indexBytes > freeB / 2) return ANI_OK;                  // not on a device that is short of memory
   DevicePool &pool = cur_pool();
   std::vector<size_t> sizes;
@@ -578,7 +578,8 @@ int ani_index_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, int what,
   switch (what) {
     case 0: src = info; sz = sizeof info; break;
     case 1: src = ch->sHash; sz = n * 4; break;
-    case 2: src = ch->sSW; sz = n * 8; break;
+    case 2: sz = n * 8; break;                                 // expanded from sPos below
+    case 11: src = ch->sPos; sz = n * 4; break;
     case 3: src = ch->mWin; sz = n * 4; break;
     case 4: src = ch->dupBits; sz = bitWords * 4; break;
     case 5: src = ch->dupList; sz = (size_t)ch->nDup * 8; break;
@@ -591,6 +592,19 @@ int ani_index_check(ani_ctx *ctx, const ani_sketch *sk, int32_t chunk, int what,
   *bytes = sz;
   if (!out || !sz) return ANI_OK;
   if (capBytes < sz) return fail(ANI_ERR_ARG, "ani_index_check: array %d takes %zu bytes, the buffer has %llu", what, sz, (unsigned long long)capBytes);
+  if (what == 2) {                                             // seqId << 32 | wpos in hash order: (mSeq << 32 | mWpos)[sPos], into a temporary
+    uint64_t *sw = nullptr;
+    HIP_TRY(hipStreamSynchronize(ctx->stream2));
+    HIP_TRY(pool_malloc((void **)&sw, sz));
+    hipLaunchKernelGGL(k_index_expand_pos, dim3(grid_for(n, 256, 65535)), dim3(256), 0, ctx->stream, (const uint32_t *)ch->sPos, (uint32_t)n,
+        (const int32_t *)ch->mSeq, (const int32_t *)ch->mWpos, sw);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, sw, sz, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    pool_free(sw);
+    HIP_TRY(e); HIP_TRY(e2);
+    return ANI_OK;
+  }
   if (!src) return fail(ANI_ERR_INTERNAL, "ani_index_check: array %d of a resident chunk is missing", what);
   if (what == 0) { memcpy(out, src, sz); return ANI_OK; }
   HIP_TRY(hipStreamSynchronize(ctx->stream2)); HIP_TRY(hipStreamSynchronize(ctx->stream));

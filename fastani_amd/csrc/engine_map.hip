@@ -90,7 +90,7 @@ static int l1_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet
     else TRY(zero_cursors(ctx, POOL_CAND));
     L1Args a;
     a.qPool = fs.qPool; a.fragOff = fs.fragOff; a.fragS = fs.fragS; a.nFrag = (int32_t)nF;
-    a.table = sk->table; a.tableSlots = sk->tableSlots; a.sSW = sk->sSW; a.bucketW = w; a.nIndex = sk->n;
+    a.table = sk->table; a.tableSlots = sk->tableSlots; a.sPos = sk->sPos; a.mSeq = sk->mSeq; a.mWpos = sk->mWpos; a.bucketW = w; a.nIndex = sk->n;
     a.minHitsLUT = set->dMinHits; a.lutMaxS = set->dLutMaxS; a.L = L;
     a.candFrag = ctx->candFrag.as<int32_t>(); a.candSeq = ctx->candSeq.as<int32_t>(); a.candStart = ctx->candStart.as<int32_t>();
     a.candEnd = ctx->candEnd.as<int32_t>();
@@ -146,12 +146,11 @@ static int l1_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet
       if (nMid) hipLaunchKernelGGL((k_l1<kL1HitCapSmall, kL1HitCapMid>), dim3(nMid), dim3(kTPB), 0, ctx->stream, a, (const int32_t *)a.midList);
       if (nBig) {
         // Fragments beyond every LDS class, batched (l1.hpp): groups of fragments whose hits fit the key buffers; one 64-bit key per
-        // hit = (fragment rank in the group, seqId, wpos), field widths from this chunk's contig count and longest contig.
+        // hit = (fragment rank in the group, position rank of the hit), the second field as wide as this chunk's entry count needs —
+        // never wider than the (seqId, wpos) fields it replaced: n <= nContigs x longest contig.
         StageTimer tb(ctx, &ctx->counters.msL1Big, 1);
-        int bitsPos = 1, bitsSeq = 1;
-        while (bitsPos < 31 && (1ll << bitsPos) <= (long long)sk->maxContigLen) bitsPos++;
-        while (bitsSeq < 31 && (1ll << bitsSeq) <= (long long)sk->nContigs) bitsSeq++;
-        const int shiftSeq = bitsPos, shiftRank = bitsPos + bitsSeq;
+        int shiftRank = 1;
+        while (shiftRank < 31 && (1ll << shiftRank) < (long long)sk->n) shiftRank++;
         const uint64_t maxFrags = std::min<uint64_t>(1ull << std::min(20, 64 - shiftRank), ctx->l1BigGroupFrags);
         const uint64_t budget = ctx->l1BigGroupHits;
         for (size_t b0 = 0; b0 < nBig;) {
@@ -181,7 +180,7 @@ static int l1_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet
           const uint32_t *d32 = ctx->l1BigTbl.as<uint32_t>();
           g.frag = (const int32_t *)d32; g.sOff = d32 + n; g.tileFirst = d32 + n + (n + 1);
           g.hitOff = (const uint64_t *)(ctx->l1BigTbl.as<uint8_t>() + ((w32 * 4 + 7) / 8) * 8);
-          g.hashOff = ctx->l1BigHash.as<int32_t>(); g.keys = ctx->l1BigHitsA.as<uint64_t>(); g.n = (int)n; g.shiftSeq = shiftSeq; g.shiftRank = shiftRank;
+          g.hashOff = ctx->l1BigHash.as<int32_t>(); g.keys = ctx->l1BigHitsA.as<uint64_t>(); g.n = (int)n; g.shiftRank = shiftRank;
           hipLaunchKernelGGL(k_l1_big_offsets, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, a, g);
           if (tiles) {
             hipLaunchKernelGGL(k_l1_big_gather, dim3((unsigned)tiles), dim3(kTPB), 0, ctx->stream, a, g);
@@ -194,7 +193,7 @@ static int l1_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet
                 &tbytes, ctx->stream); }
             if (rc != 0) return fail(ANI_ERR_DEVICE, "radix sort of seed hits failed (%d)", rc);
             hipLaunchKernelGGL(k_l1_big_unpack, dim3(grid_for((size_t)hits, 256, 65535)), dim3(256), 0, ctx->stream, ctx->l1BigHitsB.as<uint64_t>(),
-                (uint64_t)hits, shiftSeq, shiftRank);
+                (uint64_t)hits, shiftRank, (const int32_t *)sk->mSeq, (const int32_t *)sk->mWpos);
           }
           g.keys = ctx->l1BigHitsB.as<uint64_t>();
           hipLaunchKernelGGL(k_l1_big_candidates, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, a, g, ctx->l1BigV.as<int>() + 2 * (size_t)nBig);

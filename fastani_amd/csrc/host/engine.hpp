@@ -52,6 +52,10 @@ extern "C" int ani_sort_pairs_u64_u32(const uint64_t *keysIn, uint64_t *keysOut,
 extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
                               uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint64_t *tmpV, uint32_t *sHash, uint64_t *sSW,
                               void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream);
+// the same sort with the entry's position rank (its index into mSeq / mWpos) as the payload: what the index build runs
+extern "C" int ani_sort_index_pos(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
+                                  uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint32_t *tmpV, uint32_t *sHash, uint32_t *sPos,
+                                  void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream);
 extern "C" int ani_sort_check(void *tmp, hipStream_t stream);
 
 // TEST INFRASTRUCTURE (prim_check.hip; not part of include/ani_abi.h, no product code calls them): the workgroup primitives of
@@ -73,8 +77,10 @@ extern "C" int ani_reduce_check(ani_ctx *ctx, const ani_sketch *sk, const ani_ma
 // index chunk as build_chunk_index left it.  ani_index_check copies array `what` of chunk `chunk` to the host buffer `out` of
 // capBytes bytes (out = NULL: the size only) and returns its size in *bytes:
 //   0 info: uint64 {n, nUnique, nDup, tableSlots, allocated table slots, totalPosBins, nContigs, c0, nGenomes, g0, window links built, words of dupBits}
-//   1 sHash  2 sSW  3 mWin  4 dupBits  5 dupList  6 contigFirstMin (nContigs + 1)  7 posBase (nContigs + 1)  8 posSample (totalPosBins + 1)
+//   1 sHash  2 seqId << 32 | wpos of every entry in hash order (64-bit; the chunk holds ranks: expanded from sPos for the call)
+//   3 mWin  4 dupBits  5 dupList  6 contigFirstMin (nContigs + 1)  7 posBase (nContigs + 1)  8 posSample (totalPosBins + 1)
 //   9 the probe table: every allocated slot (12 bytes each), the sentinel and the slot behind it included
+//   11 sPos: the position rank of every entry in hash order (32-bit), as the chunk holds it  (10 is no array: the argument tests use it)
 // ani_index_probe_check runs table_probe — one thread per hash, with the table, window size and tableSlots that l1_probe gets — over
 // n host hashes: firstCnt[2 i] = first, firstCnt[2 i + 1] = cnt.  ani_index_links_check runs dup_flag / dup_prev / dup_next over the
 // chunk's DupLinks for n host entry numbers (each below the chunk's n): out[3 i .. 3 i + 2] = flag, prev, next.  A chunk whose index
@@ -565,7 +571,7 @@ struct IndexChunk {
   uint32_t *mHash = nullptr; int32_t *mSeq = nullptr, *mWpos = nullptr;
   uint32_t *sHash = nullptr, *mWin = nullptr;
   uint32_t *dupBits = nullptr; uint64_t *dupList = nullptr; uint32_t nDup = 0;   // same-hash links of near duplicates (index.hpp: DupLinks)
-  uint64_t *sSW = nullptr;
+  uint32_t *sPos = nullptr;               // hash order: the entry's position rank (index into mSeq / mWpos), carried through the index sort
   ani::TableSlot *table = nullptr; uint32_t tableSlots = 0;     // order-preserving probe table over the distinct hashes (index.hpp)
   uint32_t tableAlloc = 0;                 // slots allocated: the end clusters may run past tableSlots, then the sentinel and one empty slot
   int32_t *contigFirstMin = nullptr, *contigGenome = nullptr;

@@ -3,8 +3,9 @@
 // Replaces skch::Sketch::index (src/map/include/winSketch.hpp:181-193: unordered_map<hash, vector<{seqId,wpos}>>)
 // and skch::Sketch::searchIndex (:259-270) by flat device arrays:
 //   position order (≙ minimizerIndex :93)      mHash[n], mSeq[n], mWpos[n], mWin[n] (window links of the L2 event stream) + contigFirstMin[nContigs+1]
-//   hash order    (≙ minimizerPosLookupIndex)  sHash[n] (sorted), sSW[n] = seqId<<32|wpos carried through the stable sort, so
-//                                              every hash's occurrence list is one contiguous run in (seqId,wpos) order (:186-190)
+//   hash order    (≙ minimizerPosLookupIndex)  sHash[n] (sorted), sPos[n] = the entry's position rank (its index into mSeq / mWpos) carried
+//                                              through the stable sort, so every hash's occurrence list is one contiguous run in
+//                                              (seqId,wpos) order (:186-190): the position-ordered arrays are sorted by (seqId, wpos)
 //   probe table   table[2 x distinct]          order-preserving open-addressing table {hash, first, count} over the distinct hashes (below)
 //   same-hash links (for the L2 set semantics) DupLinks: for the few entries that have one, the neighbouring NEAR occurrence of the same hash in
 //                                              position order (one that can share a super-window) — a sorted list + one bit per entry
@@ -57,7 +58,7 @@ static __global__ void k_index_join(const uint32_t *__restrict__ mHash, const in
   }
 }
 
-// After the stable sort by hash (sHash[r], sSW[r] = seqId<<32|wpos; equal hashes stay in position order): unique-hash count
+// After the stable sort by hash (sHash[r], sPos[r] = the entry's position rank; equal hashes stay in position order): unique-hash count
 // and, for NEAR duplicates only, the same-hash links: two half-records per pair appended to `pairs` (unordered; the host sorts them),
 // the "has a link" bit of both entries, and the nearDup flag in their window links (bit 31 of mWin, if the chunk has window links).
 //   nearDup: two same-hash entries j' < j of one contig can share a super-window.  All entries of a window except its first
@@ -66,24 +67,19 @@ static __global__ void k_index_join(const uint32_t *__restrict__ mHash, const in
 // Entries without a link behave as plain set members in L2 (links of non-near pairs would only ever be compared against the bounds of
 // one window).  `nPairs` counts every pair; a pair beyond `pairCap` is not stored (the host reruns the kernel with room for all).
 // one same-hash pair (r - 1, r) of the sorted index: the link records if the two are near duplicates
-__device__ __forceinline__ void index_link_pair(uint32_t r, const uint64_t *__restrict__ sSW, const int32_t *__restrict__ mWpos,
-    const int32_t *__restrict__ contigFirstMin,
+__device__ __forceinline__ void index_link_pair(uint32_t r, const uint32_t *__restrict__ sPos, const int32_t *__restrict__ mSeq,
+    const int32_t *__restrict__ mWpos,
                                                 int32_t cmw, uint64_t *__restrict__ pairs, uint32_t pairCap, unsigned int *__restrict__ nPairs,
                                                 uint32_t *__restrict__ dupBits, uint32_t *__restrict__ mWin)
 {
-  const uint64_t a = sSW[r - 1], b = sSW[r];                   // a is positionally before b
-  if ((a >> 32) != (b >> 32)) return;                          // different contigs never share a window
-  const int32_t seq = (int32_t)(a >> 32), wa = (int32_t)(uint32_t)a, wb = (int32_t)(uint32_t)b;
-  // positional indices: binary search on wpos inside the contig's slice
-  int32_t lo = contigFirstMin[seq], hi = contigFirstMin[seq + 1];
-  const int32_t cHi = hi;
-  while (lo < hi) { int32_t mid = lo + ((hi - lo) >> 1); if (mWpos[mid] < wa) lo = mid + 1; else hi = mid; }
-  const int32_t ia = lo;
-  const int32_t gap = (ia + 1 < cHi) ? mWpos[ia + 1] - wa : 0;
-  if (wb - wa > cmw + gap) return;
-  hi = cHi;
-  while (lo < hi) { int32_t mid = lo + ((hi - lo) >> 1); if (mWpos[mid] < wb) lo = mid + 1; else hi = mid; }
-  const int32_t ib = lo;
+  // the ranks ARE the positional indices (until round 15: two bisections over the contig's wpos per pair); a is positionally before b
+  const int32_t ia = (int32_t)sPos[r - 1], ib = (int32_t)sPos[r];
+  // The test, for two entries of one contig (where ia + 1 <= ib is an entry of it): wb - wa <= cmw + (wpos[ia + 1] - wa), i.e.
+  // wb - wpos[ia + 1] <= cmw.  wpos is strictly increasing inside a contig, so wb - wpos[ia + 1] >= ib - (ia + 1): a pair more than
+  // cmw + 1 ranks apart is rejected on the ranks alone, without a load (nearly every pair of a repeated hash).
+  if (ib - ia - 1 > cmw) return;
+  if (mSeq[ia] != mSeq[ib]) return;                            // different contigs never share a window
+  if (mWpos[ib] - mWpos[ia + 1] > cmw) return;
   const unsigned int slot = atomicAdd(nPairs, 1u);
   if (slot < pairCap) {
     pairs[2 * (size_t)slot] = ((uint64_t)(uint32_t)ia << 32) | (1ull << 31) | (uint32_t)ib;         // ia: its next near occurrence is ib
@@ -95,8 +91,8 @@ __device__ __forceinline__ void index_link_pair(uint32_t r, const uint64_t *__re
 
 // (round 5: four consecutive entries per thread from one 16-byte load — one entry per thread and iteration was a chain of ~190
 //  dependent 4-byte loads per thread, 2.0 ms for the 1.6 GB of hashes.)
-static __global__ void k_index_links(const uint32_t *__restrict__ sHash, const uint64_t *__restrict__ sSW, uint32_t n,
-                              const int32_t *__restrict__ mWpos, const int32_t *__restrict__ contigFirstMin, int32_t cmw,
+static __global__ void k_index_links(const uint32_t *__restrict__ sHash, const uint32_t *__restrict__ sPos, uint32_t n,
+                              const int32_t *__restrict__ mSeq, const int32_t *__restrict__ mWpos, int32_t cmw,
                               uint64_t *__restrict__ pairs, uint32_t pairCap, unsigned int *__restrict__ nPairs,
                               uint32_t *__restrict__ dupBits, uint32_t *__restrict__ mWin, unsigned long long *__restrict__ nUnique)
 {
@@ -118,7 +114,7 @@ static __global__ void k_index_links(const uint32_t *__restrict__ sHash, const u
       if (r >= n) break;
       const bool samePrev = r > 0 && h[k] == h[k + 1];
       uniq += !samePrev;
-      if (samePrev) index_link_pair(r, sSW, mWpos, contigFirstMin, cmw, pairs, pairCap, nPairs, dupBits, mWin);
+      if (samePrev) index_link_pair(r, sPos, mSeq, mWpos, cmw, pairs, pairCap, nPairs, dupBits, mWin);
     }
   }
   // one atomic per workgroup (the grid is small: a grid-stride loop covers the index)
@@ -131,6 +127,16 @@ static __global__ void k_index_links(const uint32_t *__restrict__ sHash, const u
     unsigned long long t = 0;
     for (unsigned w = 0; w < (blockDim.x >> 6); w++) t += part[w];
     if (t) atomicAdd(nUnique, t);
+  }
+}
+
+// position ranks back to seqId << 32 | wpos (the tests' view of the hash-ordered payload, ani_index_check)
+static __global__ void k_index_expand_pos(const uint32_t *__restrict__ sPos, uint32_t n, const int32_t *__restrict__ mSeq,
+                                   const int32_t *__restrict__ mWpos, uint64_t *__restrict__ out)
+{
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+    const uint32_t p = sPos[r];
+    out[r] = ((uint64_t)(uint32_t)mSeq[p] << 32) | (uint32_t)mWpos[p];
   }
 }
 
@@ -163,7 +169,7 @@ __host__ __device__ __forceinline__ uint32_t bucket_key(uint32_t h, int w)
 // hashes.  Slot of a hash = its (monotone) bucket key scaled to the table size; the distinct hashes are inserted in sorted order
 // with linear probing, so a cluster stays sorted and the i-th distinct hash lands at
 //     p_i = max(slot_i, p_(i-1) + 1) = i + max_(j <= i) (slot_j - j),
-// a running maximum — no atomics, no collisions to resolve.  A slot is 12 bytes {hash, first, cnt}: the hash's run in sSW (a
+// a running maximum — no atomics, no collisions to resolve.  A slot is 12 bytes {hash, first, cnt}: the hash's run in sPos (a
 // sentinel {~0, n | 2^31, 0} closes the table).  A probe reads the slot of the hash and walks forward while the entries are
 // smaller: one dependent load in most cases.  (With 8-byte slots the run length was the next occupied slot's `first` minus this
 // one's — at load 0.25 that was four more dependent loads per probe, and the probe kernel does nothing but wait for its loads.)

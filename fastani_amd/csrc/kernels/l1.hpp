@@ -7,7 +7,8 @@
 //
 // Two passes.  k_l1_probe: one lane per sketch hash, the index chunk's probe table (index.hpp), no LDS.  k_l1<HLO,HCAP>: one workgroup per fragment with HLO <
 // H <= HCAP seed hits,
-// gather the hit runs into LDS as 64-bit (seqId<<32 | wpos) keys, bitonic sort in registers (common.hpp: block_sort), flag valid runs, compact, flag
+// gather the hit runs into LDS as 32-bit position ranks (the index's sPos: an order-preserving stand-in for seqId<<32 | wpos), noise filter
+// and bitonic sort in registers (common.hpp: block_sort) on the ranks, expand them to (seqId<<32 | wpos) through mSeq / mWpos, flag valid runs, compact, flag
 // group heads by neighbour comparison (run starts/ends are non-decreasing, so "overlaps the previous candidate" only needs
 // the previous valid run), scan, emit.  Two LDS classes (S: <= 2032 hits, 20 KiB of LDS, 7 workgroups per CU; M: <= 4080 hits, 40 KiB, 4 per CU —
 // the constants below), the larger driven by a fragment list; fragments with at most 256 hits are finished by one wave each (k_l1_tiny).  Fragments
@@ -30,7 +31,9 @@ constexpr int kL1LdsSpare = 16;
 constexpr int kL1HitCapSmall = 2048 - kL1LdsSpare;
 // class S: 16 KiB hits + 4 KiB scratch, <= 72 registers -> 7 workgroups per CU.  The kernel's time follows the number of resident
 // workgroups (a workgroup's life is a chain of latencies — probe results, hit runs, LDS round trips of the sort — and what hides them
-// is other workgroups): 5 per CU 35.8 ms, 6 per CU 30.0 ms, 7 per CU 27.1 ms per benchmark step (profiles/r06f_l1_occupancy_ab.txt)
+// is other workgroups): 5 per CU 35.8 ms, 6 per CU 30.0 ms, 7 per CU 27.1 ms per benchmark step (profiles/r06f_l1_occupancy_ab.txt).
+// (Round 15: with ranks in the filter's and the sort's registers the compiler takes 50 for class S — below the 64 that eight workgroups
+// per CU need, and 8 x 20 KiB is the CU's 160 KiB exactly; class M takes 84, still four per CU by its LDS.  profiles/r15_l1_rank_ab.txt)
 constexpr int kL1HitCapMid = 4096 - kL1LdsSpare;      // class M: 32 KiB + 8 KiB -> 4 workgroups per CU
 constexpr int kL1HitCapMax = kL1HitCapMid;   // beyond: the batched global-memory path.  (A class L of 8192 hits — 96 KiB of LDS, one workgroup
                                              // per CU — existed until round 3: 0.43 us per fragment where the batched path takes 0.33, measured at
@@ -53,7 +56,8 @@ __device__ __forceinline__ L1FragDesc l1_frag_desc(const L1FragDesc *p)
 
 struct L1Args {
   const uint32_t *qPool; const uint32_t *fragOff; const int32_t *fragS; int32_t nFrag;
-  const TableSlot *table; uint32_t tableSlots; const uint64_t *sSW; int bucketW; uint32_t nIndex;
+  const TableSlot *table; uint32_t tableSlots; const uint32_t *sPos; int bucketW; uint32_t nIndex;
+  const int32_t *mSeq, *mWpos;          // the chunk's position-ordered arrays: a sorted rank p becomes the hit mSeq[p] << 32 | mWpos[p]
   const int32_t *minHitsLUT; int32_t lutMaxS;
   int L;
   // striped pool (common.hpp: pool_take): capacity per stripe, cursors
@@ -73,18 +77,18 @@ struct L1Args {
   int tinyPath;                         // fragments with <= 256 seed hits (kL1HitCapTiny) are finished by one wave (l1_tiny; ANI_TEST_L1_TINY=0 switches it off: A/B and tests)
 };
 
-// Counter indices of a hit's two tiles for the noise filter (k_l1): tiles of width 2^shift, the second tiling offset by half a tile.
-// The xor-shift between the two multiplications matters: without it the index is (seqId * K) >> n for hits in tile 0 of consecutive
-// contigs — a draft assembly's thousands of short contigs — and that sequence covers only half of the counters (2300 contigs:
-// 1172 distinct indices instead of ~2140; a collision only keeps a hit that could have been dropped, but it kept 97 % of them).
+// Counter indices of a hit's two tiles for the noise filter (k_l1), in RANK space: tiles of 2^shift consecutive position ranks, the second
+// tiling offset by half a tile; one multiplicative hash of the tile number each (consecutive tiles — the hits of a fragment against its
+// own genome's neighbourhood — spread evenly over the counters).  The filter's argument is at its use in k_l1.
 template <int BITS>
-__device__ __forceinline__ void l1_filter_tiles(uint64_t hv, int shift, uint32_t &ia, uint32_t &ib)
+__device__ __forceinline__ void l1_filter_tiles(uint32_t p, int shift, uint32_t &ia, uint32_t &ib)
 {
-  const uint32_t wpos = (uint32_t)hv, sq = (uint32_t)(hv >> 32);
-  uint32_t ha = sq * 0x9E3779B1u + (wpos >> shift), hb = sq * 0xC2B2AE3Du + ((wpos + (1u << (shift - 1))) >> shift);
-  ha ^= ha >> 15; hb ^= hb >> 15;
-  ia = (ha * 0x85EBCA77u) >> (32 - BITS); ib = (hb * 0x27D4EB2Fu) >> (32 - BITS);
+  ia = ((p >> shift) * 0x9E3779B1u) >> (32 - BITS);
+  ib = (((p + (1u << (shift - 1))) >> shift) * 0x85EBCA77u) >> (32 - BITS);
 }
+
+// a sorted position rank back to the hit it stands for
+__device__ __forceinline__ uint64_t l1_expand(const L1Args &a, uint32_t p) { return ((uint64_t)(uint32_t)a.mSeq[p] << 32) | (uint32_t)a.mWpos[p]; }
 
 // occurrences of hash h in the hash-ordered payload array: [first, first+cnt)
 __device__ __forceinline__ void l1_probe(const L1Args &a, uint32_t h, uint32_t &first, uint32_t &cnt) { table_probe(a.table, a.bucketW, a.tableSlots, h,
@@ -295,35 +299,46 @@ static __global__ __launch_bounds__(kTPB) void k_l1_probe(L1Args a)
 //           (common.hpp: wave_sort_regs);  runs / heads / emission: computeMap.hpp:313-354 in rounds of 64 runs, ballots instead of scans.
 constexpr int kL1HitCapTiny = 4 * kWave;           // 256 hits: four keys per lane
 constexpr int kL1TinyFrags = kTPB / kWave;
-// sort the H <= 64 * KPT hits in hits[] (LDS of this wave; padded with ~0 up to 64 * KPT) through registers
-template <int KPT> __device__ __forceinline__ void l1_tiny_sort(uint64_t *hits, int H)
+// the H <= 64 * KPT keys in keys[] (LDS of this wave) into registers, padded with ~0 and sorted: lane l holds the elements l * KPT + r
+template <class K, int KPT> __device__ __forceinline__ void l1_tiny_load_sort(const K *keys, int H, K (&k)[KPT])
 {
   const int lane = threadIdx.x & (kWave - 1);
-  uint64_t k[KPT];
 #pragma unroll
   // any assignment of the unordered keys will do: the conflict-free one
-  for (int r = 0; r < KPT; r++) { const int x = r * kWave + lane; k[r] = x < H ? hits[x] : ~0ull; }
+  for (int r = 0; r < KPT; r++) { const int x = r * kWave + lane; k[r] = x < H ? keys[x] : (K)~(K)0; }
   ANI_WAVE_SYNC();
-  wave_sort_regs<uint64_t, KPT>(k);                  // :320
+  wave_sort_regs<K, KPT>(k);                         // :320
+}
+// sort the H <= 64 * KPT position ranks in the front of hits[] (LDS of this wave) through registers and leave the hits they stand for,
+// sorted, in hits[0 .. H): every rank is in a register before the first 64-bit entry is written over them
+template <int KPT> __device__ __forceinline__ void l1_tiny_sort(const L1Args &a, uint64_t *hits, int H)
+{
+  const int lane = threadIdx.x & (kWave - 1);
+  uint32_t k[KPT];
+  l1_tiny_load_sort<uint32_t, KPT>((const uint32_t *)hits, H, k);
+  uint64_t hv[KPT];
 #pragma unroll
-  for (int r = 0; r < KPT; r++) hits[lane * KPT + r] = k[r];
+  for (int r = 0; r < KPT; r++) hv[r] = lane * KPT + r < H ? l1_expand(a, k[r]) : ~0ull;      // (never the padding: it is no rank)
+#pragma unroll
+  for (int r = 0; r < KPT; r++) hits[lane * KPT + r] = hv[r];
   ANI_WAVE_SYNC();
 }
 __device__ __forceinline__ void l1_tiny(const L1Args &a, int f, int s, int H, uint32_t off, int m, uint64_t *hits, int *V)
 {
   const int lane = threadIdx.x & (kWave - 1);
   if (m < 1) m = 1;                                  // :316
+  uint32_t *ranks = (uint32_t *)hits;                // the gathered position ranks: the front half of the wave's hit array
   int mine = 0;
   for (int i = lane; i < s; i += kWave) mine += (int)a.probeCnt[off + i];
   int o = wave_incl_scan(mine) - mine;
   for (int i = lane; i < s; i += kWave) {
     const int c = (int)a.probeCnt[off + i];
-    if (c) { const uint32_t fi = a.probeFirst[off + i]; for (int x = 0; x < c; x++) hits[o + x] = a.sSW[fi + x]; o += c; }
+    if (c) { const uint32_t fi = a.probeFirst[off + i]; for (int x = 0; x < c; x++) ranks[o + x] = a.sPos[fi + x]; o += c; }
   }
   ANI_WAVE_SYNC();
-  if (H <= kWave) l1_tiny_sort<1>(hits, H);          // wave-uniform
-  else if (H <= 2 * kWave) l1_tiny_sort<2>(hits, H);
-  else l1_tiny_sort<4>(hits, H);
+  if (H <= kWave) l1_tiny_sort<1>(a, hits, H);       // wave-uniform
+  else if (H <= 2 * kWave) l1_tiny_sort<2>(a, hits, H);
+  else l1_tiny_sort<4>(a, hits, H);
   // runs of m hits on one contig within < L (computeMap.hpp:326-336), positions x = r * 64 + lane, compacted in order
   const int nA = H - m + 1;
   int nG = 0;
@@ -417,10 +432,11 @@ static __global__ __launch_bounds__(kTPB) void k_l1_list(L1Args a, int32_t *__re
 // (Measured and removed in round 3: class M "in two walks" — the hit runs read twice, first only to feed the filter's counters,
 // then to stage the survivors in the 24 KiB that class S had then instead of 48 KiB (the classes have 20 and 40 KiB now).  1000 references: class M 4.8 -> 4.3 ms per launch; 10 000
 // references, where class M is mostly noise and the gather is all there is: L1 stage 83 -> 87 ms per 300 queries.  One read wins.
-// Also measured and removed: 32-bit sort keys (rank of the contig among the fragment's distinct contigs << posBits | wpos: 3 instead of
-// 7 instructions per key and lane-exchange stage).  The ranks need a hash set of the contig ids in LDS, the distinct ids sorted, a
-// look-up per hit — five more barrier-separated phases and 20 more registers (5 instead of 6 workgroups per CU): class S, then k_l1<0,2048>, went
-// from 30.7 to 41.2 ms per step, bit-exact.)
+// Also measured and removed: 32-bit sort keys computed PER FRAGMENT (rank of the contig among the fragment's distinct contigs << posBits |
+// wpos: 3 instead of 7 instructions per key and lane-exchange stage).  The ranks need a hash set of the contig ids in LDS, the distinct
+// ids sorted, a look-up per hit — five more barrier-separated phases and 20 more registers (5 instead of 6 workgroups per CU): class S,
+// then k_l1<0,2048>, went from 30.7 to 41.2 ms per step, bit-exact.  The 32-bit key of round 15 is the index's own position rank, which
+// costs nothing to get: the index sort carries it instead of seqId << 32 | wpos.)
 template <int HLO, int HCAP>
 static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a, const int32_t *__restrict__ list)
 {
@@ -433,6 +449,9 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
   constexpr int kVWords = 4 * NBW > kMaxS ? 4 * NBW : kMaxS;
   static_assert((kArr & (kArr - 1)) == 0 && kVWords * 4 >= kArr * (int)sizeof(VT) && kVWords >= kMaxS, "the scratch holds the run indices and the hit offsets");
   __shared__ uint64_t hits[kArr];
+  // gather, filter and sort work on 32-bit position ranks in the FRONT HALF of the hit array (kArr ranks: the sort's padding stays below
+  // the spare entries); the sorted ranks are expanded to hits over the whole array afterwards
+  uint32_t *ranks = (uint32_t *)hits;
   __shared__ __attribute__((aligned(16))) uint32_t Vraw[kVWords];
   VT *V = (VT *)Vraw;
   int *ws = (int *)&hits[HCAP];                                   // 16 ints of scan scratch ...
@@ -474,15 +493,16 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
   // the lines arrive at the memory system's pace for random 128-byte lines, however the requests are issued.)  Measured by compiling the later phases out
   // (1000 x 1000 x 5 Mbp, ms per step of this kernel): gather 13.4,
   // noise filter +2.2, sort +10.3 (in registers; the LDS network it replaced: +14.8), candidate emission +4.0.  The gather reads one
-  // short run (~5 entries = 40 bytes) per sketch hash from a random place of the hash-ordered payload: ~45 KB of 128-byte lines per
-  // fragment for 10 KB of hits, 77 GB per step by the FETCH_SIZE counter — it runs at the memory system's pace for such lines.
+  // short run (~5 entries) per sketch hash from a random place of the hash-ordered payload — with the 64-bit payload of rounds 1 - 14
+  // 40 bytes: ~45 KB of 128-byte lines per fragment for 10 KB of hits, 77 GB per step by the FETCH_SIZE counter — it runs at the memory
+  // system's pace for such lines.  (The payload is the 32-bit position rank now: 20 bytes per run.)
 #pragma unroll
   for (int j = 0; j < kPerS; j++) {
     const int i = t + j * kTPB;
     if (i < s) {
       const int o = pOff[i], e = (i + 1 < s) ? pOff[i + 1] : H;
       const uint32_t fi = pFirst[j];
-      for (int c = 0; c < e - o; c++) hits[o + c] = a.sSW[fi + c];
+      for (int c = 0; c < e - o; c++) ranks[o + c] = a.sPos[fi + c];
     }
   }
   // Noise filter.  Minimizer hashes are minima over w k-mers, so they crowd the low end of the 32-bit range and most seed hits of
@@ -492,6 +512,10 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
   // spans it, i.e. would have been such a neighbour: dropping those hits leaves every candidate unchanged and shortens the sort.
   // "Has a neighbour" is tested conservatively with two offset tilings of width W >= 2 fragLen (two points closer than W/2 share a
   // tile in one of them) hashed into 2-bit occupancy counters: a collision only keeps a hit that could have been dropped.
+  // The tiles are cut in RANK space (W consecutive position ranks), which is as exact: wpos is strictly increasing inside a contig, so
+  // two hits of one contig less than fragLen apart in wpos are less than fragLen <= W / 2 apart in rank — a hit with no other hit within
+  // < fragLen ranks has no neighbour in the sense above and is in no valid run.  A rank neighbour across a contig border, or one of a
+  // sparse stretch that is >= fragLen away in wpos, only keeps a hit that could have been dropped (l1_valid decides on the expanded hits).
   int n = H;
   if (m >= 2 && H > a.filterMinHits) {
     uint32_t *bits = Vraw;
@@ -500,12 +524,12 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
     if (t == 0) sKeep = 0;
     block_barrier();
     constexpr int PER = kArr / kTPB;
-    uint64_t hv[PER];
+    uint32_t hv[PER];
 #pragma unroll
     for (int j = 0; j < PER; j++) {
       const int x = t + j * kTPB;
       if (x < H) {
-        hv[j] = hits[x];
+        hv[j] = ranks[x];
         uint32_t ia, ib;
         l1_filter_tiles<kL1FilterBits<HCAP>()>(hv[j], a.filterShift, ia, ib);
         const uint32_t ba = 1u << (ia & 31), bb = 1u << (ib & 31);
@@ -514,7 +538,7 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
       }
     }
     block_barrier();
-    // (the counter indices are computed again rather than kept across the barrier: sixteen registers, which decide how many workgroups a CU holds)
+    // (the counter indices are computed again rather than kept across the barrier: registers decide how many workgroups a CU holds)
 #pragma unroll
     for (int j = 0; j < PER; j++) {
       const int x = t + j * kTPB;
@@ -522,15 +546,28 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
         uint32_t ia, ib;
         l1_filter_tiles<kL1FilterBits<HCAP>()>(hv[j], a.filterShift, ia, ib);
         const bool keep = ((bits[NBW + (ia >> 5)] >> (ia & 31)) | (bits[3 * NBW + (ib >> 5)] >> (ib & 31))) & 1u;
-        if (keep) hits[atomicAdd(&sKeep, 1)] = hv[j];      // every lane has read its hits: compaction in place, order irrelevant
+        if (keep) ranks[atomicAdd(&sKeep, 1)] = hv[j];     // every lane has read its ranks: compaction in place, order irrelevant
       }
     }
     block_barrier();
     n = wave_uniform(sKeep);
-    // sKeep lives in the hit array's spare entries, which the sort's padding overwrites: every thread has read it
+  }
+  block_sort<uint32_t>(ranks, n);                   // :320 (starts with a barrier: the gather is complete)
+  // Sorted ranks -> hits, in place: rank x lives in the bytes of hit x / 2, so every thread takes its ranks into registers (and starts
+  // its two loads per rank) before any hit is written.  One more dependent round trip to memory in the workgroup's life.
+  {
+    constexpr int PER = kArr / kTPB;
+    uint32_t pr[PER];
+#pragma unroll
+    for (int j = 0; j < PER; j++) { const int x = t + j * kTPB; if (x < n) pr[j] = ranks[x]; }
+    uint64_t hx[PER];
+#pragma unroll
+    for (int j = 0; j < PER; j++) { const int x = t + j * kTPB; if (x < n) hx[j] = l1_expand(a, pr[j]); }      // (x < n: never the ~0 padding)
+    block_barrier();
+#pragma unroll
+    for (int j = 0; j < PER; j++) { const int x = t + j * kTPB; if (x < n) hits[x] = hx[j]; }
     block_barrier();
   }
-  block_sort<uint64_t>(hits, n);                    // :320 (starts with a barrier: the gather is complete)
 
   l1_emit_candidates(a, f, s, n, m, hits, V, ws, &sBase);
 }
@@ -540,10 +577,10 @@ static __global__ __launch_bounds__(kTPB, (HLO == 0 ? 7 : 1)) void k_l1(L1Args a
 // low-complexity references with 10^5..10^6 occurrences of one hash — take the same algorithm over global memory, BATCHED: the big
 // fragments of a sub-batch are cut into groups (a few 10^8 hits each), and a group costs five launches whatever its size:
 //   k_l1_big_offsets     per fragment: exclusive scan of its probes' run lengths (the start of every hash's hits in the fragment's list)
-//   k_l1_big_gather      one workgroup per tile of 16384 hits: hit x of fragment i -> key (i, seqId, wpos) in ONE 64-bit word
-//                        (field widths from the chunk's contig count and longest contig), read from the hash-ordered payload
-//   device radix sort    over the used key bits only: orders by fragment, then (seqId, wpos) — computeMap.hpp:320 for all fragments at once
-//   k_l1_big_unpack      keys back to (seqId << 32 | wpos)
+//   k_l1_big_gather      one workgroup per tile of 16384 hits: hit x of fragment i -> key (i, position rank) in ONE 64-bit word
+//                        (the rank field as wide as the chunk's entry count needs), read from the hash-ordered payload
+//   device radix sort    over the used key bits only: orders by fragment, then rank = (seqId, wpos) — computeMap.hpp:320 for all fragments at once
+//   k_l1_big_unpack      keys to (seqId << 32 | wpos) through mSeq / mWpos
 //   k_l1_big_candidates  one workgroup per fragment over its sorted slice (l1_emit_candidates_stream: the algorithm of the LDS classes,
 //                        walked in coalesced chunks of 256 entries)
 // ------------------------------------------------------------------------------------------------
@@ -555,7 +592,7 @@ struct L1BigArgs {
   const uint32_t *tileFirst;    // [n+1] first tile of every fragment
   int32_t *hashOff;             // [sum s] start of every hash's hits inside its fragment's list
   uint64_t *keys;               // [sum H]
-  int n; int shiftSeq, shiftRank;       // key = rank << shiftRank | seqId << shiftSeq | wpos
+  int n; int shiftRank;                 // key = fragment's rank in the group << shiftRank | position rank (shiftRank: the bits that hold the chunk's entry count)
 };
 
 static __global__ void k_l1_big_info(const int32_t *__restrict__ list, uint32_t n, const int32_t *__restrict__ fragS, const int32_t *__restrict__ fragHits,
@@ -606,17 +643,17 @@ static __global__ __launch_bounds__(kTPB) void k_l1_big_gather(L1Args a, L1BigAr
     int lo = j, hi = s;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (sho[mid] <= x) lo = mid; else hi = mid; }
     j = lo;
-    const uint64_t hit = a.sSW[a.probeFirst[off + j] + (uint32_t)(x - sho[j])];
-    out[x] = ((uint64_t)(uint32_t)i << g.shiftRank) | ((hit >> 32) << g.shiftSeq) | (uint64_t)(uint32_t)hit;
+    out[x] = ((uint64_t)(uint32_t)i << g.shiftRank) | (uint64_t)a.sPos[a.probeFirst[off + j] + (uint32_t)(x - sho[j])];
   }
 }
 
-static __global__ void k_l1_big_unpack(uint64_t *__restrict__ keys, uint64_t n, int shiftSeq, int shiftRank)
+static __global__ void k_l1_big_unpack(uint64_t *__restrict__ keys, uint64_t n, int shiftRank, const int32_t *__restrict__ mSeq,
+                                const int32_t *__restrict__ mWpos)
 {
-  const uint64_t mSeq = (1ull << (shiftRank - shiftSeq)) - 1, mPos = (1ull << shiftSeq) - 1;
+  const uint64_t mask = (1ull << shiftRank) - 1;
   for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t k = keys[x];
-    keys[x] = (((k >> shiftSeq) & mSeq) << 32) | (k & mPos);
+    const uint32_t p = (uint32_t)(keys[x] & mask);
+    keys[x] = ((uint64_t)(uint32_t)mSeq[p] << 32) | (uint32_t)mWpos[p];
   }
 }
 

@@ -2,7 +2,8 @@
 // read + one write of the data per 8-bit pass, tile prefixes by decoupled look-back).
 //
 // What it sorts on this path:
-//   * the reference index: minimizer records (hash, seqId, wpos) in position order -> (hash, seqId<<32|wpos) in hash order, every
+//   * the reference index: minimizer records (hash, seqId, wpos) in position order -> (hash, position rank) in hash order (the rank is
+//     the entry's index into the position-ordered arrays: a 32-bit stand-in for seqId<<32|wpos, SoaPosSrc below), every
 //     hash's occurrences still in (seqId, wpos) order — the flat form of filling minimizerPosLookupIndex
 //     (src/map/include/winSketch.hpp:181-193: `minimizerPosLookupIndex[e.hash].push_back(...)` in position order).  The first pass
 //     reads the 12-byte records where they lie (RecordSrc) and the histogram pass writes the position-ordered SoA arrays on the way,
@@ -67,6 +68,12 @@ struct SoaSrc {
   const uint32_t *mHash; const int32_t *mSeq, *mWpos;
   __device__ __forceinline__ uint32_t key(uint64_t i) const { return mHash[i]; }
   __device__ __forceinline__ uint64_t val(uint64_t i) const { return ((uint64_t)(uint32_t)mSeq[i] << 32) | (uint32_t)mWpos[i]; }
+};
+// the same with the entry's position rank as the value (its index into mSeq / mWpos; a chunk holds < 2^31 entries): nothing to read
+struct SoaPosSrc {
+  const uint32_t *mHash;
+  __device__ __forceinline__ uint32_t key(uint64_t i) const { return mHash[i]; }
+  __device__ __forceinline__ uint32_t val(uint64_t i) const { return (uint32_t)i; }
 };
 // 12-byte minimizer records (skch::MinimizerInfo, base_types.hpp:22-53) with set-global seqIds; the index chunk's seqIds are local
 struct RecordSrc {
@@ -166,8 +173,8 @@ static __global__ __launch_bounds__(kTPB) void k_radix_scan(unsigned long long *
 //   status     [(all tiles) * 256], zeroed;  tileCounter zeroed per launch;  errFlag: set when a look-back gave up
 // 512 threads x 12 keys: the tile's life is a string of latencies (key loads, one LDS round trip per ranked key, the look-back's
 // round trips past the L2, value loads) and what hides them is waves — 8 per workgroup; LDS per workgroup = the staging tile (6144 x max(key, value)
-// bytes: 48 KiB for the index's u32 / u64 pass, 24 KiB for u32-only) + 8 KiB of per-wave digit counters + 1 KiB of run bases ≈ 57 KiB for
-// the index pass, i.e. 2 workgroups = 16 waves per CU of 160 KiB — not instruction-level tricks: 256 x 16 (the same tile, 105 VGPRs, 16 waves per CU) measured
+// bytes: 48 KiB for a u32 / u64 pass, 24 KiB for the index's u32 / u32 pass) + 8 KiB of per-wave digit counters + 1 KiB of run bases ≈ 57 KiB for
+// a pass with a 64-bit payload, i.e. 2 workgroups = 16 waves per CU of 160 KiB (33 KiB and 4 workgroups for the index pass since its payload is the 32-bit rank) — not instruction-level tricks: 256 x 16 (the same tile, 105 VGPRs, 16 waves per CU) measured
 // 4.7 ms per pass of 4 x 10^8
 // records against 2.7 ms for rocPRIM's onesweep (profiles/r04c_radix_kernel_stats.csv).
 template <class KeyT, class ValT, class Src>

@@ -22,7 +22,7 @@
 //                                                                 [1][T] wave_uniform(x) taken with the lanes l % 4 == 1 only, ~x in the others
 //   BLOCK_SORT_U32 / _U64    u32/u64 1 1    256          <= 4096  [0][0..n) block_sort of in[0..n)
 //   BITONIC_U32 / _U64       u32/u64 1 1    256          <= 4096  [0][0..n) block_bitonic_sort of in[0..n) padded with ~0 to next_pow2(n)
-//   WAVE_SORT_1 / _2 / _4    u64   4   4    256          <= 64 KPT [w][0..n) l1_tiny_sort<KPT> (wave_sort_regs) of in[w][0..n), every wave its own
+//   WAVE_SORT_1 / _2 / _4    u64   4   4    256          <= 64 KPT [w][0..n) l1_tiny_load_sort<u64, KPT> (wave_sort_regs) of in[w][0..n), every wave its own
 //   ROTL64                   u64   1   63   256          <= cap   [r - 1][i] rotl64(in[i], r), r = 1 .. 63
 //   PERM_B32                 u32   2   1    256          <= cap / 4096   [0][i * 4096 + s] perm_b32(in[0][i], in[1][i], selector s): byte j of the
 //                                                                 selector = bits [3 j, 3 j + 3) of s
@@ -152,7 +152,11 @@ template <int KPT> __global__ __launch_bounds__(kTPB) void k_prim_wave_sort(Slot
   uint64_t *res = s.dst<uint64_t>(4, wv);
   for (int x = lane; x < H; x += kWave) hits[x] = in[x];
   ANI_WAVE_SYNC();
-  l1_tiny_sort<KPT>(hits, H);
+  uint64_t k[KPT];
+  l1_tiny_load_sort<uint64_t, KPT>(hits, H, k);     // (k_l1_tiny sorts 32-bit ranks through the same function)
+#pragma unroll
+  for (int r = 0; r < KPT; r++) hits[lane * KPT + r] = k[r];
+  ANI_WAVE_SYNC();
   for (int x = lane; x < H; x += kWave) res[x] = hits[x];
 }
 

@@ -144,9 +144,16 @@ extern "C" int ani_sort_keys_u64_range(const uint64_t *keysIn, uint64_t *keysOut
 // (seqId, wpos) order).  tmpK / tmpV: n-element ping-pong arrays.  soaReady / sideStream (optional): the event is recorded once the SoA
 // arrays are written and sideStream is made to wait for it; the call then returns with the passes still running — the caller queues its
 // side work and calls ani_sort_check.  Four 8-bit passes: SoA -> tmp -> (sHash, sSW) -> tmp -> (sHash, sSW).
-extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
-                              uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint64_t *tmpV, uint32_t *sHash, uint64_t *sSW,
-                              void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream)
+namespace {
+// pass 0 of the index sort: key = hash, value = what the entry carries through the sort (radix.hpp: SoaSrc, SoaPosSrc)
+inline SoaSrc first_pass_src(const uint32_t *mHash, const int32_t *mSeq, const int32_t *mWpos, uint64_t) { return SoaSrc{mHash, mSeq, mWpos}; }
+inline SoaPosSrc first_pass_src(const uint32_t *mHash, const int32_t *, const int32_t *, uint32_t) { return SoaPosSrc{mHash}; }
+
+// both index sorts: ValT = uint64_t carries seqId << 32 | wpos (ani_sort_index), ValT = uint32_t the position rank (ani_sort_index_pos)
+template <class ValT>
+int sort_index(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
+               uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, ValT *tmpV, uint32_t *sHash, ValT *sVal,
+               void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream)
 {
   constexpr int P = 4;
   const uint64_t tiles = tiles_of(n);
@@ -179,24 +186,24 @@ extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN,
     if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(kTPB), 0, stream, w.hist, P);
-  // pass 0 reads the SoA arrays the histogram pass has just written (three coalesced streams; the 12-byte records would be three
-  // strided ones), so the record buffers are read exactly once
+  // pass 0 reads the SoA arrays the histogram pass has just written (coalesced streams; the 12-byte records would be strided
+  // ones), so the record buffers are read exactly once.  (The rank payload reads mHash alone.)
   e = hipMemsetAsync(w.status, 0, w.statusBytes, stream);
   if (e != hipSuccess) return (int)e;
   int launch = 0;
   {
-    SoaSrc src{mHash, mSeq, mWpos};
-    hipLaunchKernelGGL((k_radix_pass<uint32_t, uint64_t, SoaSrc>), dim3((unsigned)tiles_of(n)), dim3(kRadixTPB), 0, stream, src, tmpK, tmpV, (uint64_t)n, 0, 32,
+    auto src = first_pass_src(mHash, mSeq, mWpos, ValT());
+    hipLaunchKernelGGL((k_radix_pass<uint32_t, ValT, decltype(src)>), dim3((unsigned)tiles_of(n)), dim3(kRadixTPB), 0, stream, src, tmpK, tmpV, (uint64_t)n, 0, 32,
                        (const unsigned long long *)w.hist, w.status, w.counters + launch, 0u, w.err);
     launch++;
   }
   for (int p = 1; p < P; p++) {
     const bool toOut = (p & 1) == 1;                         // tmp -> S -> tmp -> S
-    ArraySrc<uint32_t, uint64_t> src = toOut ? ArraySrc<uint32_t, uint64_t>{tmpK, tmpV} : ArraySrc<uint32_t, uint64_t>{sHash, sSW};
+    ArraySrc<uint32_t, ValT> src = toOut ? ArraySrc<uint32_t, ValT>{tmpK, tmpV} : ArraySrc<uint32_t, ValT>{sHash, sVal};
     e = hipMemsetAsync(w.status, 0, w.statusBytes, stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_radix_pass<uint32_t, uint64_t, ArraySrc<uint32_t, uint64_t>>), dim3((unsigned)tiles_of(n)), dim3(kRadixTPB), 0, stream, src,
-        toOut ? sHash : tmpK, toOut ? sSW : tmpV,
+    hipLaunchKernelGGL((k_radix_pass<uint32_t, ValT, ArraySrc<uint32_t, ValT>>), dim3((unsigned)tiles_of(n)), dim3(kRadixTPB), 0, stream, src,
+        toOut ? sHash : tmpK, toOut ? sVal : tmpV,
                        (uint64_t)n, p * kRadixBits, 32, (const unsigned long long *)(w.hist + p * kRadixDigits), w.status, w.counters + launch, 0u, w.err);
     launch++;
   }
@@ -205,6 +212,29 @@ extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN,
   if (rc != 9001) break;
   }
   return rc;
+}
+}  // namespace
+
+extern "C" int ani_sort_index(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
+                              uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint64_t *tmpV, uint32_t *sHash, uint64_t *sSW,
+                              void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream)
+{
+  return sort_index<uint64_t>(pieceRec, pieceN, nPieces, seqBase, n, mHash, mSeq, mWpos, tmpK, tmpV, sHash, sSW, tmp, tmpBytes, stream, soaReady,
+      sideStream);
+}
+
+// The index sort as the index build runs it: the payload is the entry's POSITION RANK p (its index into mSeq / mWpos, < 2^31) instead
+// of seqId << 32 | wpos.  The position-ordered arrays are sorted by (seqId, wpos) — records arrive in contig order and wpos is strictly
+// increasing inside a contig — so p orders a hash's occurrences exactly as the pair does, in half the bytes: every pass moves 4 + 4
+// bytes per element instead of 4 + 8, a tile's staging area is 24 KiB instead of 48, and pass 0 reads mHash alone (val(i) = i).
+// Output: sHash / sPos; tmpK / tmpV: n 32-bit elements each.  Stability, the look-back retry and the side-stream contract are
+// ani_sort_index's.
+extern "C" int ani_sort_index_pos(const void *const *pieceRec, const size_t *pieceN, int nPieces, uint32_t seqBase, size_t n,
+                                  uint32_t *mHash, int32_t *mSeq, int32_t *mWpos, uint32_t *tmpK, uint32_t *tmpV, uint32_t *sHash, uint32_t *sPos,
+                                  void *tmp, size_t *tmpBytes, hipStream_t stream, hipEvent_t soaReady, hipStream_t sideStream)
+{
+  return sort_index<uint32_t>(pieceRec, pieceN, nPieces, seqBase, n, mHash, mSeq, mWpos, tmpK, tmpV, sHash, sPos, tmp, tmpBytes, stream, soaReady,
+      sideStream);
 }
 
 // completes an ani_sort_index call that was given a side stream: waits for the sort and checks its error flag
