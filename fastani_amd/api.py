@@ -47,6 +47,8 @@ FRAGDIST_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count"
 HIT_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("querySeqId", "<i4"), ("identity", "<f4")])
 CI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("replicates", "<u4"), ("sum", "<u8"), ("lowSum", "<u8"),
                   ("highSum", "<u8"), ("low", "<f4"), ("high", "<f4")])
+PAINT_DT = np.dtype([("qryGenomeId", "<i4"), ("querySeqId", "<i4"), ("refGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("identity", "<f4"),
+                     ("secondGenomeId", "<i4"), ("secondIdentity", "<f4"), ("genomes", "<u4"), ("reserved", "<u4")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -153,6 +155,10 @@ def _bind(lib):
         "ani_sketch_ci_begin": (C.c_int, [vp, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]),
         "ani_sketch_ci_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_ci_end": (C.c_int, [vp]),
+        "ani_sketch_paint_begin": (C.c_int, [vp]),
+        "ani_sketch_paint_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_paint_end": (C.c_int, [vp]),
+        "ani_paint_merge": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_cluster_greedy": (C.c_int, [vp, vp, C.c_size_t, C.c_int32, C.c_float, vp, vp]),
@@ -300,6 +306,26 @@ class UploadedGenomes:
             self.close()
         except Exception:
             pass
+
+
+def paint_merge(a, b, lib=None):
+    """-> PAINT_DT[n]: the records of two lists over disjoint sets of reference genomes, each in (qryGenomeId, querySeqId) order, joined
+    into the list over the union (ani_paint_merge: a host function, no engine).  `lib`: the library to call, the product library by
+    default."""
+    if lib is None:
+        from . import _lib
+        lib = _lib.load()
+    if lib.ani_paint_merge.argtypes is None:      # no Engine has bound this library yet
+        _bind(lib)
+    a, b = np.ascontiguousarray(a, dtype=PAINT_DT), np.ascontiguousarray(b, dtype=PAINT_DT)
+    rp, n = C.c_void_p(), C.c_size_t()
+    rc = lib.ani_paint_merge(a.ctypes.data if len(a) else None, len(a), b.ctypes.data if len(b) else None, len(b), C.byref(rp), C.byref(n))
+    if rc != 0:
+        raise AniError(rc, (lib.ani_last_error() or b"").decode())
+    if n.value == 0 or not rp.value:
+        lib.ani_free(rp)
+        return np.zeros(0, dtype=PAINT_DT)
+    return np.asarray(_OwnedBuffer(lib, rp.value, n.value, PAINT_DT))
 
 
 def _as_batch(g):
@@ -997,6 +1023,22 @@ class Sketch:
 
     def ci_end(self):
         self.e._chk(self.e.lib.ani_sketch_ci_end(self.h))
+
+    def paint_begin(self):
+        """start the per-fragment records: every mapping call that reduces against this sketch appends one record per query fragment
+        that maps to at least one reference genome — its best reference, the runner-up and the number of genomes hit
+        (ani_sketch_paint_begin); refused while the mode is on"""
+        self.e._chk(self.e.lib.ani_sketch_paint_begin(self.h))
+
+    def paint_take(self):
+        """-> PAINT_DT[n]: the records appended since paint_begin or the last take, in the calls' query order, querySeqId ascending;
+        empties the list"""
+        rp, n = C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_paint_take(self.h, C.byref(rp), C.byref(n)))
+        return self.e._take(rp, n.value, PAINT_DT)
+
+    def paint_end(self):
+        self.e._chk(self.e.lib.ani_sketch_paint_end(self.h))
 
     def profile_layout(self):
         """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and

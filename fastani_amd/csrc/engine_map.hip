@@ -13,6 +13,7 @@
 #include "kernels/fragdist.hpp"
 #include "kernels/ci.hpp"
 #include "kernels/hits.hpp"
+#include "kernels/paint.hpp"
 
 namespace anih {
 using namespace ani;
@@ -687,6 +688,101 @@ static int ci_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const PairArg
   return ANI_OK;
 }
 
+// The partial paint records of one (sub-batch, index chunk) (kernels/paint.hpp), from the candidates k_oneway_bins
+// read: best -> second over the candidates, flags -> scan for the mapped fragments' slots, then the records piece by piece (paintPiece
+// records per launch and copy) through page-locked memory into ctx->paintStage as one more part, where collect_rows finds them.  Only
+// while the sketch has the mode on.
+static int paint_stage(ani_ctx *ctx, IndexChunk *sk, const OneWayArgs &wa, const FragSet &fs)
+{
+  const size_t nF = (size_t)std::max(fs.nFrag, 0);
+  if (wa.nCand == 0 || nF == 0) return ANI_OK;
+  if (!fs.fragQSeq) return fail(ANI_ERR_ARG, "paint records need the fragments' querySeqId");
+  TRY(ctx->paintBest.ensure(nF * 8)); TRY(ctx->paintSecond.ensure(nF * 8)); TRY(ctx->paintGenomes.ensure(nF * 4)); TRY(ctx->paintWin.ensure(nF * 4));
+  TRY(ctx->paintFlags.ensure(nF * 4)); TRY(ctx->paintOff.ensure(nF * 4));
+  PaintArgs pa;
+  pa.w = wa; pa.fragQSeq = fs.fragQSeq; pa.nFrag = (int32_t)nF; pa.genomeBase = sk->g0; pa.seqBase = sk->c0;
+  pa.best = ctx->paintBest.as<unsigned long long>(); pa.second = ctx->paintSecond.as<unsigned long long>();
+  pa.genomes = ctx->paintGenomes.as<uint32_t>(); pa.win = ctx->paintWin.as<uint32_t>();
+  HIP_TRY(hipMemsetAsync(ctx->paintBest.p, 0, nF * 8, ctx->stream)); HIP_TRY(hipMemsetAsync(ctx->paintSecond.p, 0, nF * 8, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->paintGenomes.p, 0, nF * 4, ctx->stream)); HIP_TRY(hipMemsetAsync(ctx->paintWin.p, 0xff, nF * 4, ctx->stream));
+  hipLaunchKernelGGL(k_paint_best, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, pa);
+  hipLaunchKernelGGL(k_paint_second, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, pa);
+  hipLaunchKernelGGL(k_paint_flags, dim3(grid_for(nF, kTPB)), dim3(kTPB), 0, ctx->stream, pa, ctx->paintFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t total = 0;
+  TRY(device_scan(ctx, ctx->paintFlags.as<int32_t>(), ctx->paintOff.as<uint32_t>(), (uint32_t)nF, &total, 0xfffffff0ull));
+  if (total == 0) return ANI_OK;
+  const size_t piece = std::min<size_t>(ctx->paintPiece, (size_t)total);
+  TRY(ctx->paintRec.ensure(piece * sizeof(PaintRec)));
+  uint8_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, piece * sizeof(PaintRec), (void **)&host));
+  PaintParts &st = ctx->paintStage;
+  if (!st.buf.reserve((size_t)total)) return fail(ANI_ERR_NOMEM, "host allocation of %llu paint records failed", (unsigned long long)total);
+  static_assert(sizeof(PaintRec) == sizeof(ani_paint_t), "the device record is the ABI's");
+  for (size_t first = 0; first < (size_t)total; first += piece) {
+    const size_t n = std::min<size_t>(piece, (size_t)total - first);
+    hipLaunchKernelGGL(k_paint_records, dim3(grid_for(nF, kTPB)), dim3(kTPB), 0, ctx->stream, pa, (const int32_t *)ctx->paintFlags.as<int32_t>(),
+                       (const uint32_t *)ctx->paintOff.as<uint32_t>(), (uint32_t)first, (uint32_t)n, ctx->paintRec.as<PaintRec>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, ctx->paintRec.p, n * sizeof(PaintRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t slice = 8192, at = st.buf.n;
+    parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(PaintRec), [&](size_t j) {      // (into fresh pages: see fragdist_stage)
+      const size_t r0 = j * slice, m = std::min(slice, n - r0);
+      memcpy(st.buf.rec + at + r0, host + r0 * sizeof(PaintRec), m * sizeof(PaintRec));
+    });
+    st.buf.n += n;
+  }
+  st.cut.push_back(st.buf.n);
+  return ANI_OK;
+}
+
+// The staged parts of a sub-batch (ctx->paintStage) get the rows' ids and move to `out`, behind the parts it holds.
+template <class Patch>
+static int paint_collect(PaintParts &in, Patch patch, PaintParts *out)
+{
+  const size_t n = in.buf.n, slice = 65536;
+  if (n == 0) { in.clear(); return ANI_OK; }
+  parallel_for((n + slice - 1) / slice, (uint64_t)n * sizeof(ani_paint_t), [&](size_t j) {
+    for (size_t r = j * slice, r1 = std::min(n, (j + 1) * slice); r < r1; r++) patch(in.buf.rec[r]); });
+  const size_t at = out->buf.n;
+  if (at == 0 && out->cut.size() == 1) { out->buf.swap(in.buf); out->cut.swap(in.cut); }
+  else {
+    if (!out->buf.reserve(n)) return fail(ANI_ERR_NOMEM, "host allocation of %zu paint records failed", n);
+    memcpy(out->buf.rec + at, in.buf.rec, n * sizeof(ani_paint_t));
+    out->buf.n = at + n;
+    for (size_t k = 1; k < in.cut.size(); k++) out->cut.push_back(at + in.cut[k]);
+  }
+  in.clear();
+  return ANI_OK;
+}
+
+// The parts of ONE sub-batch (one per index chunk that gave it records; the chunks hold disjoint genomes) joined by ani_paint_merge and
+// appended to `out`: the one way of the resident and the streamed path.
+static int paint_join(PaintParts &parts, PaintBuf *out)
+{
+  const size_t nParts = parts.cut.size() - 1;
+  if (parts.buf.n == 0) { parts.clear(); return ANI_OK; }
+  if (nParts == 1 && out->n == 0) { out->swap(parts.buf); parts.clear(); return ANI_OK; }      // one chunk, nothing pending: the buffer itself
+  ani_paint_t *acc = nullptr; size_t nAcc = 0;            // nullptr: the first part itself
+  const ani_paint_t *cur = parts.buf.rec + parts.cut[0]; size_t nCur = parts.cut[1] - parts.cut[0];
+  for (size_t k = 1; k < nParts; k++) {
+    ani_paint_t *next = nullptr; size_t nNext = 0;
+    const int rc = ani_paint_merge(cur, nCur, parts.buf.rec + parts.cut[k], parts.cut[k + 1] - parts.cut[k], &next, &nNext);
+    free(acc);
+    if (rc != ANI_OK) return rc;
+    acc = next; nAcc = nNext; cur = acc; nCur = nAcc;
+  }
+  if (nCur) {
+    if (!out->reserve(nCur)) { free(acc); return fail(ANI_ERR_NOMEM, "host allocation of %zu paint records failed", nCur); }
+    memcpy(out->rec + out->n, cur, nCur * sizeof(ani_paint_t));
+    out->n += nCur;
+  }
+  free(acc);
+  parts.clear();
+  return ANI_OK;
+}
+
 // 1-way / 2-way / mean (computeCoreIdentity.hpp:214-297) for the candidates map_stage left in the context's buffers, against one
 // index chunk; the (count, identity) results go to the chunk's column block of the dense [nQuery][nRefGenomes] table in ctx->rows.
 // `compact`: the table holds this chunk's genomes only ([nQuery][chunk genomes]; a streamed set is reduced and read back chunk by chunk)
@@ -739,6 +835,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(ci_stage(ctx, set, sk, pa));
   }
+  if (set->paint) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(paint_stage(ctx, sk, a, fs));
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -747,9 +847,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 // the dense table of a sub-batch (all chunks reduced) -> rows in (query, reference genome) order, appended to `rows`
 // (`block`: the table is the compact one of that chunk — reference genome = block->g0 + column)
 // (fdOut, hitOut, ciOut: where the sub-batch's fragment distribution, best-hit and interval records go while those modes are on —
-// default: the sketch's pending lists)
+// default: the sketch's pending lists; paintOut: where the chunk's part of the paint records waits for the sub-batch's other chunks —
+// default: this call has seen every chunk, the parts are joined into the sketch's pending list)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
-    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr)
+    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr, PaintParts *paintOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
@@ -775,6 +876,16 @@ int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuer
         [](const ani_ci_t &r) { return (size_t)r.qryGenomeId; },
         [&](ani_ci_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
         ciOut ? ciOut : &set->ciPending));
+  }
+  if (set->paint) {
+    // per fragment, not per pair: ids first, then (all chunks seen) the join of the chunks' parts
+    const int32_t base = set->refIdBase;
+    PaintParts own;
+    PaintParts *to = paintOut ? paintOut : &own;
+    TRY(paint_collect(ctx->paintStage, [&](ani_paint_t &r) {
+          r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base;
+          if (r.secondGenomeId >= 0) r.secondGenomeId += base; }, to));
+    if (!paintOut) TRY(paint_join(own, &set->paintPending));
   }
   uint32_t *dense = nullptr;
   TRY(pinned_buffer(ctx, 1, nPairs * 8 + 8, (void **)&dense));
@@ -870,6 +981,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   std::vector<FragDistBuf> fdPart(sk->fragdist ? sub.size() : 0);       // the fragment distribution records take the rows' way
   std::vector<HitBuf> hitPart(sk->hits ? sub.size() : 0);               // ... and so do the best-hit records
   std::vector<CiBuf> ciPart(sk->ci ? sub.size() : 0);                   // ... and the interval records
+  std::vector<PaintParts> paintPart(sk->paint ? sub.size() : 0);        // the paint records: a part per chunk, joined per sub-batch at the end
   for (size_t c = 0; c < sk->chunks.size(); c++) {
     TRY(ensure_chunk(sk, c));
     IndexChunk *ch = sk->chunks[c];
@@ -879,7 +991,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       TRY(map_stage(ctx, sk, ch, sb.v, &nCand));
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
       TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr,
-          sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr));
+          sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr, sk->paint ? &paintPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -931,6 +1043,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
           return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
         [](ani_ci_t &) {}, &sk->ciPending));
   }
+  for (size_t i = 0; i < paintPart.size(); i++) TRY(paint_join(paintPart[i], &sk->paintPending));
   return ANI_OK;
 }
 
@@ -1060,7 +1173,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
   const size_t nCh = sk->chunks.size();
   std::vector<std::vector<int32_t>> cFrag(nCh), cSeq(nCh), cStart(nCh); std::vector<std::vector<uint32_t>> cBits(nCh);
   std::vector<int32_t> fragQ;                        // several queries: fragment -> fs.genomeBase + its query
-  std::vector<int32_t> fragId;                       // best-hit records on: fragment -> its querySeqId as given
+  std::vector<int32_t> fragId;                       // best-hit or paint records on: fragment -> its querySeqId as given
   int32_t lastQ = -1, f = -1, q = 0;
   size_t chunkOfSeqHint = 0;
   for (size_t i = 0; i < n; i++) {
@@ -1068,7 +1181,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     if (a.querySeqId != lastQ || f < 0) {
       f++; lastQ = a.querySeqId;
       if (queryFragStart) { while (a.querySeqId >= queryFragStart[q + 1]) q++; fragQ.push_back(fs.genomeBase + q); }
-      if (sk->hits) fragId.push_back(a.querySeqId);
+      if (sk->hits || sk->paint) fragId.push_back(a.querySeqId);
     }
     size_t c = chunkOfSeqHint;
     while (c + 1 < nCh && a.refSeqId >= sk->chunks[c]->c0 + sk->chunks[c]->nContigs) c++;
@@ -1085,7 +1198,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   } else if (nF) HIP_TRY(hipMemsetAsync(ctx->fragGenome.p, 0, nF * 4, ctx->stream));
   fs.fragGenome = ctx->fragGenome.as<int32_t>();
-  if (sk->hits && nF) {
+  if ((sk->hits || sk->paint) && nF) {
     TRY(ctx->hitQSeq.ensure(nF * 4));
     HIP_TRY(hipMemcpyAsync(ctx->hitQSeq.p, fragId.data(), nF * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1103,12 +1216,17 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n, pt0 = sk->paintPending.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
   if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = h0; i < sk->hitPending.n; i++) sk->hitPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = ci0; i < sk->ciPending.n; i++) sk->ciPending.rec[i].refGenomeId -= sk->refIdBase;
+  if (sk->refIdBase) for (size_t i = pt0; i < sk->paintPending.n; i++) {
+    ani_paint_t &r = sk->paintPending.rec[i];
+    r.refGenomeId -= sk->refIdBase;
+    if (r.secondGenomeId >= 0) r.secondGenomeId -= sk->refIdBase;
+  }
   return ANI_OK;
 }
 
@@ -1510,6 +1628,76 @@ int ani_sketch_ci_end(ani_sketch *sk)
   if (!sk->ci) return fail(ANI_ERR_ARG, "ani_sketch_ci_end without ani_sketch_ci_begin");
   sk->ciPending.clear(); sk->ctx->ciStage.clear();
   sk->ci = false;
+  return ANI_OK;
+}
+
+// ---- the best reference of every query fragment (ani_abi.h: ani_sketch_paint_begin) ----
+int ani_sketch_paint_begin(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (sk->paint) return fail(ANI_ERR_ARG, "ani_sketch_paint_begin while the mode is on");
+  sk->paintPending.clear(); sk->ctx->paintStage.clear();
+  sk->paint = true;
+  return ANI_OK;
+}
+
+int ani_sketch_paint_take(ani_sketch *sk, ani_paint_t **rec, size_t *n)
+{
+  if (!sk || !rec || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->paint) return fail(ANI_ERR_ARG, "ani_sketch_paint_take without ani_sketch_paint_begin");
+  *rec = nullptr; *n = 0;
+  PaintBuf &pd = sk->paintPending;
+  if (pd.n == 0) { pd.clear(); return ANI_OK; }
+  *rec = pd.rec; *n = pd.n;                     // the buffer itself: ani_free releases it
+  pd.rec = nullptr; pd.n = pd.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_paint_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->paint) return fail(ANI_ERR_ARG, "ani_sketch_paint_end without ani_sketch_paint_begin");
+  ani_ctx *ctx = sk->ctx;
+  HIP_TRY(hipSetDevice(sk->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  sk->paintPending.clear(); ctx->paintStage.clear();
+  for (DevBuf *b : {&ctx->paintBest, &ctx->paintSecond, &ctx->paintGenomes, &ctx->paintWin, &ctx->paintFlags, &ctx->paintOff, &ctx->paintRec}) b->release();
+  sk->paint = false;
+  return ANI_OK;
+}
+
+// rule 6: a pure host function
+int ani_paint_merge(const ani_paint_t *a, size_t na, const ani_paint_t *b, size_t nb, ani_paint_t **out, size_t *n)
+{
+  if (!out || !n || (na && !a) || (nb && !b)) return fail(ANI_ERR_ARG, "null argument");
+  *out = nullptr; *n = 0;
+  auto before = [](const ani_paint_t &x, const ani_paint_t &y) {
+    return x.qryGenomeId < y.qryGenomeId || (x.qryGenomeId == y.qryGenomeId && x.querySeqId < y.querySeqId); };
+  for (size_t i = 1; i < na; i++) if (!before(a[i - 1], a[i])) return fail(ANI_ERR_ARG, "ani_paint_merge: the first list is not in (qryGenomeId, querySeqId) order at %zu", i);
+  for (size_t i = 1; i < nb; i++) if (!before(b[i - 1], b[i])) return fail(ANI_ERR_ARG, "ani_paint_merge: the second list is not in (qryGenomeId, querySeqId) order at %zu", i);
+  if (na + nb == 0) return ANI_OK;
+  if (na + nb > SIZE_MAX / sizeof(ani_paint_t)) return fail(ANI_ERR_NOMEM, "host allocation of paint records failed");
+  ani_paint_t *o = (ani_paint_t *)malloc((na + nb) * sizeof(ani_paint_t));
+  if (!o) return fail(ANI_ERR_NOMEM, "host allocation of %zu paint records failed", na + nb);
+  // rule 2 on (identity bits, genome id): does (xb, xg) come before (yb, yg)?
+  auto first = [](uint32_t xb, int32_t xg, uint32_t yb, int32_t yg) { return xb > yb || (xb == yb && xg < yg); };
+  auto idb = [](float v) { uint32_t u; memcpy(&u, &v, 4); return u; };
+  size_t i = 0, j = 0, m = 0;
+  while (i < na || j < nb) {
+    if (j >= nb || (i < na && before(a[i], b[j]))) { o[m++] = a[i++]; continue; }
+    if (i >= na || before(b[j], a[i])) { o[m++] = b[j++]; continue; }
+    const ani_paint_t &x = a[i++], &y = b[j++];
+    const bool xFirst = first(idb(x.identity), x.refGenomeId, idb(y.identity), y.refGenomeId);
+    const ani_paint_t &w = xFirst ? x : y, &l = xFirst ? y : x;      // the winner's record and the other's
+    ani_paint_t r = w;
+    r.genomes = x.genomes + y.genomes; r.reserved = 0;
+    // the second: the loser's first, or the winner's own second
+    r.secondGenomeId = l.refGenomeId; r.secondIdentity = l.identity;
+    if (w.secondGenomeId >= 0 && first(idb(w.secondIdentity), w.secondGenomeId, idb(l.identity), l.refGenomeId)) {
+      r.secondGenomeId = w.secondGenomeId; r.secondIdentity = w.secondIdentity; }
+    o[m++] = r;
+  }
+  *out = o; *n = m;
   return ANI_OK;
 }
 

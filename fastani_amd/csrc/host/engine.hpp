@@ -462,6 +462,14 @@ struct RecBuf {
 };
 using HitBuf = RecBuf<ani_hit_t>;
 using CiBuf = RecBuf<ani_ci_t>;
+// the per-fragment records of the paint mode (ani_sketch_paint_begin; kernels/paint.hpp).  PaintParts: the partial records of ONE
+// sub-batch, one part per index chunk (part k = rec[cut[k] .. cut[k + 1]), each in (query, querySeqId) order), until ani_paint_merge
+// joins them
+using PaintBuf = RecBuf<ani_paint_t>;
+struct PaintParts {
+  PaintBuf buf; std::vector<size_t> cut = std::vector<size_t>(1, 0);
+  void clear() { buf.clear(); cut.assign(1, 0); }
+};
 
 // =====================================================================================================
 struct ani_ctx {
@@ -551,6 +559,12 @@ struct ani_ctx {
   CiBuf ciStage;
   uint32_t ciPiece = 1u << 18;            // records per launch and copy, and 64 pool cells per record (env ANI_TEST_CI_PIECE, tests)
   uint32_t ciLdsCells = 2560 /* ani::kCiLdsCells */;    // cells of a pair kept in LDS (env ANI_TEST_CI_LDS_CELLS lowers it, tests)
+  // paint records (only while a sketch has them on): the per-fragment state of a (sub-batch, chunk) — best and second key, genome count,
+  // winning candidate: 24 bytes per fragment —, the flags and slots of the mapped fragments, one piece of records on the device, and the
+  // partial records reduce_stage has staged for the sub-batch's collect_rows, one part per chunk (query = index in the sub-batch)
+  DevBuf paintBest, paintSecond, paintGenomes, paintWin, paintFlags, paintOff, paintRec;
+  PaintParts paintStage;
+  uint32_t paintPiece = 1u << 22;         // records per launch and copy (env ANI_TEST_PAINT_PIECE, tests)
 };
 
 // One index over a contiguous run of reference genomes: < 2^31 minimizers, 32-bit indices, chunk-local seqIds.  A reference set
@@ -620,6 +634,11 @@ struct ani_sketch {
   // of the fragment distributions' records to `ciPending`, which ani_sketch_ci_take hands over
   bool ci = false; uint32_t ciMinIdBits = 0, ciMinFragments = 1, ciReplicates = 200, ciLevel = 950, ciSeed = 1;
   CiBuf ciPending;
+  // paint records (ani_sketch_paint_begin .. _end): reduce_stage makes a partial record per mapped fragment of every (sub-batch, chunk)
+  // while they are on; collect_rows gives them the rows' ids, ani_paint_merge joins the chunks' parts, and the joined records wait in
+  // `paintPending` for ani_sketch_paint_take
+  bool paint = false;
+  PaintBuf paintPending;
 };
 
 namespace anih {

@@ -50,6 +50,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <iomanip>
 #include <iostream>
 #include <memory>
 #include <mutex>
@@ -89,6 +90,7 @@ struct Options {
   bool fragDist = false;                               // --fragDist: the .fragdist file, the spread of the fragment identities behind every -o line
   std::vector<float> fragDistEdges;                    // --fragDistEdges: the class edges of its histograms (default_fragdist_edges)
   bool hits = false;                                   // --hits: the .hits file, the reciprocal best fragment hits behind every -o line
+  bool paint = false;                                  // --paint: the .paint and .paintsum files, every query fragment's best reference over all references
   float hitsMinANI = 0.0f; int hitsMinFragments = 1;   // --hitsMinANI, --hitsMinFragments: the pairs that get lines (ani_sketch_hits_begin's gate)
   bool ci = false;                                     // --ci: the .ci file, a bootstrap interval beside the ANI of every -o line
   int ciReplicates = 200, ciLevelPermille = 950; uint32_t ciSeed = 1;   // --ciReplicates, --ciLevel (percent), --ciSeed (ani_sketch_ci_begin)
@@ -119,7 +121,7 @@ struct Options {
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
-    "             [--hits] [--hitsMinANI <value>] [--hitsMinFragments <value>]\n"
+    "             [--hits] [--hitsMinANI <value>] [--hitsMinFragments <value>] [--paint]\n"
     "             [--ci] [--ciReplicates <value>] [--ciLevel <value>] [--ciSeed <value>] [--ciMinANI <value>] [--ciMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
@@ -196,6 +198,17 @@ struct Options {
     "                 per query contig; the two options below are the remedy for runs whose hits do not fit\n"
     "     --hitsMinANI <value>  only the pairs from this ANI on get lines (0 <= value <= 100) [default : 0, every line of the output]\n"
     "     --hitsMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
+    "     --paint  also write <output>.paint and <output>.paintsum: for every fragment of every query genome the reference it maps\n"
+    "                 to best over ALL references, the runner-up and the number of references it maps to (contamination and chimera\n"
+    "                 checks, transferred regions, painting plots, novel regions); works in every input mode --hits does, and with\n"
+    "                 --gpus.  <output>.paint, one line per fragment, queries in list order, fragments ascending: query, qStart, qEnd,\n"
+    "                 reference, identity, rStart, rEnd, genomes, second, secondIdentity (coordinates as in .hits; NA in the last seven\n"
+    "                 columns for a fragment that maps nowhere, NA for second and secondIdentity where one reference only is hit; at\n"
+    "                 equal identity the reference that comes first in the list).  <output>.paintsum, per query one line per reference\n"
+    "                 that is some fragment's best: query, reference, fragments, share, meanIdentity, alone (fragments that map to\n"
+    "                 this reference only), by fragments descending, and a last line query, NA, unmapped fragments, share, NA, NA.\n"
+    "                 Host memory: 40 bytes per mapped fragment until the files are written (about 6 GB for 90 000 genomes of 5 Mbp),\n"
+    "                 and 4 bytes per query contig\n"
     "     --ci  also write <output>.ci: a percentile bootstrap interval of every ANI value, resampled from the fragment identities it is\n"
     "           the mean of.  Line 1 is \"#replicates<TAB>B<TAB>level<TAB>L<TAB>seed<TAB>s\"; then per line of the output, in its order:\n"
     "           query, reference, ANI, low, high, fragments\n"
@@ -302,6 +315,7 @@ Options parse(int argc, char **argv)
     else if (a == "--fragDistMinANI") { o.fragDistMinANI = (float)atof(need(i)); fragDistMinANI = true;
       if (!(o.fragDistMinANI >= 0.0f && o.fragDistMinANI <= 100.0f)) { std::cerr << "ERROR, --fragDistMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hits") o.hits = true;
+    else if (a == "--paint") o.paint = true;
     else if (a == "--hitsMinANI") { o.hitsMinANI = (float)atof(need(i)); hitsMinANI = true;
       if (!(o.hitsMinANI >= 0.0f && o.hitsMinANI <= 100.0f)) { std::cerr << "ERROR, --hitsMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hitsMinFragments") { o.hitsMinFragments = atoi(need(i)); hitsMinFragments = true;
@@ -835,6 +849,63 @@ struct HitsTable {
 };
 HitsTable g_hits;
 
+// --paint: the per-fragment records (ani_sketch_paint_begin) of the queries over all references.  Begun and drained where the profile is.
+// What a sketch hands over covers its own references only: the ids become the reference list's indices, the winner's position becomes
+// the offset inside its genome while the sketch that knows the contigs is alive (62 bits, carried in refSeqId : refStartPos), and the
+// lists of the shards, blocks and splits are joined by ani_paint_merge before the files are written.
+struct PaintTable {
+  bool on = false;
+  struct List { ani_paint_t *rec; size_t n; };
+  std::vector<List> lists;                                 // each in (query, fragment) order, over disjoint references
+  void init(const Options &o) { on = o.paint; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_paint_begin(sk)) { std::cerr << "ERROR, ani_sketch_paint_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  static int64_t ref_start(const ani_paint_t &e) { return ((int64_t)e.refSeqId << 31) | (int64_t)e.refStartPos; }
+  // what the mapping calls left in `sk`: genome g of the sketch is reference refOf(g); the query ids are the run's own
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_paint_t *r = nullptr; size_t n = 0; const int32_t *cl = nullptr, *gcs = nullptr;
+    if (ani_sketch_paint_take(sk, &r, &n) || ani_sketch_tables(sk, &cl, &gcs)) { std::cerr << "ERROR, ani_sketch_paint_take: " << ani_last_error() << std::endl; exit(1); }
+    if (!n) return;
+    int32_t nContigs = 0;
+    if (ani_sketch_stats(sk, nullptr, nullptr, nullptr, &nContigs, nullptr)) { std::cerr << "ERROR, ani_sketch_stats: " << ani_last_error() << std::endl; exit(1); }
+    std::vector<int64_t> contigStart((size_t)nContigs + 1, 0);      // first base of every contig of the sketch, over all of them
+    for (int32_t c = 0; c < nContigs; c++) contigStart[(size_t)c + 1] = contigStart[(size_t)c] + cl[c];
+    bool ordered = true;
+    for (size_t i = 0; i < n; i++) {
+      ani_paint_t &e = r[i];
+      const int64_t off = contigStart[(size_t)e.refSeqId] - contigStart[(size_t)gcs[e.refGenomeId]] + e.refStartPos;
+      e.refSeqId = (int32_t)(off >> 31); e.refStartPos = (int32_t)(off & 0x7fffffff);
+      e.refGenomeId = (int32_t)refOf(e.refGenomeId);
+      if (e.secondGenomeId >= 0) e.secondGenomeId = (int32_t)refOf(e.secondGenomeId);
+      if (i && !(r[i - 1].qryGenomeId < e.qryGenomeId || (r[i - 1].qryGenomeId == e.qryGenomeId && r[i - 1].querySeqId < e.querySeqId))) ordered = false;
+    }
+    if (!ordered) std::sort(r, r + n, [](const ani_paint_t &x, const ani_paint_t &y) {
+        return x.qryGenomeId < y.qryGenomeId || (x.qryGenomeId == y.qryGenomeId && x.querySeqId < y.querySeqId); });
+    lists.push_back(List{r, n});
+  }
+  // every list joined into lists[0] (pairwise, so that a record is copied log2(lists) times)
+  void join()
+  {
+    while (lists.size() > 1) {
+      std::vector<List> next;
+      for (size_t i = 0; i + 1 < lists.size(); i += 2) {
+        List m{nullptr, 0};
+        if (ani_paint_merge(lists[i].rec, lists[i].n, lists[i + 1].rec, lists[i + 1].n, &m.rec, &m.n)) {
+          std::cerr << "ERROR, ani_paint_merge: " << ani_last_error() << std::endl; exit(1); }
+        ani_free(lists[i].rec); ani_free(lists[i + 1].rec);
+        next.push_back(m);
+      }
+      if (lists.size() & 1) next.push_back(lists.back());
+      lists.swap(next);
+    }
+  }
+};
+PaintTable g_paint;
+
 // --ci: the bootstrap intervals (ani_sketch_ci_begin) of the pairs, keyed by (query, reference) file index.  Begun and drained where the
 // profile is.
 struct CiTable {
@@ -1141,6 +1212,7 @@ struct Streaming {
     g_profile.take(shard[d].sk, ap.fragLen, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_fragdist.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_hits.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_paint.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_ci.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
   }
 
@@ -1236,7 +1308,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); }
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); g_paint.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1467,7 +1539,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk); g_paint.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1525,6 +1597,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     g_profile.take(sk, ap.fragLen, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });      // the split's genome g is reference refIdx[g]
     g_fragdist.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_hits.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
+    g_paint.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_ci.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
@@ -1664,6 +1737,59 @@ void write_hits(const Options &o, const ani_params_t &ap, const std::vector<ani_
             << h.refStart << "\t" << h.refStart + ap.fragLen - 1 << "\tNA\tNA\n";
     }
   }
+}
+
+// ---- .paint: one line per fragment of every query genome, queries in list order, fragments ascending: query, qStart, qEnd, reference,
+// identity, rStart, rEnd, genomes, second, secondIdentity (coordinates as in .hits; NA where the fragment has no record, and for a
+// second that does not exist).  .paintsum: per query one line per reference that is some fragment's best — query, reference, fragments,
+// share of the query's fragments, the mean identity (exact: from the sum of llrint(identity * 2^20)), alone = those of them that map to
+// this reference only — by fragments descending, then list order; and a last line per query for the fragments without a record.
+void write_paint(const Options &o, const ani_params_t &ap, GenomeLengths &lengths)
+{
+  g_paint.join();
+  const ani_paint_t *rec = g_paint.lists.empty() ? nullptr : g_paint.lists[0].rec;
+  const size_t n = g_paint.lists.empty() ? 0 : g_paint.lists[0].n;
+  BufferedFile f(o.out + ".paint"), s(o.out + ".paintsum");
+  s.out << std::fixed;
+  struct Sum { size_t ref; uint64_t fragments, fix, alone; };
+  size_t at = 0;
+  for (size_t q = 0; q < o.queries.size(); q++) {
+    // the fragment ids of the query as fragment_offsets walks them; a contig shorter than a fragment takes an id and has no fragment
+    const std::vector<int32_t> &lens = lengths.contigs_of(o.queries[q]);
+    while (at < n && rec[at].qryGenomeId < (int32_t)q) at++;
+    std::unordered_map<size_t, size_t> slot; std::vector<Sum> sums;
+    uint64_t total = 0, unmapped = 0; int64_t run = 0; int32_t id = 0;
+    for (int32_t len : lens) {
+      if (len < ap.windowSize || len < ap.kmerSize || len < ap.fragLen) { id++; run += len; continue; }
+      const int fc = len / ap.fragLen;
+      for (int i = 0; i < fc; i++, id++) {
+        const int64_t qs = run;
+        run += (i != fc - 1) ? ap.fragLen : ap.fragLen + len % ap.fragLen;
+        total++;
+        while (at < n && rec[at].qryGenomeId == (int32_t)q && rec[at].querySeqId < id) at++;
+        f.out << o.queries[q] << "\t" << qs << "\t" << qs + ap.fragLen - 1;
+        if (at >= n || rec[at].qryGenomeId != (int32_t)q || rec[at].querySeqId != id) { f.out << "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n"; unmapped++; continue; }
+        const ani_paint_t &e = rec[at];
+        const int64_t rs = PaintTable::ref_start(e);
+        f.out << "\t" << o.refs[(size_t)e.refGenomeId] << "\t" << e.identity << "\t" << rs << "\t" << rs + ap.fragLen - 1 << "\t" << e.genomes;
+        if (e.secondGenomeId >= 0) f.out << "\t" << o.refs[(size_t)e.secondGenomeId] << "\t" << e.secondIdentity << "\n";
+        else f.out << "\tNA\tNA\n";
+        auto it = slot.find((size_t)e.refGenomeId);
+        if (it == slot.end()) { it = slot.emplace((size_t)e.refGenomeId, sums.size()).first; sums.push_back(Sum{(size_t)e.refGenomeId, 0, 0, 0}); }
+        Sum &x = sums[it->second];
+        x.fragments++; x.fix += (uint64_t)llrint((double)e.identity * 1048576.0); x.alone += e.genomes == 1;
+      }
+    }
+    std::sort(sums.begin(), sums.end(), [](const Sum &a, const Sum &b) { return a.fragments > b.fragments || (a.fragments == b.fragments && a.ref < b.ref); });
+    const double den = total ? (double)total : 1.0;
+    for (const Sum &x : sums) {
+      s.out << o.queries[q] << "\t" << o.refs[x.ref] << "\t" << x.fragments << "\t" << std::setprecision(4) << (double)x.fragments / den << "\t";
+      s.out << std::defaultfloat << std::setprecision(6) << (float)((double)x.fix / 1048576.0 / (double)x.fragments) << std::fixed << "\t" << x.alone << "\n";
+    }
+    s.out << o.queries[q] << "\tNA\t" << unmapped << "\t" << std::setprecision(4) << (double)unmapped / den << "\tNA\tNA\n";
+  }
+  for (auto &l : g_paint.lists) ani_free(l.rec);
+  g_paint.lists.clear();
 }
 
 // The cells of the .matrix, shared by the .clusters writer so that the two files never disagree: genomes numbered queries first, then
@@ -2175,10 +2301,10 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o);
+  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o); g_paint.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
-  lengths.keepContigs = o.hits;
+  lengths.keepContigs = o.hits || o.paint;
   Startup su(o, m, ap);
   std::cerr << "INFO [thread 0], skch::Sketch::build, window size for minimizer sampling  = " << ap.windowSize << std::endl;
   std::cerr << "INFO [thread 0], skch::main, Count of threads executing parallel_for : " << (o.sanityCheck ? o.threads : (int)su.dev.size()) << std::endl;
@@ -2199,6 +2325,7 @@ int main(int argc, char **argv)
   if (o.fragDist) write_fragdist(o, res.rows, trusted);
   if (o.hits) write_hits(o, ap, res.rows, trusted, lengths);
   if (o.ci) write_ci(o, res.rows, trusted);
+  if (o.paint) write_paint(o, ap, lengths);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

@@ -461,6 +461,41 @@ int ani_sketch_ci_begin(ani_sketch *sk, float minIdentity, int32_t minFragments,
 int ani_sketch_ci_take(ani_sketch *sk, ani_ci_t **rec, size_t *n);
 int ani_sketch_ci_end(ani_sketch *sk);
 
+/* ---- the best reference of every query fragment over the whole reference set ("genome painting"; no counterpart in the reference, whose
+ * outputs are all per pair of genomes).  Between begin and end every call that reduces against the sketch (the
+ * calls of the profile's rule 5; ani_map_query adds nothing) appends one record per mapped query fragment to a list on the host, which
+ * take hands over.  The records are per fragment, not per pair, and know no gate.  Everything is integer or bit pattern.
+ *  1. 1-way winner: rule 1 of the hits.  For a fragment f and a reference genome g it is the maximum under (nucIdentity bits, refSeqId,
+ *     refStartPos) over f's mappings to g with identity bits != 0; a genome without such a mapping has no winner.
+ *  2. Order of genomes for a fragment: the genome whose winner has the higher identity bits comes first; at equal bits the SMALLER
+ *     refGenomeId, with the ids as the records carry them (the "preferred genomes first" convention of ani_cluster_greedy).
+ *  3. Record.  One record per fragment that has at least one winner, none for a fragment that has none.  qryGenomeId, querySeqId: the
+ *     fragment (ids as rule 4 of the hits gives them: firstQueryId, the query ids of a merged set; querySeqId as ani_map_query reports
+ *     it, for ani_compute_cgi and ani_reduce_check the mapping's own — not dense, up to 2^31 - 1).  refGenomeId, refSeqId, refStartPos,
+ *     identity: the first genome under rule 2 (ani_sketch_set_ref_id_base included) and its 1-way winner, bit for bit; refSeqId is the
+ *     sketch's own set-global contig id.  secondGenomeId, secondIdentity: the second genome under rule 2 and the identity of its
+ *     winner, -1 and 0.0f where one genome only has a winner.  genomes: the number of reference genomes with a winner.  reserved = 0.
+ *  4. Order.  The records of one call follow the call's query order, then querySeqId ascending; calls follow each other in call order.
+ *  5. Independence.  Nothing depends on schedule, sub-batch size, index chunking, residency (resident, chunked, streamed) or piece size.
+ *     Rows are untouched; the profile, the distributions, the hits and the intervals can be on beside it and do not see it.
+ *  6. Merge.  ani_paint_merge(a, na, b, nb, &out, &n): a and b are record lists over DISJOINT sets of reference genomes, each ordered by
+ *     (qryGenomeId, querySeqId) ascending; out is the list over the union, in that order: a fragment in one list only is copied; for a
+ *     fragment in both, genomes is the sum, first and second are the top two under rule 2 of the up to four (genome, identity) entries
+ *     the two records hold, and refSeqId and refStartPos travel with the first.  out[n] is released with ani_free (n = 0: NULL).  A pure
+ *     host function: no context.  The engine joins the partial records of the index chunks of a set with it (their genomes are
+ *     disjoint); callers join shards, blocks and splits of a reference set, after giving the records their final ids.
+ * begin starts; take hands over everything appended since begin or the last take and empties the list: rec[n], released with ani_free;
+ * with n = 0 it comes back NULL.  40 bytes per record of host memory until taken, 24 bytes per fragment of a sub-batch on the device
+ * while the mode is on.  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null pointer, a begin while the mode is on, take
+ * or end without a begin, a list out of order (merge).  ANI_ERR_NOMEM: host or device memory.  ANI_ERR_LIMIT: more than 2^32 - 16
+ * records in one (sub-batch, index chunk).  After a call that failed while reducing, the pending list is unspecified until end. */
+typedef struct { int32_t qryGenomeId, querySeqId, refGenomeId, refSeqId, refStartPos; float identity;
+                 int32_t secondGenomeId; float secondIdentity; uint32_t genomes, reserved; } ani_paint_t;   /* 40 bytes */
+int ani_sketch_paint_begin(ani_sketch *sk);
+int ani_sketch_paint_take(ani_sketch *sk, ani_paint_t **rec, size_t *n);
+int ani_sketch_paint_end(ani_sketch *sk);
+int ani_paint_merge(const ani_paint_t *a, size_t na, const ani_paint_t *b, size_t nb, ani_paint_t **out, size_t *n);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
