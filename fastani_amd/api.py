@@ -49,6 +49,11 @@ CI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4
                   ("highSum", "<u8"), ("low", "<f4"), ("high", "<f4")])
 PAINT_DT = np.dtype([("qryGenomeId", "<i4"), ("querySeqId", "<i4"), ("refGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("identity", "<f4"),
                      ("secondGenomeId", "<i4"), ("secondIdentity", "<f4"), ("genomes", "<u4"), ("reserved", "<u4")])
+SYNTENY_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("forward", "<u4"), ("reverse", "<u4"), ("breaks", "<u4"),
+                       ("contigBorders", "<u4"), ("blocks", "<u4"), ("reverseBlocks", "<u4"), ("reverseHits", "<u4"), ("largestBlock", "<u4"),
+                       ("singletons", "<u4")])
+SYNBLOCK_DT = np.dtype([("refSeqId", "<i4"), ("refStartFirst", "<i4"), ("refStartLast", "<i4"), ("qSeqFirst", "<i4"), ("qSeqLast", "<i4"),
+                        ("hits", "<u4"), ("idSum", "<u8")])
 
 ANI_SEQ_HOST_ASCII = 0
 ANI_SEQ_DEVICE_PACKED2 = 1
@@ -158,6 +163,9 @@ def _bind(lib):
         "ani_sketch_paint_begin": (C.c_int, [vp]),
         "ani_sketch_paint_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_paint_end": (C.c_int, [vp]),
+        "ani_sketch_synteny_begin": (C.c_int, [vp, C.c_float, C.c_int32]),
+        "ani_sketch_synteny_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_synteny_end": (C.c_int, [vp]),
         "ani_paint_merge": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_synth_packed": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]),
         "ani_synth_packed_clusters": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
@@ -1039,6 +1047,22 @@ class Sketch:
 
     def paint_end(self):
         self.e._chk(self.e.lib.ani_sketch_paint_end(self.h))
+
+    def synteny_begin(self, min_identity=0.0, min_fragments=1):
+        """start (or restart) the synteny records: every mapping call that reduces against this sketch appends, for every pair whose row
+        has countSeq >= min_fragments and identity >= min_identity, one pair record (adjacency classes, blocks, reversed blocks) and one
+        record per collinear block of its best hits (ani_sketch_synteny_begin)"""
+        self.e._chk(self.e.lib.ani_sketch_synteny_begin(self.h, float(min_identity), int(min_fragments)))
+
+    def synteny_take(self):
+        """-> (SYNTENY_DT[nPairs], SYNBLOCK_DT[nBlocks]): the records appended since synteny_begin or the last take, pairs in row order,
+        the blocks in the same pair order and per pair in bin order, pair["blocks"] of them; empties both lists"""
+        pp, n, bp, m = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_synteny_take(self.h, C.byref(pp), C.byref(n), C.byref(bp), C.byref(m)))
+        return self.e._take(pp, n.value, SYNTENY_DT), self.e._take(bp, m.value, SYNBLOCK_DT)
+
+    def synteny_end(self):
+        self.e._chk(self.e.lib.ani_sketch_synteny_end(self.h))
 
     def profile_layout(self):
         """-> (contig_bin_start int64[nContigs + 1], genome_bin_start int64[nGenomes + 1]): the first set-global bin of every contig and

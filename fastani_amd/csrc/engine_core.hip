@@ -165,6 +165,8 @@ int ani_init(int device, ani_ctx **out)
   if (const char *ev = getenv("ANI_TEST_FRAGDIST_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->fragDistPiece = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_HITS_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->hitsPiece = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_PAINT_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->paintPiece = (uint32_t)v; }
+  if (const char *ev = getenv("ANI_TEST_SYNTENY_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->synPiece = (uint32_t)v; }
+  if (const char *ev = getenv("ANI_TEST_SYNTENY_LDS_HITS")) { const long long v = atoll(ev); if (v >= 1 && v <= 2048 /* ani::kSynLdsHits */) c->synLdsHits = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CI_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->ciPiece = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CI_LDS_CELLS")) { const long long v = atoll(ev); if (v >= 1 && v <= 2560 /* ani::kCiLdsCells */) c->ciLdsCells = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CAND_POOL_MIN")) { const long long v = atoll(ev); if (v >= 1) c->candPoolMin = (uint64_t)v; }
@@ -201,7 +203,9 @@ void ani_shutdown(ani_ctx *c)
                     &c->fdFlags, &c->fdOff, &c->fdList, &c->fdRec, &c->fdHist,
                     &c->hitOwner, &c->hitFlags, &c->hitOff, &c->hitList, &c->hitCount, &c->hitRecOff, &c->hitRec, &c->hitQSeq,
                     &c->ciFlags, &c->ciOff, &c->ciList, &c->ciPoolCells, &c->ciPoolOff, &c->ciPool, &c->ciRec,
-                    &c->paintBest, &c->paintSecond, &c->paintGenomes, &c->paintWin, &c->paintFlags, &c->paintOff, &c->paintRec};
+                    &c->paintBest, &c->paintSecond, &c->paintGenomes, &c->paintWin, &c->paintFlags, &c->paintOff, &c->paintRec,
+                    &c->synFlags, &c->synOff, &c->synList, &c->synCount, &c->synRecOff, &c->synPoolUnits, &c->synPoolOff, &c->synPool, &c->synRec,
+                    &c->synBlkPool, &c->synBlkCount, &c->synBlkOff, &c->synBlk};
   for (DevBuf *b : bufs) b->release();
   for (hipEvent_t e : c->timerEvents) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; i++) { if (c->evSimA[i]) (void)hipEventDestroy(c->evSimA[i]); if (c->evSetDone[i]) (void)hipEventDestroy(c->evSetDone[i]);

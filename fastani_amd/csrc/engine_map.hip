@@ -1,7 +1,7 @@
 // engine_map.hip — mapping and reduction: L1 seed lookup + candidate regions, L2 sliding MinHash, identity filter
 // (≙ skch::Map, src/map/include/computeMap.hpp:112-545) and the ANI reducer (≙ cgi::computeCGI,
 // src/cgi/include/computeCoreIdentity.hpp:166-298), for one query genome or fused for whole batches / kept fragment sets, with the
-// record modes of the reducer (profile, fragment distributions, best hits, bootstrap intervals).  What works on the finished rows
+// record modes of the reducer (profile, fragment distributions, best hits, bootstrap intervals, paint, synteny).  What works on the finished rows
 // (clustering, trees) is engine_graph.hip; the whole-genome sketch estimate is engine_sig.hip.
 #include <atomic>
 #include <thread>
@@ -13,6 +13,7 @@
 #include "kernels/fragdist.hpp"
 #include "kernels/ci.hpp"
 #include "kernels/hits.hpp"
+#include "kernels/synteny.hpp"
 #include "kernels/paint.hpp"
 
 namespace anih {
@@ -783,6 +784,122 @@ static int paint_join(PaintParts &parts, PaintBuf *out)
   return ANI_OK;
 }
 
+// The synteny records of one (sub-batch, index chunk) (kernels/synteny.hpp): gate -> flags -> scan, the hits' owner
+// -> claim passes over the candidates under THIS mode's gate (into ctx->hitOwner: hits_stage, if on, has finished with it on this stream
+// and has waited for its last copy), the list with the pairs' hit counts and pool units, two scans for the hit and pool offsets, then
+// piece by piece — at most synPiece pairs, 2^22 hits and 2^24 pool units per piece; a piece ends at a pair border and a larger pair is a
+// piece of its own — k_syn_pairs, a scan over the piece's block counts, k_syn_compact, and both record lists through page-locked memory
+// into ctx->synStage, where collect_rows finds them.  Only while the sketch has the mode on.
+static int synteny_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const OneWayArgs &wa, const PairArgs &pa, const FragSet &fs)
+{
+  const size_t nPairs = (size_t)pa.nQuery * (size_t)sk->nGenomes, nBins = pa.binsPerQuery * (size_t)pa.nQuery;
+  if (nPairs == 0 || wa.nCand == 0 || nBins == 0) return ANI_OK;
+  if (!fs.fragQSeq) return fail(ANI_ERR_ARG, "synteny records need the fragments' querySeqId");
+  TRY(ctx->hitOwner.ensure(nBins * 4));
+  SynArgs sa;
+  HitsArgs &ha = sa.h;
+  ha.w = wa; ha.fragQSeq = fs.fragQSeq; ha.nQuery = pa.nQuery; ha.nRefGenomes = sk->nGenomes; ha.genomeBinStart = sk->genomeBinStart;
+  ha.pairCount = pa.pairCount; ha.pairIdentity = pa.pairIdentity; ha.outStride = pa.outStride; ha.outCol0 = pa.outCol0;
+  ha.minIdBits = set->synMinIdBits; ha.minFragments = set->synMinFragments; ha.genomeBase = sk->g0; ha.seqBase = sk->c0;
+  ha.owner = ctx->hitOwner.as<uint32_t>();
+  sa.ldsHits = std::min<uint32_t>(ctx->synLdsHits, (uint32_t)kSynLdsHits);
+  TRY(ctx->synFlags.ensure(nPairs * 4)); TRY(ctx->synOff.ensure(nPairs * 4));
+  hipLaunchKernelGGL(k_hits_flags, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ha, ctx->synFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t listed = 0, total = 0, poolTotal = 0;
+  TRY(device_scan(ctx, ctx->synFlags.as<int32_t>(), ctx->synOff.as<uint32_t>(), (uint32_t)nPairs, &listed));
+  if (listed == 0) return ANI_OK;
+  HIP_TRY(hipMemsetAsync(ctx->hitOwner.p, 0, nBins * 4, ctx->stream));
+  hipLaunchKernelGGL(k_hits_owner, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, ha);
+  hipLaunchKernelGGL(k_hits_claim, dim3(grid_for((size_t)wa.nCand, kTPB)), dim3(kTPB), 0, ctx->stream, ha);
+  const size_t nL = (size_t)listed;
+  TRY(ctx->synList.ensure(nL * 4)); TRY(ctx->synCount.ensure(nL * 4)); TRY(ctx->synRecOff.ensure(nL * 4));
+  TRY(ctx->synPoolUnits.ensure(nL * 4)); TRY(ctx->synPoolOff.ensure(nL * 4));
+  hipLaunchKernelGGL(k_syn_list, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, sa, (const int32_t *)ctx->synFlags.as<int32_t>(),
+                     (const uint32_t *)ctx->synOff.as<uint32_t>(), ctx->synList.as<uint32_t>(), ctx->synCount.as<int32_t>(), ctx->synPoolUnits.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  // (every hit is a candidate of its own, so the sum stays below 2^31, and a pair has at most as many blocks; the limit is the ABI's)
+  TRY(device_scan(ctx, ctx->synCount.as<int32_t>(), ctx->synRecOff.as<uint32_t>(), (uint32_t)listed, &total, 0xfffffff0ull));
+  if (total == 0) return ANI_OK;
+  TRY(device_scan(ctx, ctx->synPoolUnits.as<int32_t>(), ctx->synPoolOff.as<uint32_t>(), (uint32_t)listed, &poolTotal));
+  std::vector<uint32_t> recOff(nL + 1), poolOff(nL + 1, 0);
+  HIP_TRY(hipMemcpyAsync(recOff.data(), ctx->synRecOff.p, nL * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (poolTotal) HIP_TRY(hipMemcpyAsync(poolOff.data(), ctx->synPoolOff.p, nL * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  recOff[nL] = (uint32_t)total; poolOff[nL] = (uint32_t)poolTotal;
+  SynBufs &st = ctx->synStage;
+  if (!st.pairs.reserve(nL)) return fail(ANI_ERR_NOMEM, "host allocation of %zu synteny records failed", nL);
+  static_assert(sizeof(SynRec) == sizeof(ani_synteny_t) && sizeof(SynBlock) == sizeof(ani_synblock_t), "the device records are the ABI's");
+  const uint64_t hitsPiece = 1ull << 22, poolPiece = 1ull << 24;
+  for (size_t a = 0; a < nL;) {
+    size_t b = a + 1;
+    while (b < nL && b - a < ctx->synPiece && (uint64_t)recOff[b + 1] - recOff[a] <= hitsPiece && (uint64_t)poolOff[b + 1] - poolOff[a] <= poolPiece) b++;
+    const size_t n = b - a, hits = recOff[b] - recOff[a], units = poolOff[b] - poolOff[a];
+    TRY(ctx->synRec.ensure(n * sizeof(SynRec))); TRY(ctx->synBlkPool.ensure(hits * sizeof(SynBlock)));
+    TRY(ctx->synBlkCount.ensure(n * 4)); TRY(ctx->synBlkOff.ensure(n * 4));
+    TRY(ctx->synPool.ensure((units ? units : 1) * 8));          // (the stream is idle: the last piece has been copied)
+    hipLaunchKernelGGL(k_syn_pairs, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, sa, (const uint32_t *)ctx->synList.as<uint32_t>(),
+                       (const uint32_t *)ctx->synRecOff.as<uint32_t>(), (const uint32_t *)ctx->synPoolOff.as<uint32_t>(), (uint32_t)a, (uint32_t)n,
+                       recOff[a], poolOff[a], ctx->synPool.as<unsigned long long>(), ctx->synRec.as<SynRec>(), ctx->synBlkPool.as<SynBlock>(),
+                       ctx->synBlkCount.as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    uint64_t nBlk = 0;
+    TRY(device_scan(ctx, ctx->synBlkCount.as<int32_t>(), ctx->synBlkOff.as<uint32_t>(), (uint32_t)n, &nBlk, 0xfffffff0ull));
+    if (nBlk == 0 || nBlk > hits) return fail(ANI_ERR_DEVICE, "synteny: %llu blocks from %zu hits", (unsigned long long)nBlk, hits);
+    TRY(ctx->synBlk.ensure((size_t)nBlk * sizeof(SynBlock)));
+    hipLaunchKernelGGL(k_syn_compact, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, (const uint32_t *)ctx->synRecOff.as<uint32_t>(), (uint32_t)a,
+                       (uint32_t)n, recOff[a], (const int32_t *)ctx->synBlkCount.as<int32_t>(), (const uint32_t *)ctx->synBlkOff.as<uint32_t>(),
+                       (const SynBlock *)ctx->synBlkPool.as<SynBlock>(), ctx->synBlk.as<SynBlock>());
+    HIP_TRY(hipGetLastError());
+    uint8_t *host = nullptr;
+    const size_t recBytes = n * sizeof(SynRec), blkBytes = (size_t)nBlk * sizeof(SynBlock);
+    TRY(pinned_buffer(ctx, 1, recBytes + blkBytes, (void **)&host));
+    HIP_TRY(hipMemcpyAsync(host, ctx->synRec.p, recBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(host + recBytes, ctx->synBlk.p, blkBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!st.blocks.reserve((size_t)nBlk)) return fail(ANI_ERR_NOMEM, "host allocation of %llu synteny block records failed", (unsigned long long)nBlk);
+    memcpy(st.pairs.rec + st.pairs.n, host, recBytes);
+    memcpy(st.blocks.rec + st.blocks.n, host + recBytes, blkBytes);
+    st.pairs.n += n; st.blocks.n += (size_t)nBlk;
+    a = b;
+  }
+  return ANI_OK;
+}
+
+// The staged synteny records of a sub-batch (`in`: chunk by chunk, per chunk pairs in (query, reference) order, the blocks in the pairs'
+// order) in (query, reference) order, appended to `out` with the ids `patch` gives the pairs: hits_distribute for two lists that stay
+// aligned — the pairs are distributed stably by the query's slot, and every pair takes its `blocks` block records with it.
+template <class SlotOf, class Patch>
+static int syn_distribute(SynBufs &in, size_t nq, bool ordered, SlotOf slot_of, Patch patch, SynBufs *out)
+{
+  const size_t n = in.pairs.n, nb = in.blocks.n;
+  if (n == 0) { in.clear(); return ANI_OK; }
+  const size_t at = out->pairs.n, atB = out->blocks.n;
+  if (ordered && at == 0 && atB == 0) { out->pairs.swap(in.pairs); out->blocks.swap(in.blocks); }
+  else {
+    if (!out->pairs.reserve(n) || !out->blocks.reserve(nb)) return fail(ANI_ERR_NOMEM, "host allocation of %zu synteny records failed", n + nb);
+    if (ordered) { memcpy(out->pairs.rec + at, in.pairs.rec, n * sizeof(ani_synteny_t)); memcpy(out->blocks.rec + atB, in.blocks.rec, nb * sizeof(ani_synblock_t)); }
+    else {
+      std::vector<size_t> start(nq + 1, 0), to(n), blkTo(n + 1, 0);
+      for (size_t r = 0; r < n; r++) start[slot_of(in.pairs.rec[r]) + 1]++;
+      for (size_t q = 0; q < nq; q++) start[q + 1] += start[q];
+      for (size_t r = 0; r < n; r++) { to[r] = start[slot_of(in.pairs.rec[r])]++; blkTo[to[r] + 1] = in.pairs.rec[r].blocks; }
+      for (size_t r = 0; r < n; r++) blkTo[r + 1] += blkTo[r];                 // by destination: where the pair's blocks begin
+      size_t from = 0;
+      for (size_t r = 0; r < n; r++) {
+        const size_t k = in.pairs.rec[r].blocks;
+        out->pairs.rec[at + to[r]] = in.pairs.rec[r];
+        memcpy(out->blocks.rec + atB + blkTo[to[r]], in.blocks.rec + from, k * sizeof(ani_synblock_t));
+        from += k;
+      }
+    }
+    out->pairs.n = at + n; out->blocks.n = atB + nb;
+  }
+  for (size_t r = at; r < at + n; r++) patch(out->pairs.rec[r]);
+  in.clear();
+  return ANI_OK;
+}
+
 // 1-way / 2-way / mean (computeCoreIdentity.hpp:214-297) for the candidates map_stage left in the context's buffers, against one
 // index chunk; the (count, identity) results go to the chunk's column block of the dense [nQuery][nRefGenomes] table in ctx->rows.
 // `compact`: the table holds this chunk's genomes only ([nQuery][chunk genomes]; a streamed set is reduced and read back chunk by chunk)
@@ -839,6 +956,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(paint_stage(ctx, sk, a, fs));
   }
+  if (set->synteny) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(synteny_stage(ctx, set, sk, a, pa, fs));
+  }
   }
   HIP_TRY(e1); HIP_TRY(hipGetLastError());
   return ANI_OK;
@@ -848,9 +969,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 // (`block`: the table is the compact one of that chunk — reference genome = block->g0 + column)
 // (fdOut, hitOut, ciOut: where the sub-batch's fragment distribution, best-hit and interval records go while those modes are on —
 // default: the sketch's pending lists; paintOut: where the chunk's part of the paint records waits for the sub-batch's other chunks —
-// default: this call has seen every chunk, the parts are joined into the sketch's pending list)
+// default: this call has seen every chunk, the parts are joined into the sketch's pending list; synOut: as hitOut, for the synteny records)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
-    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr, PaintParts *paintOut = nullptr)
+    const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr, PaintParts *paintOut = nullptr,
+    SynBufs *synOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
@@ -886,6 +1008,13 @@ int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuer
           r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base;
           if (r.secondGenomeId >= 0) r.secondGenomeId += base; }, to));
     if (!paintOut) TRY(paint_join(own, &set->paintPending));
+  }
+  if (set->synteny) {
+    const int32_t base = set->refIdBase;
+    TRY(syn_distribute(ctx->synStage, (size_t)nQuery, block || set->chunks.size() == 1,
+        [](const ani_synteny_t &r) { return (size_t)r.qryGenomeId; },
+        [&](ani_synteny_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
+        synOut ? synOut : &set->synPending));
   }
   uint32_t *dense = nullptr;
   TRY(pinned_buffer(ctx, 1, nPairs * 8 + 8, (void **)&dense));
@@ -982,6 +1111,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   std::vector<HitBuf> hitPart(sk->hits ? sub.size() : 0);               // ... and so do the best-hit records
   std::vector<CiBuf> ciPart(sk->ci ? sub.size() : 0);                   // ... and the interval records
   std::vector<PaintParts> paintPart(sk->paint ? sub.size() : 0);        // the paint records: a part per chunk, joined per sub-batch at the end
+  std::vector<SynBufs> synPart(sk->synteny ? sub.size() : 0);           // the synteny records take the best-hit records' way
   for (size_t c = 0; c < sk->chunks.size(); c++) {
     TRY(ensure_chunk(sk, c));
     IndexChunk *ch = sk->chunks[c];
@@ -991,7 +1121,8 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       TRY(map_stage(ctx, sk, ch, sb.v, &nCand));
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
       TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr,
-          sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr, sk->paint ? &paintPart[i] : nullptr));
+          sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr, sk->paint ? &paintPart[i] : nullptr,
+          sk->synteny ? &synPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -1044,6 +1175,13 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
         [](ani_ci_t &) {}, &sk->ciPending));
   }
   for (size_t i = 0; i < paintPart.size(); i++) TRY(paint_join(paintPart[i], &sk->paintPending));
+  for (size_t i = 0; i < synPart.size(); i++) {
+    const int32_t q0 = sub[i].firstQueryId, nq = sub[i].g1 - sub[i].g0;
+    const int32_t *ids = sub[i].queryIds;
+    TRY(syn_distribute(synPart[i], (size_t)nq, sk->chunks.size() == 1, [&](const ani_synteny_t &r) {
+          return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
+        [](ani_synteny_t &) {}, &sk->synPending));
+  }
   return ANI_OK;
 }
 
@@ -1173,7 +1311,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
   const size_t nCh = sk->chunks.size();
   std::vector<std::vector<int32_t>> cFrag(nCh), cSeq(nCh), cStart(nCh); std::vector<std::vector<uint32_t>> cBits(nCh);
   std::vector<int32_t> fragQ;                        // several queries: fragment -> fs.genomeBase + its query
-  std::vector<int32_t> fragId;                       // best-hit or paint records on: fragment -> its querySeqId as given
+  std::vector<int32_t> fragId;                       // best-hit, paint or synteny records on: fragment -> its querySeqId as given
   int32_t lastQ = -1, f = -1, q = 0;
   size_t chunkOfSeqHint = 0;
   for (size_t i = 0; i < n; i++) {
@@ -1181,7 +1319,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     if (a.querySeqId != lastQ || f < 0) {
       f++; lastQ = a.querySeqId;
       if (queryFragStart) { while (a.querySeqId >= queryFragStart[q + 1]) q++; fragQ.push_back(fs.genomeBase + q); }
-      if (sk->hits || sk->paint) fragId.push_back(a.querySeqId);
+      if (sk->hits || sk->paint || sk->synteny) fragId.push_back(a.querySeqId);
     }
     size_t c = chunkOfSeqHint;
     while (c + 1 < nCh && a.refSeqId >= sk->chunks[c]->c0 + sk->chunks[c]->nContigs) c++;
@@ -1198,7 +1336,7 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   } else if (nF) HIP_TRY(hipMemsetAsync(ctx->fragGenome.p, 0, nF * 4, ctx->stream));
   fs.fragGenome = ctx->fragGenome.as<int32_t>();
-  if ((sk->hits || sk->paint) && nF) {
+  if ((sk->hits || sk->paint || sk->synteny) && nF) {
     TRY(ctx->hitQSeq.ensure(nF * 4));
     HIP_TRY(hipMemcpyAsync(ctx->hitQSeq.p, fragId.data(), nF * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1216,12 +1354,13 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n, pt0 = sk->paintPending.n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n, pt0 = sk->paintPending.n, sy0 = sk->synPending.pairs.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
   if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = h0; i < sk->hitPending.n; i++) sk->hitPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = ci0; i < sk->ciPending.n; i++) sk->ciPending.rec[i].refGenomeId -= sk->refIdBase;
+  if (sk->refIdBase) for (size_t i = sy0; i < sk->synPending.pairs.n; i++) sk->synPending.pairs.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = pt0; i < sk->paintPending.n; i++) {
     ani_paint_t &r = sk->paintPending.rec[i];
     r.refGenomeId -= sk->refIdBase;
@@ -1663,6 +1802,44 @@ int ani_sketch_paint_end(ani_sketch *sk)
   sk->paintPending.clear(); ctx->paintStage.clear();
   for (DevBuf *b : {&ctx->paintBest, &ctx->paintSecond, &ctx->paintGenomes, &ctx->paintWin, &ctx->paintFlags, &ctx->paintOff, &ctx->paintRec}) b->release();
   sk->paint = false;
+  return ANI_OK;
+}
+
+// ---- collinear blocks of the best hits (ani_abi.h: ani_sketch_synteny_begin) ----
+int ani_sketch_synteny_begin(ani_sketch *sk, float minIdentity, int32_t minFragments)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  memcpy(&sk->synMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->synMinIdBits = 0;                   // -0.0 counts as 0
+  sk->synMinFragments = (uint32_t)minFragments;
+  sk->synPending.clear(); sk->ctx->synStage.clear();
+  sk->synteny = true;
+  return ANI_OK;
+}
+
+int ani_sketch_synteny_take(ani_sketch *sk, ani_synteny_t **pairs, size_t *nPairs, ani_synblock_t **blocks, size_t *nBlocks)
+{
+  if (!sk || !pairs || !nPairs || !blocks || !nBlocks) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->synteny) return fail(ANI_ERR_ARG, "ani_sketch_synteny_take without ani_sketch_synteny_begin");
+  *pairs = nullptr; *nPairs = 0; *blocks = nullptr; *nBlocks = 0;
+  SynBufs &pd = sk->synPending;
+  if (pd.pairs.n == 0) { pd.clear(); return ANI_OK; }
+  *pairs = pd.pairs.rec; *nPairs = pd.pairs.n;  // the buffers themselves: ani_free releases them
+  pd.pairs.rec = nullptr; pd.pairs.n = pd.pairs.cap = 0;
+  if (pd.blocks.n == 0) { pd.blocks.clear(); return ANI_OK; }
+  *blocks = pd.blocks.rec; *nBlocks = pd.blocks.n;
+  pd.blocks.rec = nullptr; pd.blocks.n = pd.blocks.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_synteny_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->synteny) return fail(ANI_ERR_ARG, "ani_sketch_synteny_end without ani_sketch_synteny_begin");
+  sk->synPending.clear(); sk->ctx->synStage.clear();
+  sk->synteny = false;
   return ANI_OK;
 }
 

@@ -466,6 +466,12 @@ using CiBuf = RecBuf<ani_ci_t>;
 // sub-batch, one part per index chunk (part k = rec[cut[k] .. cut[k + 1]), each in (query, querySeqId) order), until ani_paint_merge
 // joins them
 using PaintBuf = RecBuf<ani_paint_t>;
+// the synteny records (ani_sketch_synteny_begin; kernels/synteny.hpp): one record per gated pair and, in the same pair order, `blocks` block
+// records per pair
+struct SynBufs {
+  RecBuf<ani_synteny_t> pairs; RecBuf<ani_synblock_t> blocks;
+  void clear() { pairs.clear(); blocks.clear(); }
+};
 struct PaintParts {
   PaintBuf buf; std::vector<size_t> cut = std::vector<size_t>(1, 0);
   void clear() { buf.clear(); cut.assign(1, 0); }
@@ -565,6 +571,14 @@ struct ani_ctx {
   DevBuf paintBest, paintSecond, paintGenomes, paintWin, paintFlags, paintOff, paintRec;
   PaintParts paintStage;
   uint32_t paintPiece = 1u << 22;         // records per launch and copy (env ANI_TEST_PAINT_PIECE, tests)
+  // synteny records (only while a sketch has them on; the owner table is the hits', used after hits_stage is done with it): the gate's
+  // flags, offsets, list, hit counts and hit offsets of a (sub-batch, chunk), the pool units of the pairs above the LDS cap and their
+  // offsets, and per piece the work pool, the pair records, the block pool at hit offsets, the block counts and offsets and the compacted
+  // blocks; the records reduce_stage has staged for the sub-batch's collect_rows (query = index in the sub-batch)
+  DevBuf synFlags, synOff, synList, synCount, synRecOff, synPoolUnits, synPoolOff, synPool, synRec, synBlkPool, synBlkCount, synBlkOff, synBlk;
+  SynBufs synStage;
+  uint32_t synPiece = 1u << 20;           // pairs per launch and copy, and at most 2^22 hits unless one pair has more (env ANI_TEST_SYNTENY_PIECE, tests)
+  uint32_t synLdsHits = 2048 /* ani::kSynLdsHits */;    // hits of a pair kept in LDS (env ANI_TEST_SYNTENY_LDS_HITS lowers it, tests)
 };
 
 // One index over a contiguous run of reference genomes: < 2^31 minimizers, 32-bit indices, chunk-local seqIds.  A reference set
@@ -639,6 +653,10 @@ struct ani_sketch {
   // `paintPending` for ani_sketch_paint_take
   bool paint = false;
   PaintBuf paintPending;
+  // synteny records (ani_sketch_synteny_begin .. _end): reduce_stage makes a pair record and its block records per gated pair while they
+  // are on; both lists take the way of the best-hit records to `synPending`, which ani_sketch_synteny_take hands over
+  bool synteny = false; uint32_t synMinIdBits = 0, synMinFragments = 1;
+  SynBufs synPending;
 };
 
 namespace anih {

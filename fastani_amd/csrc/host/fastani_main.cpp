@@ -92,6 +92,8 @@ struct Options {
   bool hits = false;                                   // --hits: the .hits file, the reciprocal best fragment hits behind every -o line
   bool paint = false;                                  // --paint: the .paint and .paintsum files, every query fragment's best reference over all references
   float hitsMinANI = 0.0f; int hitsMinFragments = 1;   // --hitsMinANI, --hitsMinFragments: the pairs that get lines (ani_sketch_hits_begin's gate)
+  bool synteny = false;                                // --synteny: the .synteny and .synblocks files, the order of the hits behind every -o line
+  float syntenyMinANI = 0.0f; int syntenyMinFragments = 1;   // --syntenyMinANI, --syntenyMinFragments: the pairs that get lines (ani_sketch_synteny_begin's gate)
   bool ci = false;                                     // --ci: the .ci file, a bootstrap interval beside the ANI of every -o line
   int ciReplicates = 200, ciLevelPermille = 950; uint32_t ciSeed = 1;   // --ciReplicates, --ciLevel (percent), --ciSeed (ani_sketch_ci_begin)
   float ciMinANI = 0.0f; int ciMinFragments = 1;       // --ciMinANI, --ciMinFragments: the pairs that get a line (its gate)
@@ -122,6 +124,7 @@ struct Options {
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
     "             [--hits] [--hitsMinANI <value>] [--hitsMinFragments <value>] [--paint]\n"
+    "             [--synteny] [--syntenyMinANI <value>] [--syntenyMinFragments <value>]\n"
     "             [--ci] [--ciReplicates <value>] [--ciLevel <value>] [--ciSeed <value>] [--ciMinANI <value>] [--ciMinFragments <value>]\n"
     "             [-o <value>] [-s] [-v] [--gpus <value>]\n\n"
     "OPTIONS\n"
@@ -209,6 +212,19 @@ struct Options {
     "                 this reference only), by fragments descending, and a last line query, NA, unmapped fragments, share, NA, NA.\n"
     "                 Host memory: 40 bytes per mapped fragment until the files are written (about 6 GB for 90 000 genomes of 5 Mbp),\n"
     "                 and 4 bytes per query contig\n"
+    "     --synteny  also write <output>.synteny and <output>.synblocks: the ORDER of the reciprocal best hits behind every line of\n"
+    "                 the output (collinear end to end, an inversion, a translocated island, a shuffled draft assembly), computed on\n"
+    "                 the device; works in every input mode --hits does, and with --gpus.  <output>.synteny, one line per line of the\n"
+    "                 output: query, reference, fragments, forward, reverse, breaks, contigBorders, blocks, reverseBlocks,\n"
+    "                 reverseFragments, largestBlock, singletons, collinearity = (forward + reverse) / (fragments - 1 - contigBorders),\n"
+    "                 NA where that denominator is 0.  Two hits that are neighbours on the reference are joined forward / reverse if\n"
+    "                 their fragments are neighbours among the pair's matched fragments, in that direction; a block is a maximal\n"
+    "                 joined run.  <output>.synblocks, one line per block in reference order: query, reference, direction (+, -, .),\n"
+    "                 qStart, qEnd, rStart, rEnd, fragments, meanIdentity (coordinates as in .hits).  The query's contigs count as\n"
+    "                 one sequence in file order (a draft query shows at most one break per contig border), and a circular genome\n"
+    "                 cut at another origin shows one break.  Host memory: 48 bytes per pair and 32 per block\n"
+    "     --syntenyMinANI <value>  only the pairs from this ANI on get lines (0 <= value <= 100) [default : 0, every line of the output]\n"
+    "     --syntenyMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
     "     --ci  also write <output>.ci: a percentile bootstrap interval of every ANI value, resampled from the fragment identities it is\n"
     "           the mean of.  Line 1 is \"#replicates<TAB>B<TAB>level<TAB>L<TAB>seed<TAB>s\"; then per line of the output, in its order:\n"
     "           query, reference, ANI, low, high, fragments\n"
@@ -253,7 +269,8 @@ Options parse(int argc, char **argv)
   std::string refName, refList, qryName, qryList;
   bool help = false, version = false, treeMethod = false, treeFill = false, sketchSize = false, sketchMinANI = false, sketchContain = false;
   bool profileMinANI = false, profileMinFragments = false;
-  bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false, hitsMinANI = false, hitsMinFragments = false;
+  bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false, hitsMinANI = false, hitsMinFragments = false,
+       syntenyMinANI = false, syntenyMinFragments = false;
   const char *ciSub = nullptr;                         // the first --ci sub-option seen
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
@@ -316,6 +333,11 @@ Options parse(int argc, char **argv)
       if (!(o.fragDistMinANI >= 0.0f && o.fragDistMinANI <= 100.0f)) { std::cerr << "ERROR, --fragDistMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hits") o.hits = true;
     else if (a == "--paint") o.paint = true;
+    else if (a == "--synteny") o.synteny = true;
+    else if (a == "--syntenyMinANI") { o.syntenyMinANI = (float)atof(need(i)); syntenyMinANI = true;
+      if (!(o.syntenyMinANI >= 0.0f && o.syntenyMinANI <= 100.0f)) { std::cerr << "ERROR, --syntenyMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
+    else if (a == "--syntenyMinFragments") { o.syntenyMinFragments = atoi(need(i)); syntenyMinFragments = true;
+      if (o.syntenyMinFragments < 1) { std::cerr << "ERROR, --syntenyMinFragments takes a count of at least 1" << std::endl; exit(1); } }
     else if (a == "--hitsMinANI") { o.hitsMinANI = (float)atof(need(i)); hitsMinANI = true;
       if (!(o.hitsMinANI >= 0.0f && o.hitsMinANI <= 100.0f)) { std::cerr << "ERROR, --hitsMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hitsMinFragments") { o.hitsMinFragments = atoi(need(i)); hitsMinFragments = true;
@@ -363,6 +385,8 @@ Options parse(int argc, char **argv)
   if (fragDistMinANI && !o.fragDist) { std::cerr << "ERROR, --fragDistMinANI needs --fragDist" << std::endl; exit(1); }
   if (hitsMinANI && !o.hits) { std::cerr << "ERROR, --hitsMinANI needs --hits" << std::endl; exit(1); }
   if (hitsMinFragments && !o.hits) { std::cerr << "ERROR, --hitsMinFragments needs --hits" << std::endl; exit(1); }
+  if (syntenyMinANI && !o.synteny) { std::cerr << "ERROR, --syntenyMinANI needs --synteny" << std::endl; exit(1); }
+  if (syntenyMinFragments && !o.synteny) { std::cerr << "ERROR, --syntenyMinFragments needs --synteny" << std::endl; exit(1); }
   if (ciSub && !o.ci) { std::cerr << "ERROR, " << ciSub << " needs --ci" << std::endl; exit(1); }
   if (fragDistMinFragments && !o.fragDist) { std::cerr << "ERROR, --fragDistMinFragments needs --fragDist" << std::endl; exit(1); }
   if (o.fragDist && !fragDistEdges) { for (int e = 70; e <= 99; e++) o.fragDistEdges.push_back((float)e); o.fragDistEdges.push_back(99.5f); o.fragDistEdges.push_back(99.9f); }
@@ -849,6 +873,46 @@ struct HitsTable {
 };
 HitsTable g_hits;
 
+// --synteny: the pair and block records (ani_sketch_synteny_begin) of the pairs, keyed by (query, reference) file index.  Begun and drained
+// where the profile is.  A block's reference positions become offsets inside the reference genome while the sketch that knows the contigs
+// is alive.
+struct SyntenyTable {
+  bool on = false; float minANI = 0.0f; int32_t minFragments = 1;
+  struct Block { int64_t rFirst, rLast; int32_t qFirst, qLast; uint32_t hits; uint64_t idSum; };
+  struct Pair { ani_synteny_t rec; size_t firstBlock; };
+  std::vector<Pair> pair; std::vector<Block> block;
+  std::unordered_map<uint64_t, size_t> at;                 // (query << 32 | reference) -> pair
+  void init(const Options &o) { on = o.synteny; minANI = o.syntenyMinANI; minFragments = o.syntenyMinFragments; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_synteny_begin(sk, minANI, minFragments)) { std::cerr << "ERROR, ani_sketch_synteny_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  // what the mapping calls left in `sk`: genome g of the sketch is reference refOf(g); the query ids are the run's own
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_synteny_t *p = nullptr; ani_synblock_t *b = nullptr; size_t n = 0, nb = 0; const int32_t *cl = nullptr, *gcs = nullptr;
+    if (ani_sketch_synteny_take(sk, &p, &n, &b, &nb) || ani_sketch_tables(sk, &cl, &gcs)) {
+      std::cerr << "ERROR, ani_sketch_synteny_take: " << ani_last_error() << std::endl; exit(1); }
+    size_t k = 0;
+    for (size_t i = 0; i < n; i++) {
+      const int32_t g = p[i].refGenomeId;
+      Pair e{p[i], block.size()};
+      e.rec.refGenomeId = (int32_t)refOf(g);
+      at[((uint64_t)(uint32_t)e.rec.qryGenomeId << 32) | (uint32_t)e.rec.refGenomeId] = pair.size();
+      pair.push_back(e);
+      int32_t seq = gcs[g]; int64_t off = 0;                // a pair's blocks ascend by contig
+      for (uint32_t j = 0; j < p[i].blocks && k < nb; j++, k++) {
+        const ani_synblock_t &x = b[k];
+        for (; seq < x.refSeqId; seq++) off += cl[seq];
+        block.push_back(Block{off + x.refStartFirst, off + x.refStartLast, x.qSeqFirst, x.qSeqLast, x.hits, x.idSum});
+      }
+    }
+    ani_free(p); ani_free(b);
+  }
+};
+SyntenyTable g_synteny;
+
 // --paint: the per-fragment records (ani_sketch_paint_begin) of the queries over all references.  Begun and drained where the profile is.
 // What a sketch hands over covers its own references only: the ids become the reference list's indices, the winner's position becomes
 // the offset inside its genome while the sketch that knows the contigs is alive (62 bits, carried in refSeqId : refStartPos), and the
@@ -1213,6 +1277,7 @@ struct Streaming {
     g_fragdist.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_hits.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_paint.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_synteny.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_ci.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
   }
 
@@ -1308,7 +1373,8 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); g_paint.begin(shard[d].sk); }
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); g_paint.begin(shard[d].sk);
+      g_synteny.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
         if (shard[d].nGenomes > 0 && !g_sigs.have[(size_t)shard[d].g0]) g_sigs.collect(shard[d].sk, (size_t)shard[d].g0, (size_t)shard[d].nGenomes);
@@ -1539,7 +1605,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk); g_paint.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk); g_paint.begin(sk); g_synteny.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1598,6 +1664,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     g_fragdist.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_hits.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_paint.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
+    g_synteny.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_ci.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
@@ -1735,6 +1802,38 @@ void write_hits(const Options &o, const ani_params_t &ap, const std::vector<ani_
       const int64_t qs = (size_t)h.qSeq < qOff.size() ? qOff[(size_t)h.qSeq] : 0;
       f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << h.identity << "\tNA\tNA\tNA\t" << qs << "\t" << qs + ap.fragLen - 1 << "\t"
             << h.refStart << "\t" << h.refStart + ap.fragLen - 1 << "\tNA\tNA\n";
+    }
+  }
+}
+
+// ---- .synteny: per line of the output file whose pair passed the gate, in its order: query, reference, fragments, forward, reverse, breaks,
+// contigBorders, blocks, reverseBlocks, reverseFragments, largestBlock, singletons, collinearity (four decimals; NA where fragments - 1 -
+// contigBorders is 0).  .synblocks: the pair's blocks in reference order: query, reference, direction, qStart, qEnd (from the start of the
+// smaller fragment id to the end of the larger), rStart, rEnd (from the first hit's start to the last hit's end), fragments, meanIdentity
+// (exact: from the sum of llrint(identity * 2^20)); coordinates as in .hits
+void write_synteny(const Options &o, const ani_params_t &ap, const std::vector<ani_cgi_t> &rows, const Trusted &trusted, GenomeLengths &lengths)
+{
+  BufferedFile f(o.out + ".synteny"), fb(o.out + ".synblocks");
+  int32_t q = -1; std::vector<int64_t> qOff;
+  for (auto &e : rows) {
+    if (!trusted(e)) continue;
+    const auto it = g_synteny.at.find(((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId);
+    if (it == g_synteny.at.end()) continue;                 // the pair did not pass the gate
+    const SyntenyTable::Pair &p = g_synteny.pair[it->second];
+    const ani_synteny_t &x = p.rec;
+    f.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << x.count << "\t" << x.forward << "\t" << x.reverse << "\t" << x.breaks << "\t"
+          << x.contigBorders << "\t" << x.blocks << "\t" << x.reverseBlocks << "\t" << x.reverseHits << "\t" << x.largestBlock << "\t" << x.singletons << "\t";
+    const uint32_t den = x.count - 1u - x.contigBorders;
+    if (den) f.out << std::fixed << std::setprecision(4) << (double)(x.forward + x.reverse) / (double)den << std::defaultfloat << std::setprecision(6) << "\n";
+    else f.out << "NA\n";
+    if (e.qryGenomeId != q) { q = e.qryGenomeId; qOff = fragment_offsets(ap, lengths.contigs_of(o.queries[(size_t)q])); }
+    for (size_t i = p.firstBlock; i < p.firstBlock + x.blocks && i < g_synteny.block.size(); i++) {
+      const SyntenyTable::Block &b = g_synteny.block[i];
+      const int32_t lo = std::min(b.qFirst, b.qLast), hi = std::max(b.qFirst, b.qLast);
+      const int64_t qs = (size_t)lo < qOff.size() ? qOff[(size_t)lo] : 0, qe = ((size_t)hi < qOff.size() ? qOff[(size_t)hi] : 0) + ap.fragLen - 1;
+      fb.out << o.queries[e.qryGenomeId] << "\t" << o.refs[e.refGenomeId] << "\t" << (b.qLast > b.qFirst ? "+" : b.qLast < b.qFirst ? "-" : ".") << "\t"
+             << qs << "\t" << qe << "\t" << b.rFirst << "\t" << b.rLast + ap.fragLen - 1 << "\t" << b.hits << "\t"
+             << (float)((double)b.idSum / 1048576.0 / (double)b.hits) << "\n";
     }
   }
 }
@@ -2301,10 +2400,10 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o); g_paint.init(o);
+  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o); g_paint.init(o); g_synteny.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
-  lengths.keepContigs = o.hits || o.paint;
+  lengths.keepContigs = o.hits || o.paint || o.synteny;
   Startup su(o, m, ap);
   std::cerr << "INFO [thread 0], skch::Sketch::build, window size for minimizer sampling  = " << ap.windowSize << std::endl;
   std::cerr << "INFO [thread 0], skch::main, Count of threads executing parallel_for : " << (o.sanityCheck ? o.threads : (int)su.dev.size()) << std::endl;
@@ -2326,6 +2425,7 @@ int main(int argc, char **argv)
   if (o.hits) write_hits(o, ap, res.rows, trusted, lengths);
   if (o.ci) write_ci(o, res.rows, trusted);
   if (o.paint) write_paint(o, ap, lengths);
+  if (o.synteny) write_synteny(o, ap, res.rows, trusted, lengths);
   MatrixCells mc;
   if (o.matrix || o.cluster > 0.0f || o.tree || o.sketchANI || o.sketchNeighbors || o.sketchCluster > 0.0f || o.sketchGraph > 0.0f) mc = matrix_cells(o, res.rows, trusted);
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);

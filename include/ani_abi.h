@@ -496,6 +496,48 @@ int ani_sketch_paint_take(ani_sketch *sk, ani_paint_t **rec, size_t *n);
 int ani_sketch_paint_end(ani_sketch *sk);
 int ani_paint_merge(const ani_paint_t *a, size_t na, const ani_paint_t *b, size_t nb, ani_paint_t **out, size_t *n);
 
+/* ---- collinear blocks and breakpoints of a pair's reciprocal best hits (the ORDER of the hits, which the reference shows only as the
+ * dot plot of --visualize, one pair per run).  Between begin and end every call that reduces against the sketch
+ * (the calls of the profile's rule 5; ani_map_query adds nothing) appends one pair record per contributing pair and one block record per
+ * collinear block of it to two lists on the host, which take hands over.  Everything is integer arithmetic on the pair's best-hit records
+ * as rules 1 - 6 of the hits define them: the synteny records of a pair are a pure function of that pair's hit records.
+ *  1. Input.  A pair that passes the gate (the hits' rule 3, with this mode's own minIdentity and minFragments) has the hits
+ *     h[0 .. n - 1] in bin order (the hits' rule 6), n = countSeq; q[i] = querySeqId, c[i] = refSeqId, p[i] = refStartPos, F[i] =
+ *     fix(identity) = (uint64_t) llrint((double) identity * 2^20) of h[i].  The q[i] of one pair are distinct.
+ *  2. Rank.  r[i] = the number of j with q[j] < q[i]: the rank among the pair's own hits, not the id itself.  Fragments that mapped
+ *     nowhere and insertions of unmatched sequence therefore break nothing; querySeqId need not be dense and goes up to 2^31 - 1.
+ *  3. Adjacency (i, i + 1), 0 <= i < n - 1, has exactly one class: `contig` if c[i] != c[i + 1]; else `forward` if r[i + 1] = r[i] + 1;
+ *     else `reverse` if r[i + 1] = r[i] - 1; else `break`.  (Ranks are distinct, so forward is never directly followed by reverse.)
+ *  4. Block.  A maximal run of consecutive hits joined by forward / reverse adjacencies; its direction is +1, -1, or 0 for a block of one
+ *     hit (a singleton).
+ *  5. Pair record.  refGenomeId and qryGenomeId as the hits' rule 4 gives them; count = n; forward, reverse, breaks, contigBorders = the
+ *     adjacencies per class; blocks; reverseBlocks = the blocks of direction -1; reverseHits = the hits inside those; largestBlock, in
+ *     hits; singletons.  forward + reverse + breaks + contigBorders = count - 1 and blocks = breaks + contigBorders + 1.
+ *  6. Block record.  refSeqId (the sketch's own set-global contig id); refStartFirst, refStartLast = p of the block's first and last hit in
+ *     bin order; qSeqFirst, qSeqLast = q of the same two hits (qSeqLast > qSeqFirst: forward, <: reverse, equal: singleton); hits; idSum
+ *     = the sum of the F[i] of the block.  A pair's blocks come in bin order, `blocks` of them; their hits add up to count and their
+ *     idSum to ani_ci_t.sum of the same pair.
+ *  7. Order.  The pair records of one call come in the order of that call's rows, restricted to the pairs that pass the gate; the block
+ *     records in the same pair order; calls follow each other in call order.
+ *  8. Independence.  Rows are untouched.  Nothing depends on schedule, sub-batch size, index chunking, residency or piece sizes.  All
+ *     other modes can be on beside it and do not see it; each has its own gate, and the hits' gate and this one may differ in one call.
+ * Limits of the statement: query contig borders are not known here (only querySeqId is), so the query's contigs count as one sequence
+ * in file order and a draft query shows at most one break per contig border; a circular genome cut at another origin shows one break.
+ * begin starts (a second begin drops what is pending and takes the new gate).  take hands over everything appended since begin or the
+ * last take and empties both lists: pairs[nPairs] and blocks[nBlocks], each released with ani_free; an empty list comes back NULL with
+ * 0.  48 bytes per pair and 32 per block of host memory until taken.  While the mode is on the device holds one more uint32 per cell of
+ * a sub-batch's bin table (the hits' owner table, shared with them).  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null
+ * sketch (or a null out pointer), a gate outside its ranges (NaN included), take or end without a begin; a refused begin leaves a
+ * running mode as it was.  ANI_ERR_NOMEM: the records do not fit the host, or the device cannot hold the table or a piece.
+ * ANI_ERR_LIMIT: more than 2^32 - 16 hits, and so blocks, in one (sub-batch, index chunk).  After a call that failed while reducing,
+ * the pending lists are unspecified until the next begin. */
+typedef struct { int32_t refGenomeId, qryGenomeId; uint32_t count, forward, reverse, breaks, contigBorders, blocks, reverseBlocks,
+                 reverseHits, largestBlock, singletons; } ani_synteny_t;   /* 48 bytes */
+typedef struct { int32_t refSeqId, refStartFirst, refStartLast, qSeqFirst, qSeqLast; uint32_t hits; uint64_t idSum; } ani_synblock_t;  /* 32 bytes */
+int ani_sketch_synteny_begin(ani_sketch *sk, float minIdentity, int32_t minFragments);
+int ani_sketch_synteny_take(ani_sketch *sk, ani_synteny_t **pairs, size_t *nPairs, ani_synblock_t **blocks, size_t *nBlocks);
+int ani_sketch_synteny_end(ani_sketch *sk);
+
 /* ---- greedy species clustering of the pair graph (no counterpart in the reference, which stops at the rows and the .matrix file;
  * DESIGN.md section 2.11).  Rows' qryGenomeId / refGenomeId are ids in ONE numbering [0, nGenomes) (the command line uses the .matrix
  * numbering); the rows of a pair are folded in the order given (the first sets w, every later one w = (w + identity) / 2 in float),
