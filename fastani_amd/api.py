@@ -47,6 +47,8 @@ FRAGDIST_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count"
 HIT_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("querySeqId", "<i4"), ("identity", "<f4")])
 CI_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("replicates", "<u4"), ("sum", "<u8"), ("lowSum", "<u8"),
                   ("highSum", "<u8"), ("low", "<f4"), ("high", "<f4")])
+BOOT_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("replicates", "<u4"), ("sum", "<u8")])
+TREE_METHODS = {"average": 0, "nj": 1, "single": 2}          # ANI_TREE_AVERAGE, ANI_TREE_NJ, ANI_TREE_SINGLE
 PAINT_DT = np.dtype([("qryGenomeId", "<i4"), ("querySeqId", "<i4"), ("refGenomeId", "<i4"), ("refSeqId", "<i4"), ("refStartPos", "<i4"), ("identity", "<f4"),
                      ("secondGenomeId", "<i4"), ("secondIdentity", "<f4"), ("genomes", "<u4"), ("reserved", "<u4")])
 SYNTENY_DT = np.dtype([("refGenomeId", "<i4"), ("qryGenomeId", "<i4"), ("count", "<u4"), ("forward", "<u4"), ("reverse", "<u4"), ("breaks", "<u4"),
@@ -160,6 +162,11 @@ def _bind(lib):
         "ani_sketch_ci_begin": (C.c_int, [vp, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]),
         "ani_sketch_ci_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_ci_end": (C.c_int, [vp]),
+        "ani_sketch_boot_begin": (C.c_int, [vp, C.c_float, C.c_int32, C.c_int32, C.c_uint32]),
+        "ani_sketch_boot_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "ani_sketch_boot_end": (C.c_int, [vp]),
+        "ani_tree_support": (C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp]),
+        "ani_tree_support_bootstrap": (C.c_int, [vp, C.c_int32, vp, C.c_size_t, C.c_int32, C.c_float, vp, C.c_int32, vp, vp]),
         "ani_sketch_paint_begin": (C.c_int, [vp]),
         "ani_sketch_paint_take": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "ani_sketch_paint_end": (C.c_int, [vp]),
@@ -334,6 +341,35 @@ def paint_merge(a, b, lib=None):
         lib.ani_free(rp)
         return np.zeros(0, dtype=PAINT_DT)
     return np.asarray(_OwnedBuffer(lib, rp.value, n.value, PAINT_DT))
+
+
+def boot_identity(records, sums):
+    """-> float32[n, B]: the replicate identities of the records and sums of Sketch.boot_take, by the boot records' rule 3 of ani_abi.h:
+    (float)((double) S[r] / ((double) count * 1048576.0))"""
+    records = np.ascontiguousarray(records, dtype=BOOT_DT)
+    sums = np.ascontiguousarray(sums, dtype=np.uint64).reshape(len(records), -1)
+    return (sums.astype(np.float64) / (records["count"].astype(np.float64) * 1048576.0)[:, None]).astype(np.float32)
+
+
+def tree_support(children, rep_children, unrooted=False, lib=None):
+    """-> uint32[n_genomes - 1]: per record of the tree `children` (int (n_genomes - 1, 2), the record form of Engine.tree_average /
+    tree_single (columns 0 and 1 of the linkage) / tree_nj) the number of replicate trees `rep_children` (int (B, n_genomes - 1, 2)) that
+    hold the same clade — with `unrooted` the same split (ani_tree_support: a host function, no engine).  `lib`: the library to call,
+    the product library by default."""
+    if lib is None:
+        from . import _lib
+        lib = _lib.load()
+    if lib.ani_tree_support.argtypes is None:      # no Engine has bound this library yet
+        _bind(lib)
+    children = np.ascontiguousarray(np.asarray(children).reshape(-1, 2), dtype=np.int32)
+    m = len(children)
+    rep_children = np.ascontiguousarray(np.asarray(rep_children).reshape(-1, m, 2) if m else np.zeros((0, 0, 2)), dtype=np.int32)
+    support = np.zeros(m, dtype=np.uint32)
+    rc = lib.ani_tree_support(children.ctypes.data if m else None, m + 1, rep_children.ctypes.data if rep_children.size else None,
+                              len(rep_children), 1 if unrooted else 0, support.ctypes.data if m else None)
+    if rc != 0:
+        raise AniError(rc, (lib.ani_last_error() or b"").decode())
+    return support
 
 
 def _as_batch(g):
@@ -527,6 +563,27 @@ class Engine:
                                            edges.ctypes.data if m and return_edges else None))
         z = self._linkage(children, height, n_genomes)
         return (z, edges.reshape(m, 2).astype(np.int64)) if return_edges else z
+
+    def tree_support_bootstrap(self, method, rows, n_genomes, rep_identity, children, missing_identity=0.0):
+        """-> uint32[n_genomes - 1]: the bootstrap support of the records of `children`, the tree of `method` ("average", "nj" or "single")
+        over `rows`: per replicate r the method's tree over the rows with identity rep_identity[i, r] (float32 (len(rows), B), from
+        Sketch.boot_take and boot_identity, a row without a replicate record keeping its own identity in every column), then
+        tree_support, unrooted for nj (ani_tree_support_bootstrap)"""
+        rows = np.ascontiguousarray(rows, dtype=CGI_DT)
+        n_genomes = int(n_genomes)
+        m = max(n_genomes - 1, 0)
+        rep_identity = np.ascontiguousarray(rep_identity, dtype=np.float32)
+        if rep_identity.ndim != 2 or rep_identity.shape[0] != len(rows):
+            raise ValueError("rep_identity must be (len(rows), replicates)")
+        children = np.ascontiguousarray(np.asarray(children).reshape(-1), dtype=np.int32)
+        if len(children) != 2 * m:
+            raise ValueError("children must hold n_genomes - 1 records")
+        support = np.zeros(m, dtype=np.uint32)
+        self._chk(self.lib.ani_tree_support_bootstrap(self.h, TREE_METHODS[method] if isinstance(method, str) else int(method),
+                                                      rows.ctypes.data if len(rows) else None, len(rows), n_genomes, float(missing_identity),
+                                                      rep_identity.ctypes.data if rep_identity.size else None, rep_identity.shape[1],
+                                                      children.ctypes.data if m else None, support.ctypes.data if m else None))
+        return support
 
     @staticmethod
     def _linkage(children, height, n_genomes):
@@ -1031,6 +1088,25 @@ class Sketch:
 
     def ci_end(self):
         self.e._chk(self.e.lib.ani_sketch_ci_end(self.h))
+
+    def boot_begin(self, replicates=100, seed=1, min_identity=0.0, min_fragments=1):
+        """start (or restart) the bootstrap replicate records: every mapping call that reduces against this sketch appends one record and
+        `replicates` (1 .. 1024) replicate sums — the intervals' draws, kept — per pair whose row has countSeq >= min_fragments and
+        identity >= min_identity; `seed` a uint32 (ani_sketch_boot_begin)"""
+        self.e._chk(self.e.lib.ani_sketch_boot_begin(self.h, float(min_identity), int(min_fragments), int(replicates), int(seed) & 0xffffffff))
+        self._boot_replicates = int(replicates)
+
+    def boot_take(self):
+        """-> (records BOOT_DT[n], sums uint64[n, replicates]) appended since boot_begin or the last take, in row order; empties the list"""
+        rp, sp, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self.e._chk(self.e.lib.ani_sketch_boot_take(self.h, C.byref(rp), C.byref(sp), C.byref(n)))
+        k = self._boot_replicates
+        rec = self.e._take(rp, n.value, BOOT_DT)
+        sums = self.e._take(sp, n.value * k, np.dtype("<u8")).reshape(n.value, k)
+        return rec, sums
+
+    def boot_end(self):
+        self.e._chk(self.e.lib.ani_sketch_boot_end(self.h))
 
     def paint_begin(self):
         """start the per-fragment records: every mapping call that reduces against this sketch appends one record per query fragment

@@ -169,6 +169,8 @@ int ani_init(int device, ani_ctx **out)
   if (const char *ev = getenv("ANI_TEST_SYNTENY_LDS_HITS")) { const long long v = atoll(ev); if (v >= 1 && v <= 2048 /* ani::kSynLdsHits */) c->synLdsHits = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CI_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->ciPiece = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CI_LDS_CELLS")) { const long long v = atoll(ev); if (v >= 1 && v <= 2560 /* ani::kCiLdsCells */) c->ciLdsCells = (uint32_t)v; }
+  if (const char *ev = getenv("ANI_TEST_BOOT_PIECE")) { const long long v = atoll(ev); if (v >= 1 && v <= (1 << 24)) c->bootPiece = (uint32_t)v; }
+  if (const char *ev = getenv("ANI_TEST_BOOT_LDS_CELLS")) { const long long v = atoll(ev); if (v >= 1 && v <= 2560 /* ani::kCiLdsCells */) c->bootLdsCells = (uint32_t)v; }
   if (const char *ev = getenv("ANI_TEST_CAND_POOL_MIN")) { const long long v = atoll(ev); if (v >= 1) c->candPoolMin = (uint64_t)v; }
   if (const char *ev = getenv("ANI_TEST_L1_BIG_GROUP_HITS")) { const long long v = atoll(ev); if (v >= 1) c->l1BigGroupHits = (uint64_t)v; }
   if (const char *ev = getenv("ANI_TEST_L1_BIG_GROUP_FRAGS")) { const long long v = atoll(ev); if (v >= 1) c->l1BigGroupFrags = (uint64_t)v; }
@@ -202,7 +204,7 @@ void ani_shutdown(ani_ctx *c)
                     &c->l2First, &c->l2Last, &c->refStart, &c->idBits, &c->keepFlags, &c->keepOff, &c->mapOut, &c->bins, &c->queryFragments, &c->rows,
                     &c->fdFlags, &c->fdOff, &c->fdList, &c->fdRec, &c->fdHist,
                     &c->hitOwner, &c->hitFlags, &c->hitOff, &c->hitList, &c->hitCount, &c->hitRecOff, &c->hitRec, &c->hitQSeq,
-                    &c->ciFlags, &c->ciOff, &c->ciList, &c->ciPoolCells, &c->ciPoolOff, &c->ciPool, &c->ciRec,
+                    &c->ciFlags, &c->ciOff, &c->ciList, &c->ciPoolCells, &c->ciPoolOff, &c->ciPool, &c->ciRec, &c->bootRec, &c->bootSums,
                     &c->paintBest, &c->paintSecond, &c->paintGenomes, &c->paintWin, &c->paintFlags, &c->paintOff, &c->paintRec,
                     &c->synFlags, &c->synOff, &c->synList, &c->synCount, &c->synRecOff, &c->synPoolUnits, &c->synPoolOff, &c->synPool, &c->synRec,
                     &c->synBlkPool, &c->synBlkCount, &c->synBlkOff, &c->synBlk};

@@ -573,4 +573,134 @@ int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGeno
 
 int ani_tree_single_rounds(const ani_ctx *ctx) { return ctx ? ctx->treeSingleRounds : 0; }
 
+// ---- clade support (ani_abi.h: ani_tree_support) ----
+namespace {
+
+struct LeafSet { int32_t mn, mx, size; };              // of positions in the main tree's traversal order
+inline LeafSet join(const LeafSet &a, const LeafSet &b)
+{
+  if (!a.size) return b;
+  if (!b.size) return a;
+  return LeafSet{std::min(a.mn, b.mn), std::max(a.mx, b.mx), a.size + b.size};
+}
+
+// rule 5: record s names two ids below nGenomes + s, and no id twice.  n - 1 such records over n leaves are one tree, rooted at the last.
+bool is_tree(const int32_t *ch, int32_t n, std::vector<uint8_t> &used)
+{
+  used.assign((size_t)2 * n - 1, 0);
+  for (int32_t s = 0; s < n - 1; s++)
+    for (int k = 0; k < 2; k++) {
+      const int32_t v = ch[2 * (size_t)s + k];
+      if (v < 0 || v >= n + s || used[(size_t)v]) return false;
+      used[(size_t)v] = 1;
+    }
+  return true;
+}
+
+}  // namespace
+
+int ani_tree_support(const int32_t *children, int32_t nGenomes, const int32_t *repChildren, int32_t nReplicates, int32_t unrooted, uint32_t *support)
+{
+  if (nGenomes < 0 || nReplicates < 0) return fail(ANI_ERR_ARG, "negative count");
+  if (nGenomes <= 1) return ANI_OK;
+  if (!children || !support || (nReplicates && !repChildren)) return fail(ANI_ERR_ARG, "null argument");
+  try {
+    const int32_t n = nGenomes, M = n - 1;
+    const size_t nodes = (size_t)2 * n - 1;
+    std::vector<uint8_t> used;
+    if (!is_tree(children, n, used)) return fail(ANI_ERR_ARG, "ani_tree_support: the main record list is not a tree");
+    for (int32_t r = 0; r < nReplicates; r++)
+      if (!is_tree(repChildren + (size_t)r * 2 * M, n, used)) return fail(ANI_ERR_ARG, "ani_tree_support: the record list of replicate %d is not a tree", r);
+    // the main tree: sizes in record order, then positions from the root down (a parent's record comes after its children's): the leaves
+    // of a node are the positions start .. start + size - 1
+    std::vector<int32_t> size(nodes, 1), start(nodes, 0);
+    for (int32_t s = 0; s < M; s++) size[(size_t)n + s] = size[(size_t)children[2 * (size_t)s]] + size[(size_t)children[2 * (size_t)s + 1]];
+    for (int32_t s = M - 1; s >= 0; s--) {
+      const int32_t a = children[2 * (size_t)s], b = children[2 * (size_t)s + 1];
+      start[(size_t)a] = start[(size_t)n + s]; start[(size_t)b] = start[(size_t)n + s] + size[(size_t)a];
+    }
+    // the clades asked for as intervals (lo << 32 | hi), sorted; unrooted: the side of the split without the last position, which is an
+    // interval for every main node — and so must the matching side of a replicate's node be
+    std::vector<uint64_t> key; key.reserve((size_t)M);
+    std::vector<uint64_t> want((size_t)M, ~0ull);        // per record; ~0: trivial
+    for (int32_t s = 0; s < M; s++) {
+      const int64_t lo = start[(size_t)n + s], sz = size[(size_t)n + s], hi = lo + sz - 1;
+      if (!unrooted) want[(size_t)s] = ((uint64_t)lo << 32) | (uint64_t)hi;
+      else if (sz >= n - 1) continue;
+      else want[(size_t)s] = hi < n - 1 ? (((uint64_t)lo << 32) | (uint64_t)hi) : (uint64_t)(lo - 1);      // [0, lo - 1]
+      key.push_back(want[(size_t)s]);
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    std::vector<uint32_t> count(key.size(), 0);
+    std::vector<int32_t> seen(key.size(), -1);             // the last replicate that had the clade: a replicate counts once
+    std::vector<LeafSet> in(nodes), out(unrooted ? nodes : 0);
+    for (int32_t i = 0; i < n; i++) in[(size_t)i] = LeafSet{start[(size_t)i], start[(size_t)i], 1};
+    auto look = [&](const LeafSet &x, int32_t r) {
+      if (x.size < 2 || x.mx - x.mn + 1 != x.size) return;
+      const uint64_t k = ((uint64_t)x.mn << 32) | (uint64_t)x.mx;
+      const auto it = std::lower_bound(key.begin(), key.end(), k);
+      if (it == key.end() || *it != k) return;
+      const size_t at = (size_t)(it - key.begin());
+      if (seen[at] != r) { seen[at] = r; count[at]++; }
+    };
+    for (int32_t r = 0; r < nReplicates; r++) {
+      const int32_t *ch = repChildren + (size_t)r * 2 * M;
+      for (int32_t s = 0; s < M; s++) {
+        in[(size_t)n + s] = join(in[(size_t)ch[2 * (size_t)s]], in[(size_t)ch[2 * (size_t)s + 1]]);
+        look(in[(size_t)n + s], r);
+      }
+      if (!unrooted) continue;
+      // the other side of every node's split: the parent's other side and the sibling, from the root (whose other side is empty) down
+      out[nodes - 1] = LeafSet{0, 0, 0};
+      for (int32_t s = M - 1; s >= 0; s--) {
+        const int32_t a = ch[2 * (size_t)s], b = ch[2 * (size_t)s + 1];
+        out[(size_t)a] = join(out[(size_t)n + s], in[(size_t)b]); out[(size_t)b] = join(out[(size_t)n + s], in[(size_t)a]);
+        look(out[(size_t)n + s], r);
+      }
+    }
+    for (int32_t s = 0; s < M; s++) {
+      if (want[(size_t)s] == ~0ull) { support[s] = (uint32_t)nReplicates; continue; }
+      support[s] = count[(size_t)(std::lower_bound(key.begin(), key.end(), want[(size_t)s]) - key.begin())];
+    }
+    return ANI_OK;
+  } catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
+// ---- bootstrap support of a tree: the replicate trees through the method's own entry point, then ani_tree_support ----
+int ani_tree_support_bootstrap(ani_ctx *ctx, int32_t method, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                               const float *repIdentity, int32_t nReplicates, const int32_t *children, uint32_t *support)
+{
+  if (!ctx || (n && !rows) || (nGenomes > 1 && (!children || !support)) || (n && nReplicates > 0 && !repIdentity)) return fail(ANI_ERR_ARG, "null argument");
+  if (method != ANI_TREE_AVERAGE && method != ANI_TREE_NJ && method != ANI_TREE_SINGLE) return fail(ANI_ERR_ARG, "unknown tree method %d", method);
+  if (nGenomes < 0 || nReplicates < 0) return fail(ANI_ERR_ARG, "negative count");
+  if (!(missingIdentity >= 0.0f && missingIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "missingIdentity %g outside [0, 100]", (double)missingIdentity);
+  if (method == ANI_TREE_SINGLE ? nGenomes > (1 << 30) : nGenomes > 65536)
+    return fail(ANI_ERR_LIMIT, "%d genomes: the tree takes at most %d", nGenomes, method == ANI_TREE_SINGLE ? 1 << 30 : 65536);
+  if (n > 0xfffffff0ull) return fail(ANI_ERR_LIMIT, "%zu rows: the pair sort takes fewer than 2^32 - 16", n);
+  for (size_t i = 0; i < n; i++) if (rows[i].qryGenomeId < 0 || rows[i].qryGenomeId >= nGenomes || rows[i].refGenomeId < 0 || rows[i].refGenomeId >= nGenomes)
+    return fail(ANI_ERR_ARG, "row %zu: genome id outside [0, %d)", i, nGenomes);
+  for (size_t i = 0; i < n * (size_t)nReplicates; i++) if (!(repIdentity[i] > 0.0f && repIdentity[i] <= 100.0f))
+    return fail(ANI_ERR_ARG, "repIdentity of row %zu, replicate %zu (%g) outside (0, 100]", i / (size_t)nReplicates, i % (size_t)nReplicates, (double)repIdentity[i]);
+  if (nGenomes <= 1) return ANI_OK;
+  try {
+    {                                                    // the main tree, as ani_tree_support will check it: before the first tree call
+      std::vector<uint8_t> used;
+      if (!is_tree(children, nGenomes, used)) return fail(ANI_ERR_ARG, "ani_tree_support_bootstrap: the main record list is not a tree");
+    }
+    const size_t M = (size_t)nGenomes - 1, B = (size_t)nReplicates;
+    std::vector<ani_cgi_t> rep(rows, rows + n);
+    std::vector<int32_t> repChildren(B * 2 * M);
+    std::vector<float> branch(2 * M);                    // heights or lengths: not used
+    for (size_t r = 0; r < B; r++) {
+      for (size_t i = 0; i < n; i++) rep[i].identity = repIdentity[i * B + r];
+      int32_t *ch = repChildren.data() + r * 2 * M;
+      if (method == ANI_TREE_AVERAGE) TRY(ani_tree_average(ctx, rep.data(), n, nGenomes, missingIdentity, ch, branch.data()));
+      else if (method == ANI_TREE_NJ) TRY(ani_tree_nj(ctx, rep.data(), n, nGenomes, missingIdentity, ch, branch.data()));
+      else TRY(ani_tree_single(ctx, rep.data(), n, nGenomes, missingIdentity, ch, branch.data(), nullptr));
+    }
+    return ani_tree_support(children, nGenomes, repChildren.data(), nReplicates, method == ANI_TREE_NJ, support);
+  } catch (const std::bad_alloc &) { return fail(ANI_ERR_NOMEM, "host allocation failed"); }
+}
+
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "kernels/profile.hpp"
 #include "kernels/fragdist.hpp"
 #include "kernels/ci.hpp"
+#include "kernels/boot.hpp"
 #include "kernels/hits.hpp"
 #include "kernels/synteny.hpp"
 #include "kernels/paint.hpp"
@@ -689,6 +690,108 @@ static int ci_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const PairArg
   return ANI_OK;
 }
 
+// The bootstrap replicate records of one (sub-batch, index chunk) (kernels/boot.hpp): ci_stage under this mode's
+// own gate, B and seed, with the intervals' flag, list and pool buffers (ci_stage, if it ran, has copied its last piece to the host) —
+// gate -> flags -> scan -> list, a second scan over the pool cells of the pairs above the LDS cap, then records and sums piece by piece:
+// a piece holds at most bootPiece records (by default as many as keep its sums within 2^28 bytes) and at most 64 pool cells per record
+// (of at most 2^18 records: the intervals' pool bound, whatever B),
+// ends at a pair border, and a larger pair is a piece of its own — through page-locked memory into ctx->bootStage, where collect_rows
+// finds them.  Only while the sketch has the mode on.
+static int boot_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const PairArgs &pa)
+{
+  const size_t nPairs = (size_t)pa.nQuery * (size_t)sk->nGenomes;
+  if (nPairs == 0) return ANI_OK;
+  CiArgs ca;
+  ca.nQuery = pa.nQuery; ca.nRefGenomes = sk->nGenomes; ca.bins = pa.bins; ca.binsPerQuery = pa.binsPerQuery; ca.genomeBinStart = sk->genomeBinStart;
+  ca.pairCount = pa.pairCount; ca.pairIdentity = pa.pairIdentity; ca.outStride = pa.outStride; ca.outCol0 = pa.outCol0;
+  ca.minIdBits = set->bootMinIdBits; ca.minFragments = set->bootMinFragments; ca.genomeBase = sk->g0;
+  const size_t B = set->bootReplicates;
+  ca.replicates = (uint32_t)B; ca.lowRank = 0; ca.highRank = 0; ca.seed = set->bootSeed;
+  ca.ldsCells = std::min<uint32_t>(ctx->bootLdsCells, (uint32_t)kCiLdsCells);
+  TRY(ctx->ciFlags.ensure(nPairs * 4)); TRY(ctx->ciOff.ensure(nPairs * 4));
+  hipLaunchKernelGGL(k_ci_flags, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ca, ctx->ciFlags.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  uint64_t listed = 0, poolTotal = 0;
+  TRY(device_scan(ctx, ctx->ciFlags.as<int32_t>(), ctx->ciOff.as<uint32_t>(), (uint32_t)nPairs, &listed));
+  if (listed == 0) return ANI_OK;
+  TRY(ctx->ciList.ensure((size_t)listed * 4)); TRY(ctx->ciPoolCells.ensure((size_t)listed * 4)); TRY(ctx->ciPoolOff.ensure((size_t)listed * 4));
+  hipLaunchKernelGGL(k_ci_list, dim3(grid_for(nPairs, kTPB)), dim3(kTPB), 0, ctx->stream, ca, (const int32_t *)ctx->ciFlags.as<int32_t>(),
+                     (const uint32_t *)ctx->ciOff.as<uint32_t>(), ctx->ciList.as<uint32_t>(), ctx->ciPoolCells.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  TRY(device_scan(ctx, ctx->ciPoolCells.as<int32_t>(), ctx->ciPoolOff.as<uint32_t>(), (uint32_t)listed, &poolTotal));
+  std::vector<uint32_t> poolOff;                       // only where a pair is above the cap: else every piece is `piece` records
+  if (poolTotal) {
+    poolOff.resize((size_t)listed + 1);
+    HIP_TRY(hipMemcpyAsync(poolOff.data(), ctx->ciPoolOff.p, (size_t)listed * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    poolOff[(size_t)listed] = (uint32_t)poolTotal;
+  }
+  const size_t cap = ctx->bootPiece ? (size_t)ctx->bootPiece : std::max<size_t>(1, ((size_t)1 << 28) / (B * 8));
+  const size_t piece = std::min<size_t>(cap, (size_t)listed);
+  const uint64_t poolPiece = (uint64_t)std::min<size_t>(cap, (size_t)1 << 18) * 64;      // (the intervals' bound, whatever B)
+  TRY(ctx->bootRec.ensure(piece * sizeof(BootRec))); TRY(ctx->bootSums.ensure(piece * B * 8));
+  uint8_t *host = nullptr;
+  TRY(pinned_buffer(ctx, 1, piece * (sizeof(BootRec) + B * 8), (void **)&host));
+  BootBuf &st = ctx->bootStage;
+  if (!st.reserve((size_t)listed, B)) return fail(ANI_ERR_NOMEM, "host allocation of %llu replicate records failed", (unsigned long long)listed);
+  static_assert(sizeof(BootRec) == sizeof(ani_boot_t), "the device record is the ABI's");
+  for (size_t a = 0; a < (size_t)listed;) {
+    size_t b = std::min(a + piece, (size_t)listed);
+    uint32_t poolBase = 0; size_t poolCells = 0;
+    if (poolTotal) {
+      b = a + 1;
+      while (b < a + piece && b < (size_t)listed && (uint64_t)poolOff[b + 1] - poolOff[a] <= poolPiece) b++;
+      poolBase = poolOff[a]; poolCells = poolOff[b] - poolOff[a];
+    }
+    const size_t n = b - a;
+    TRY(ctx->ciPool.ensure((poolCells ? poolCells : 1) * 4));     // (the stream is idle: the last piece has been copied)
+    hipLaunchKernelGGL(k_boot_records, dim3((unsigned)n), dim3(kTPB), 0, ctx->stream, ca, (const uint32_t *)ctx->ciList.as<uint32_t>(),
+                       (const uint32_t *)ctx->ciPoolOff.as<uint32_t>(), (uint32_t)a, (uint32_t)n, poolBase, ctx->ciPool.as<uint32_t>(), ctx->bootRec.as<BootRec>(),
+                       ctx->bootSums.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host, ctx->bootRec.p, n * sizeof(BootRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(host + piece * sizeof(BootRec), ctx->bootSums.p, n * B * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t slice = 1024, at = st.n;
+    parallel_for((n + slice - 1) / slice, (uint64_t)n * (sizeof(BootRec) + B * 8), [&](size_t i) {     // (into fresh pages: see fragdist_stage)
+      const size_t r0 = i * slice, m = std::min(slice, n - r0);
+      memcpy(st.rec + at + r0, host + r0 * sizeof(BootRec), m * sizeof(BootRec));
+      memcpy(st.sums + (at + r0) * B, host + piece * sizeof(BootRec) + r0 * B * 8, m * B * 8);
+    });
+    st.n += n;
+    a = b;
+  }
+  return ANI_OK;
+}
+
+// fragdist_distribute for the replicate records and their sums (`width` = replicates uint64 per record)
+template <class SlotOf, class Patch>
+static int boot_distribute(BootBuf &in, size_t width, size_t nq, bool ordered, SlotOf slot_of, Patch patch, BootBuf *out)
+{
+  const size_t n = in.n;
+  if (n == 0) return ANI_OK;
+  const size_t at = out->n;
+  if (ordered && at == 0) out->swap(in);
+  else {
+    if (!out->reserve(n, width)) return fail(ANI_ERR_NOMEM, "host allocation of %zu replicate records failed", n);
+    if (ordered) { memcpy(out->rec + at, in.rec, n * sizeof(ani_boot_t)); memcpy(out->sums + at * width, in.sums, n * width * 8); }
+    else {
+      std::vector<size_t> start(nq + 1, 0);
+      for (size_t r = 0; r < n; r++) start[slot_of(in.rec[r]) + 1]++;
+      for (size_t q = 0; q < nq; q++) start[q + 1] += start[q];
+      for (size_t r = 0; r < n; r++) {
+        const size_t to = at + start[slot_of(in.rec[r])]++;
+        out->rec[to] = in.rec[r];
+        memcpy(out->sums + to * width, in.sums + r * width, width * 8);
+      }
+    }
+    out->n = at + n;
+  }
+  for (size_t r = at; r < at + n; r++) patch(out->rec[r]);
+  in.clear();
+  return ANI_OK;
+}
+
 // The partial paint records of one (sub-batch, index chunk) (kernels/paint.hpp), from the candidates k_oneway_bins
 // read: best -> second over the candidates, flags -> scan for the mapped fragments' slots, then the records piece by piece (paintPiece
 // records per launch and copy) through page-locked memory into ctx->paintStage as one more part, where collect_rows finds them.  Only
@@ -952,6 +1055,10 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(ci_stage(ctx, set, sk, pa));
   }
+  if (set->boot) {
+    HIP_TRY(e1); HIP_TRY(hipGetLastError());
+    TRY(boot_stage(ctx, set, sk, pa));
+  }
   if (set->paint) {
     HIP_TRY(e1); HIP_TRY(hipGetLastError());
     TRY(paint_stage(ctx, sk, a, fs));
@@ -972,7 +1079,7 @@ int reduce_stage(ani_ctx *ctx, ani_sketch *set, IndexChunk *sk, const FragSet &f
 // default: this call has seen every chunk, the parts are joined into the sketch's pending list; synOut: as hitOut, for the synteny records)
 int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuery, int32_t firstQueryId, RowBuf *rows, const IndexChunk *block = nullptr,
     const int32_t *queryIds = nullptr, FragDistBuf *fdOut = nullptr, HitBuf *hitOut = nullptr, CiBuf *ciOut = nullptr, PaintParts *paintOut = nullptr,
-    SynBufs *synOut = nullptr)
+    SynBufs *synOut = nullptr, BootBuf *bootOut = nullptr)
 {
   const int32_t nCols = block ? block->nGenomes : set->nGenomes, col0 = (block ? block->g0 : 0) + set->refIdBase;
   const size_t nPairs = (size_t)nQuery * (size_t)nCols;
@@ -998,6 +1105,13 @@ int collect_rows(ani_ctx *ctx, ani_sketch *set, const FragSet &fs, int32_t nQuer
         [](const ani_ci_t &r) { return (size_t)r.qryGenomeId; },
         [&](ani_ci_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
         ciOut ? ciOut : &set->ciPending));
+  }
+  if (set->boot) {
+    const int32_t base = set->refIdBase;
+    TRY(boot_distribute(ctx->bootStage, (size_t)set->bootReplicates, (size_t)nQuery, block || set->chunks.size() == 1,
+        [](const ani_boot_t &r) { return (size_t)r.qryGenomeId; },
+        [&](ani_boot_t &r) { r.qryGenomeId = firstQueryId + (queryIds ? queryIds[r.qryGenomeId] : r.qryGenomeId); r.refGenomeId += base; },
+        bootOut ? bootOut : &set->bootPending));
   }
   if (set->paint) {
     // per fragment, not per pair: ids first, then (all chunks seen) the join of the chunks' parts
@@ -1110,6 +1224,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
   std::vector<FragDistBuf> fdPart(sk->fragdist ? sub.size() : 0);       // the fragment distribution records take the rows' way
   std::vector<HitBuf> hitPart(sk->hits ? sub.size() : 0);               // ... and so do the best-hit records
   std::vector<CiBuf> ciPart(sk->ci ? sub.size() : 0);                   // ... and the interval records
+  std::vector<BootBuf> bootPart(sk->boot ? sub.size() : 0);              // ... and the replicate records with their sums
   std::vector<PaintParts> paintPart(sk->paint ? sub.size() : 0);        // the paint records: a part per chunk, joined per sub-batch at the end
   std::vector<SynBufs> synPart(sk->synteny ? sub.size() : 0);           // the synteny records take the best-hit records' way
   for (size_t c = 0; c < sk->chunks.size(); c++) {
@@ -1122,7 +1237,7 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
       TRY(reduce_stage(ctx, sk, ch, sb.v, nCand, sb.g1 - sb.g0, true));
       TRY(collect_rows(ctx, sk, sb.v, sb.g1 - sb.g0, sb.firstQueryId, &part[i], ch, sb.queryIds, sk->fragdist ? &fdPart[i] : nullptr,
           sk->hits ? &hitPart[i] : nullptr, sk->ci ? &ciPart[i] : nullptr, sk->paint ? &paintPart[i] : nullptr,
-          sk->synteny ? &synPart[i] : nullptr));
+          sk->synteny ? &synPart[i] : nullptr, sk->boot ? &bootPart[i] : nullptr));
     }
   }
   // a sub-batch's rows are (chunk, query, reference)-ordered and a chunk's references all precede the next chunk's: a stable
@@ -1173,6 +1288,13 @@ int map_fragsets(ani_ctx *ctx, ani_sketch *sk, const std::vector<const ani_frags
     TRY(hits_distribute(ciPart[i], (size_t)nq, sk->chunks.size() == 1, [&](const ani_ci_t &r) {
           return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
         [](ani_ci_t &) {}, &sk->ciPending));
+  }
+  for (size_t i = 0; i < bootPart.size(); i++) {
+    const int32_t q0 = sub[i].firstQueryId, nq = sub[i].g1 - sub[i].g0;
+    const int32_t *ids = sub[i].queryIds;
+    TRY(boot_distribute(bootPart[i], (size_t)sk->bootReplicates, (size_t)nq, sk->chunks.size() == 1, [&](const ani_boot_t &r) {
+          return ids ? (size_t)(std::lower_bound(ids, ids + nq, r.qryGenomeId - q0) - ids) : (size_t)(r.qryGenomeId - q0); },
+        [](ani_boot_t &) {}, &sk->bootPending));
   }
   for (size_t i = 0; i < paintPart.size(); i++) TRY(paint_join(paintPart[i], &sk->paintPending));
   for (size_t i = 0; i < synPart.size(); i++) {
@@ -1354,12 +1476,14 @@ static int reduce_mapping_list(ani_ctx *ctx, ani_sketch *sk, const ani_mapping_t
     TRY(reduce_stage(ctx, sk, sk->chunks[c], fs, (int32_t)nc, nQuery));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // the next chunk reuses the candidate buffers
   }
-  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n, pt0 = sk->paintPending.n, sy0 = sk->synPending.pairs.n;
+  const size_t m0 = rows->n, fd0 = sk->fdPending.n, h0 = sk->hitPending.n, ci0 = sk->ciPending.n, pt0 = sk->paintPending.n, sy0 = sk->synPending.pairs.n,
+               bt0 = sk->bootPending.n;
   TRY(collect_rows(ctx, sk, fs, nQuery, firstQueryId, rows));
   if (sk->refIdBase) for (size_t i = m0; i < rows->n; i++) rows->p[i].refGenomeId -= sk->refIdBase;      // collect_rows adds it for the batch entry points
   if (sk->refIdBase) for (size_t i = fd0; i < sk->fdPending.n; i++) sk->fdPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = h0; i < sk->hitPending.n; i++) sk->hitPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = ci0; i < sk->ciPending.n; i++) sk->ciPending.rec[i].refGenomeId -= sk->refIdBase;
+  if (sk->refIdBase) for (size_t i = bt0; i < sk->bootPending.n; i++) sk->bootPending.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = sy0; i < sk->synPending.pairs.n; i++) sk->synPending.pairs.rec[i].refGenomeId -= sk->refIdBase;
   if (sk->refIdBase) for (size_t i = pt0; i < sk->paintPending.n; i++) {
     ani_paint_t &r = sk->paintPending.rec[i];
@@ -1767,6 +1891,45 @@ int ani_sketch_ci_end(ani_sketch *sk)
   if (!sk->ci) return fail(ANI_ERR_ARG, "ani_sketch_ci_end without ani_sketch_ci_begin");
   sk->ciPending.clear(); sk->ctx->ciStage.clear();
   sk->ci = false;
+  return ANI_OK;
+}
+
+// ---- bootstrap replicate records (ani_abi.h: ani_sketch_boot_begin) ----
+int ani_sketch_boot_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, int32_t replicates, uint32_t seed)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!(minIdentity >= 0.0f && minIdentity <= 100.0f)) return fail(ANI_ERR_ARG, "minIdentity %g outside [0, 100]", (double)minIdentity);
+  if (minFragments < 1) return fail(ANI_ERR_ARG, "minFragments %d below 1", minFragments);
+  if (replicates < 1 || replicates > kCiMaxReplicates) return fail(ANI_ERR_ARG, "%d replicates: 1 to %d are taken", replicates, kCiMaxReplicates);
+  memcpy(&sk->bootMinIdBits, &minIdentity, 4);
+  if (minIdentity == 0.0f) sk->bootMinIdBits = 0;                  // -0.0 counts as 0
+  sk->bootMinFragments = (uint32_t)minFragments;
+  sk->bootReplicates = (uint32_t)replicates; sk->bootSeed = seed;
+  sk->bootPending.clear(); sk->ctx->bootStage.clear();
+  sk->boot = true;
+  return ANI_OK;
+}
+
+int ani_sketch_boot_take(ani_sketch *sk, ani_boot_t **rec, uint64_t **sums, size_t *n)
+{
+  if (!sk || !rec || !n) return fail(ANI_ERR_ARG, "null argument");
+  if (!sk->boot) return fail(ANI_ERR_ARG, "ani_sketch_boot_take without ani_sketch_boot_begin");
+  *rec = nullptr; *n = 0;
+  if (sums) *sums = nullptr;
+  BootBuf &pd = sk->bootPending;
+  if (pd.n == 0) { pd.clear(); return ANI_OK; }
+  *rec = pd.rec; *n = pd.n;                     // the buffers themselves: ani_free releases them
+  if (sums) *sums = pd.sums; else free(pd.sums);
+  pd.rec = nullptr; pd.sums = nullptr; pd.n = pd.cap = 0;
+  return ANI_OK;
+}
+
+int ani_sketch_boot_end(ani_sketch *sk)
+{
+  if (!sk) return fail(ANI_ERR_ARG, "null sketch");
+  if (!sk->boot) return fail(ANI_ERR_ARG, "ani_sketch_boot_end without ani_sketch_boot_begin");
+  sk->bootPending.clear(); sk->ctx->bootStage.clear();
+  sk->boot = false;
   return ANI_OK;
 }
 

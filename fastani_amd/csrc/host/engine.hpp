@@ -462,6 +462,30 @@ struct RecBuf {
 };
 using HitBuf = RecBuf<ani_hit_t>;
 using CiBuf = RecBuf<ani_ci_t>;
+// the bootstrap replicate records on the host (ani_sketch_boot_begin; kernels/boot.hpp): rec[i] with its `width` = replicates sums at
+// sums[i * width], as FragDistBuf keeps the distributions' histograms; ani_sketch_boot_take hands the two buffers to the caller as they are
+struct BootBuf {
+  ani_boot_t *rec = nullptr; uint64_t *sums = nullptr; size_t n = 0, cap = 0;
+  BootBuf() = default;
+  BootBuf(const BootBuf &) = delete;
+  BootBuf &operator=(const BootBuf &) = delete;
+  ~BootBuf() { clear(); }
+  bool reserve(size_t extra, size_t width)              // room for `extra` more records; false: out of memory (the buffer stays as it was)
+  {
+    if (n + extra <= cap && rec && sums) return true;
+    const size_t want = std::max<size_t>(n + extra, cap + cap / 2 + 1024);
+    if (want > SIZE_MAX / (width * 8)) return false;
+    void *r = realloc(rec, want * sizeof(ani_boot_t));
+    if (!r) return false;
+    rec = (ani_boot_t *)r;
+    void *h = realloc(sums, want * width * 8);
+    if (!h) return false;
+    sums = (uint64_t *)h; cap = want;
+    return true;
+  }
+  void swap(BootBuf &o) { std::swap(rec, o.rec); std::swap(sums, o.sums); std::swap(n, o.n); std::swap(cap, o.cap); }
+  void clear() { free(rec); free(sums); rec = nullptr; sums = nullptr; n = cap = 0; }
+};
 // the per-fragment records of the paint mode (ani_sketch_paint_begin; kernels/paint.hpp).  PaintParts: the partial records of ONE
 // sub-batch, one part per index chunk (part k = rec[cut[k] .. cut[k + 1]), each in (query, querySeqId) order), until ani_paint_merge
 // joins them
@@ -565,6 +589,13 @@ struct ani_ctx {
   CiBuf ciStage;
   uint32_t ciPiece = 1u << 18;            // records per launch and copy, and 64 pool cells per record (env ANI_TEST_CI_PIECE, tests)
   uint32_t ciLdsCells = 2560 /* ani::kCiLdsCells */;    // cells of a pair kept in LDS (env ANI_TEST_CI_LDS_CELLS lowers it, tests)
+  // bootstrap replicate records (only while a sketch has them on): the flags, offsets, list and pool are the intervals' buffers above —
+  // ci_stage has copied its last piece to the host when boot_stage starts —, one piece of records and of sums on the device, and the
+  // records reduce_stage has staged for the sub-batch's collect_rows (query = index in the sub-batch)
+  DevBuf bootRec, bootSums;
+  BootBuf bootStage;
+  uint32_t bootPiece = 0;                 // records per launch and copy; 0: 2^28 bytes of sums (env ANI_TEST_BOOT_PIECE, tests)
+  uint32_t bootLdsCells = 2560 /* ani::kCiLdsCells */;  // cells of a pair kept in LDS (env ANI_TEST_BOOT_LDS_CELLS lowers it, tests)
   // paint records (only while a sketch has them on): the per-fragment state of a (sub-batch, chunk) — best and second key, genome count,
   // winning candidate: 24 bytes per fragment —, the flags and slots of the mapped fragments, one piece of records on the device, and the
   // partial records reduce_stage has staged for the sub-batch's collect_rows, one part per chunk (query = index in the sub-batch)
@@ -648,6 +679,10 @@ struct ani_sketch {
   // of the fragment distributions' records to `ciPending`, which ani_sketch_ci_take hands over
   bool ci = false; uint32_t ciMinIdBits = 0, ciMinFragments = 1, ciReplicates = 200, ciLevel = 950, ciSeed = 1;
   CiBuf ciPending;
+  // bootstrap replicate records (ani_sketch_boot_begin .. _end): reduce_stage makes a record and `bootReplicates` sums per gated pair
+  // while they are on; they take the way of the fragment distributions' records to `bootPending`, which ani_sketch_boot_take hands over
+  bool boot = false; uint32_t bootMinIdBits = 0, bootMinFragments = 1, bootReplicates = 100, bootSeed = 1;
+  BootBuf bootPending;
   // paint records (ani_sketch_paint_begin .. _end): reduce_stage makes a partial record per mapped fragment of every (sub-batch, chunk)
   // while they are on; collect_rows gives them the rows' ids, ani_paint_merge joins the chunks' parts, and the joined records wait in
   // `paintPending` for ani_sketch_paint_take

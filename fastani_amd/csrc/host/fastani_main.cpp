@@ -6,7 +6,9 @@
 // cgi::computeGenomeLengths :48-92), same log lines, error messages and exit codes.  `--cluster T` (extension) adds a .clusters file
 // (greedy species clusters over the .matrix cells, ani_cluster_greedy), `--tree` (extension) a .newick file (their average-linkage
 // tree, ani_tree_average, with `--treeMethod nj` their neighbour-joining tree, ani_tree_nj, or with `--treeMethod single` their
-// single-linkage tree and, in a .mst file, their minimum spanning tree, ani_tree_single).  `--sketchANI` (extension) adds a .sketch
+// single-linkage tree and, in a .mst file, their minimum spanning tree, ani_tree_single; with `--treeSupport B` a .support and a
+// .support.newick file: how many of B bootstrap replicate trees hold each merge, ani_sketch_boot_begin + ani_tree_support_bootstrap).
+// `--sketchANI` (extension) adds a .sketch
 // file (the whole-genome sketch estimate between the genomes, ani_sketch_signatures + ani_signature_pairs), `--treeFill sketch` gives the
 // tree that estimate for the pairs without a .matrix cell (streamed through ani_tree_single_sketch for a single-linkage tree of more
 // than 65 536 genomes), `--sketchNeighbors K` a .neighbors file (the K nearest genomes of every genome under that estimate,
@@ -94,6 +96,7 @@ struct Options {
   float hitsMinANI = 0.0f; int hitsMinFragments = 1;   // --hitsMinANI, --hitsMinFragments: the pairs that get lines (ani_sketch_hits_begin's gate)
   bool synteny = false;                                // --synteny: the .synteny and .synblocks files, the order of the hits behind every -o line
   float syntenyMinANI = 0.0f; int syntenyMinFragments = 1;   // --syntenyMinANI, --syntenyMinFragments: the pairs that get lines (ani_sketch_synteny_begin's gate)
+  int treeSupport = 0; uint32_t treeSupportSeed = 1;   // --treeSupport B, --treeSupportSeed: bootstrap support of the tree's clades (.support, .support.newick)
   bool ci = false;                                     // --ci: the .ci file, a bootstrap interval beside the ANI of every -o line
   int ciReplicates = 200, ciLevelPermille = 950; uint32_t ciSeed = 1;   // --ciReplicates, --ciLevel (percent), --ciSeed (ani_sketch_ci_begin)
   float ciMinANI = 0.0f; int ciMinFragments = 1;       // --ciMinANI, --ciMinFragments: the pairs that get a line (its gate)
@@ -119,7 +122,8 @@ struct Options {
     "SYNOPSIS\n"
     "     " << argv0 << " [-h] [-r <value>] [--rl <value>] [-q <value>] [--ql <value>] [-k <value>] [-t <value>]\n"
     "             [--fragLen <value>] [--minFraction <value>] [--maxRatioDiff <value>] [--visualize] [--matrix] [--cluster <value>]\n"
-    "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
+    "             [--tree] [--treeMethod <value>] [--treeFill <value>] [--treeSupport <value>] [--treeSupportSeed <value>]\n"
+    "             [--sketchANI] [--sketchSize <value>] [--sketchMinANI <value>]\n"
     "             [--sketchNeighbors <value>] [--sketchScreen <value>] [--sketchContain <value>] [--sketchCluster <value>]\n"
     "             [--sketchGraph <value>] [--profile] [--profileMinANI <value>] [--profileMinFragments <value>]\n"
     "             [--fragDist] [--fragDistEdges <a,b,...>] [--fragDistMinANI <value>] [--fragDistMinFragments <value>]\n"
@@ -225,6 +229,10 @@ struct Options {
     "                 cut at another origin shows one break.  Host memory: 48 bytes per pair and 32 per block\n"
     "     --syntenyMinANI <value>  only the pairs from this ANI on get lines (0 <= value <= 100) [default : 0, every line of the output]\n"
     "     --syntenyMinFragments <value>  ... and from this many matched fragments on (>= 1) [default : 1]\n"
+    "     --treeSupport <value>  with --tree: bootstrap support of the tree's clades over that many replicates, 1 to 1024, each the same\n"
+    "                 tree method over ANI values resampled from the pairs' fragment identities (the draws of --ci); writes\n"
+    "                 <output>.support (a count per merge) and <output>.support.newick (the tree with percentages) [default : none]\n"
+    "     --treeSupportSeed <value>  seed of the draws (a 32-bit number) [default : 1]\n"
     "     --ci  also write <output>.ci: a percentile bootstrap interval of every ANI value, resampled from the fragment identities it is\n"
     "           the mean of.  Line 1 is \"#replicates<TAB>B<TAB>level<TAB>L<TAB>seed<TAB>s\"; then per line of the output, in its order:\n"
     "           query, reference, ANI, low, high, fragments\n"
@@ -271,6 +279,7 @@ Options parse(int argc, char **argv)
   bool profileMinANI = false, profileMinFragments = false;
   bool fragDistEdges = false, fragDistMinANI = false, fragDistMinFragments = false, hitsMinANI = false, hitsMinFragments = false,
        syntenyMinANI = false, syntenyMinFragments = false;
+  bool treeSupportSeed = false;
   const char *ciSub = nullptr;                         // the first --ci sub-option seen
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) usage(argv[0], 1); return argv[++i]; };
   for (int i = 1; i < argc; i++) {
@@ -342,6 +351,12 @@ Options parse(int argc, char **argv)
       if (!(o.hitsMinANI >= 0.0f && o.hitsMinANI <= 100.0f)) { std::cerr << "ERROR, --hitsMinANI takes an ANI in [0, 100]" << std::endl; exit(1); } }
     else if (a == "--hitsMinFragments") { o.hitsMinFragments = atoi(need(i)); hitsMinFragments = true;
       if (o.hitsMinFragments < 1) { std::cerr << "ERROR, --hitsMinFragments takes a count of at least 1" << std::endl; exit(1); } }
+    else if (a == "--treeSupport") { char *end = nullptr; const char *t = need(i); const long v = strtol(t, &end, 10);
+      if (!*t || !end || *end || v < 1 || v > 1024) { std::cerr << "ERROR, --treeSupport takes a replicate count in 1 .. 1024" << std::endl; exit(1); }
+      o.treeSupport = (int)v; }
+    else if (a == "--treeSupportSeed") { char *end = nullptr; const char *t = need(i); const unsigned long long v = strtoull(t, &end, 10); treeSupportSeed = true;
+      if (!*t || *t == '-' || !end || *end || v > 0xffffffffull) { std::cerr << "ERROR, --treeSupportSeed takes a number in 0 .. 4294967295" << std::endl; exit(1); }
+      o.treeSupportSeed = (uint32_t)v; }
     else if (a == "--ci") o.ci = true;
     else if (a == "--ciReplicates") { o.ciReplicates = atoi(need(i)); if (!ciSub) ciSub = "--ciReplicates";
       if (o.ciReplicates < 1 || o.ciReplicates > 1024) { std::cerr << "ERROR, --ciReplicates takes a count in 1 .. 1024" << std::endl; exit(1); } }
@@ -371,6 +386,8 @@ Options parse(int argc, char **argv)
   if (help) usage(argv[0], 0);
   if (version) { std::cerr << "version 1.33\n\n"; exit(0); }                         // parseCmdArgs.hpp:194-198
   if (treeMethod && !o.tree) { std::cerr << "ERROR, --treeMethod needs --tree" << std::endl; exit(1); }
+  if (o.treeSupport && !o.tree) { std::cerr << "ERROR, --treeSupport needs --tree" << std::endl; exit(1); }
+  if (treeSupportSeed && !o.treeSupport) { std::cerr << "ERROR, --treeSupportSeed needs --treeSupport" << std::endl; exit(1); }
   if (treeFill && !o.tree) { std::cerr << "ERROR, --treeFill needs --tree" << std::endl; exit(1); }
   if (sketchSize && !o.signatures()) { std::cerr << "ERROR, --sketchSize needs --sketchANI or --treeFill sketch" << std::endl; exit(1); }
   if (sketchMinANI && !o.sketchANI && !o.sketchNeighbors && !o.sketchScreen) { std::cerr << "ERROR, --sketchMinANI needs --sketchANI" << std::endl; exit(1); }
@@ -999,6 +1016,36 @@ struct CiTable {
 };
 CiTable g_ci;
 
+// --treeSupport: the bootstrap replicate identities (ani_sketch_boot_begin, gate open; rule 3 of the boot records) of the pairs, keyed by
+// (query, reference) file index as the intervals are.  Begun and drained where the profile is; the sums are released as soon as they are
+// floats: 4 B bytes per row.
+struct BootTable {
+  bool on = false; int32_t replicates = 100; uint32_t seed = 1;
+  std::vector<float> id;                                   // [records][replicates]
+  std::unordered_map<uint64_t, size_t> at;                 // (query << 32 | reference) -> record
+  void init(const Options &o) { on = o.treeSupport > 0; replicates = o.treeSupport; seed = o.treeSupportSeed; }
+  void begin(ani_sketch *sk) const
+  {
+    if (on && ani_sketch_boot_begin(sk, 0.0f, 1, replicates, seed)) {
+      std::cerr << "ERROR, ani_sketch_boot_begin: " << ani_last_error() << std::endl; exit(1); }
+  }
+  void take(ani_sketch *sk, const std::function<size_t(int32_t)> &refOf)
+  {
+    if (!on) return;
+    ani_boot_t *r = nullptr; uint64_t *sums = nullptr; size_t n = 0;
+    if (ani_sketch_boot_take(sk, &r, &sums, &n)) { std::cerr << "ERROR, ani_sketch_boot_take: " << ani_last_error() << std::endl; exit(1); }
+    const size_t B = (size_t)replicates, first = id.size() / B;
+    id.resize((first + n) * B);
+    for (size_t i = 0; i < n; i++) {
+      at[((uint64_t)(uint32_t)r[i].qryGenomeId << 32) | (uint32_t)refOf(r[i].refGenomeId)] = first + i;
+      const double den = (double)r[i].count * 1048576.0;
+      for (size_t k = 0; k < B; k++) id[(first + i) * B + k] = (float)((double)sums[i * B + k] / den);
+    }
+    ani_free(r); ani_free(sums);
+  }
+};
+BootTable g_boot;
+
 // --sketchANI / --treeFill sketch / --sketchNeighbors need every .matrix genome to be a reference of the run (the signatures come from the reference sketch),
 // and the pair step takes 65 536 genomes: refused here, before anything is read, sketched or mapped.  The single-linkage tree alone has
 // no ceiling: its sketch pairs are streamed (write_tree_single_streamed), and neither have the neighbour lists (write_neighbors).
@@ -1007,6 +1054,7 @@ void check_sketch_genomes(const Options &o)
   std::unordered_set<std::string> refs(o.refs.begin(), o.refs.end());
   if (refs.size() > 65536 && o.pairStep()) {
     std::cerr << "ERROR, --sketchANI and --treeFill sketch take at most 65536 genomes, this run has " << refs.size() << std::endl; exit(1); }
+  if (refs.size() > 65536 && o.treeSupport) { std::cerr << "ERROR, --treeSupport takes at most 65536 genomes" << std::endl; exit(1); }
   for (auto &q : o.queries)
     if (!refs.count(q)) {
       std::cerr << "ERROR, --sketchANI" << (o.sketchNeighbors ? ", --sketchNeighbors" : "") << (o.sketchCluster > 0.0f ? ", --sketchCluster" : "")
@@ -1279,6 +1327,7 @@ struct Streaming {
     g_paint.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_synteny.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
     g_ci.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
+    g_boot.take(shard[d].sk, [g0](int32_t g) { return (size_t)(g0 + g); });
   }
 
   // every device sketches its run of the reference slices into its shard's tables and record parts (all-vs-all: the query sets too)
@@ -1373,7 +1422,7 @@ struct Streaming {
         for (auto &pt : sh.parts) if (pt.rec) { ani_device_free(su.dev[d].ctx, pt.rec); pt.rec = nullptr; }
         return "";
       });
-    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); g_paint.begin(shard[d].sk);
+    for (int d = 0; d < nDev; d++) { g_profile.begin(shard[d].sk); g_fragdist.begin(shard[d].sk); g_hits.begin(shard[d].sk); g_ci.begin(shard[d].sk); g_boot.begin(shard[d].sk); g_paint.begin(shard[d].sk);
       g_synteny.begin(shard[d].sk); }
     if (o.signatures()) {
       for (int d = 0; d < nDev; d++)                                  // (a block that comes round again with the next wave has been seen)
@@ -1605,7 +1654,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     if (ani_sketch_build(ctx, &ap, &rb, &sk)) die("ani_sketch_build");
     uint64_t occ = 0, uniq = 0, tot = 0;
     if (ani_sketch_stats(sk, &occ, &uniq, &tot, nullptr, nullptr)) die("ani_sketch_stats");
-    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk); g_paint.begin(sk); g_synteny.begin(sk);
+    g_profile.begin(sk); g_fragdist.begin(sk); g_hits.begin(sk); g_ci.begin(sk); g_boot.begin(sk); g_paint.begin(sk); g_synteny.begin(sk);
     if (o.signatures()) {                                               // the split's genome g is reference refIdx[g]
       SigTable part; part.init(g_sigs.size, refIdx.size());
       part.collect(sk, 0, refIdx.size());
@@ -1666,6 +1715,7 @@ void run_split(const Options &o, const ani_params_t &ap, ani_ctx *ctx, GenomeLen
     g_paint.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_synteny.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     g_ci.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
+    g_boot.take(sk, [&](int32_t g) { return (size_t)refIdx[(size_t)g]; });
     ani_sketch_destroy(sk);
   }
   for (int sp = 0; sp < nSplits; sp++) std::cerr << "INFO [thread " << sp << "], skch::main, ready to exit the loop" << std::endl;
@@ -1894,7 +1944,8 @@ void write_paint(const Options &o, const ani_params_t &ap, GenomeLengths &length
 // The cells of the .matrix, shared by the .clusters writer so that the two files never disagree: genomes numbered queries first, then
 // references not seen yet (first occurrence wins, :353-380); every trusted row that is not a self row becomes a (row > column, identity)
 // cell, in result order.
-struct MatrixCells { std::vector<std::string> names; std::vector<Cell> cells; };
+// (from: with --treeSupport, per cell the (query << 32 | reference) file indices of its row, the key of its replicate identities)
+struct MatrixCells { std::vector<std::string> names; std::vector<Cell> cells; std::vector<uint64_t> from; };
 
 MatrixCells matrix_cells(const Options &o, const std::vector<ani_cgi_t> &rows, const Trusted &trusted)
 {
@@ -1911,6 +1962,7 @@ MatrixCells matrix_cells(const Options &o, const std::vector<ani_cgi_t> &rows, c
       if (a == b) continue;
       if (a < b) std::swap(a, b);
       mc.cells.push_back(Cell{a, b, e.identity});
+      if (g_boot.on) mc.from.push_back(((uint64_t)(uint32_t)e.qryGenomeId << 32) | (uint32_t)e.refGenomeId);
     }
   return mc;
 }
@@ -1957,8 +2009,57 @@ std::vector<ani_cgi_t> tree_rows(const MatrixCells &mc, const std::vector<Cell> 
   return rows;
 }
 
-// a linkage (children, height: scipy form) as newick
-void write_linkage(const std::string &path, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<float> &height)
+// <output>.newick -> <output>.support
+std::string support_path(const std::string &newick) { return newick.substr(0, newick.size() - 7) + ".support"; }
+
+// ---- --treeSupport: .support and .support.newick.  The support of the tree's records over the replicate trees
+// (ani_tree_support_bootstrap on the first device): every cell takes the replicate identities of the row it came from, in the cells'
+// order, so that the cells of a pair are folded as the main tree folds them; a fill cell keeps its value in every replicate.
+std::vector<uint32_t> tree_support(ani_ctx *ctx, int32_t method, const MatrixCells &mc, const std::vector<ani_cgi_t> &rows, const std::vector<int32_t> &children)
+{
+  const size_t B = (size_t)g_boot.replicates, n = mc.names.size();
+  std::vector<float> rep(rows.size() * B);
+  for (size_t i = 0; i < rows.size(); i++) {
+    const auto it = i < mc.from.size() ? g_boot.at.find(mc.from[i]) : g_boot.at.end();
+    if (it == g_boot.at.end()) std::fill(rep.begin() + (std::ptrdiff_t)(i * B), rep.begin() + (std::ptrdiff_t)((i + 1) * B), rows[i].identity);
+    else std::copy(g_boot.id.begin() + (std::ptrdiff_t)(it->second * B), g_boot.id.begin() + (std::ptrdiff_t)((it->second + 1) * B), rep.begin() + (std::ptrdiff_t)(i * B));
+  }
+  std::vector<float>().swap(g_boot.id);
+  std::vector<uint32_t> support(n > 1 ? n - 1 : 0);
+  if (ani_tree_support_bootstrap(ctx, method, rows.data(), rows.size(), (int32_t)n, 0.0f, rep.data(), (int32_t)B, children.data(), support.data()))
+    die("ani_tree_support_bootstrap");
+  trace("tree support counted");
+  return support;
+}
+
+// the label of a node: the integer percentage of its support, rounded half up
+unsigned support_percent(uint32_t support) { const unsigned B = (unsigned)g_boot.replicates; return (200u * support + B) / (2u * B); }
+
+// .support: "#replicates B seed s method m", then per record in record order: s, its two children (a leaf's .matrix name, #k for the node
+// of record k), the leaves below it, its support
+void write_support(const std::string &path, const char *method, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<uint32_t> &support)
+{
+  const int n = (int)mc.names.size();
+  BufferedFile f(path);
+  f.out << "#replicates\t" << g_boot.replicates << "\tseed\t" << g_boot.seed << "\tmethod\t" << method << "\n";
+  std::vector<int32_t> leaves((size_t)(n > 0 ? 2 * n - 1 : 0), 1);
+  for (size_t s = 0; s < support.size(); s++) {
+    leaves[(size_t)n + s] = leaves[(size_t)children[2 * s]] + leaves[(size_t)children[2 * s + 1]];
+    f.out << s;
+    for (int k = 0; k < 2; k++) {
+      const int c = children[2 * s + (size_t)k];
+      if (c < n) f.out << "\t" << mc.names[(size_t)c]; else f.out << "\t#" << (c - n);
+    }
+    f.out << "\t" << leaves[(size_t)n + s] << "\t" << support[s] << "\n";
+  }
+  f.out.close();
+  if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
+  trace("tree support written");
+}
+
+// a linkage (children, height: scipy form) as newick; with `support`, every inner node below the root carries its percentage
+void write_linkage(const std::string &path, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<float> &height,
+                   const std::vector<uint32_t> *support = nullptr)
 {
   const int n = (int)mc.names.size();
   BufferedFile f(path);
@@ -1973,7 +2074,11 @@ void write_linkage(const std::string &path, const MatrixCells &mc, const std::ve
     const size_t s = (size_t)(fr.node - n);
     const int child = fr.phase == 0 ? -1 : children[2 * s + (size_t)fr.phase - 1];
     if (fr.phase > 0) { snprintf(len, sizeof len, "%.9g", (h(fr.node) - h(child)) / 2); f.out << ':' << len; }
-    if (fr.phase == 2) { f.out << ')'; stack.pop_back(); continue; }
+    if (fr.phase == 2) {
+      f.out << ')';
+      if (support && stack.size() > 1) f.out << support_percent((*support)[s]);
+      stack.pop_back(); continue;
+    }
     f.out << (fr.phase == 0 ? '(' : ',');
     stack.back().phase++;
     stack.push_back(Frame{children[2 * s + (size_t)fr.phase], 0});
@@ -1990,9 +2095,14 @@ void write_tree(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, co
   const size_t m = n > 1 ? (size_t)n - 1 : 0;
   std::vector<int32_t> children(2 * m); std::vector<float> height(m);
   if (ani_tree_average(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data())) die("ani_tree_average");
-  std::vector<ani_cgi_t>().swap(rows);
+  if (!g_boot.on) std::vector<ani_cgi_t>().swap(rows);
   write_linkage(path, mc, children, height);
   trace("tree written");
+  if (g_boot.on) {
+    const std::vector<uint32_t> support = tree_support(ctx, ANI_TREE_AVERAGE, mc, rows, children);
+    write_support(support_path(path), "average", mc, children, support);
+    write_linkage(support_path(path) + ".newick", mc, children, height, &support);
+  }
 }
 
 // ---- .newick with --treeMethod single: the single-linkage tree of the cells (ani_tree_single on the first device, a pair without cells at
@@ -2008,9 +2118,15 @@ void write_tree_single(const std::string &path, const std::string &mstPath, ani_
   const size_t m = n > 1 ? (size_t)n - 1 : 0;
   std::vector<int32_t> children(2 * m), edges(2 * m); std::vector<float> height(m);
   if (ani_tree_single(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), height.data(), edges.data())) die("ani_tree_single");
-  std::vector<ani_cgi_t>().swap(rows);
+  if (!g_boot.on) std::vector<ani_cgi_t>().swap(rows);
   write_linkage(path, mc, children, height);
   trace("tree written");
+  if (g_boot.on) {
+    const std::vector<uint32_t> support = tree_support(ctx, ANI_TREE_SINGLE, mc, rows, children);
+    write_support(support_path(path), "single", mc, children, support);
+    write_linkage(support_path(path) + ".newick", mc, children, height, &support);
+  }
+  std::vector<ani_cgi_t>().swap(rows);
   write_mst(mstPath, mc, edges, height, fill);
 }
 
@@ -2044,6 +2160,9 @@ void write_mst(const std::string &mstPath, const MatrixCells &mc, const std::vec
 // ---- .newick with --treeMethod nj: the neighbour-joining tree of the cells (ani_tree_nj on the first device, a pair without cells at
 // identity 0).  The tree is unrooted, so the top is the customary trifurcation: the two children of the last join and the node
 // that remained beside it, whose branch is the sum of the last record's two lengths.  Branch lengths are ani_tree_nj's, unclamped.
+void write_nj_newick(const std::string &path, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<float> &length,
+                     const std::vector<uint32_t> *support = nullptr);
+
 void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc, const std::vector<Cell> &fill)
 {
   const int n = (int)mc.names.size();
@@ -2051,7 +2170,22 @@ void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc,
   const size_t m = n > 1 ? (size_t)n - 1 : 0;
   std::vector<int32_t> children(2 * m); std::vector<float> length(2 * m);
   if (ani_tree_nj(ctx, rows.data(), rows.size(), n, 0.0f, children.data(), length.data())) die("ani_tree_nj");
-  std::vector<ani_cgi_t>().swap(rows);
+  if (!g_boot.on) std::vector<ani_cgi_t>().swap(rows);
+  write_nj_newick(path, mc, children, length);
+  trace("tree written");
+  if (g_boot.on) {
+    const std::vector<uint32_t> support = tree_support(ctx, ANI_TREE_NJ, mc, rows, children);
+    write_support(support_path(path), "nj", mc, children, support);
+    write_nj_newick(support_path(path) + ".newick", mc, children, length, &support);
+  }
+}
+
+// (with `support`, every inner node below the three top branches carries its percentage)
+void write_nj_newick(const std::string &path, const MatrixCells &mc, const std::vector<int32_t> &children, const std::vector<float> &length,
+                     const std::vector<uint32_t> *support)
+{
+  const int n = (int)mc.names.size();
+  const size_t m = n > 1 ? (size_t)n - 1 : 0;
   BufferedFile f(path);
   char len[64];
   auto put_length = [&](double x) { snprintf(len, sizeof len, "%.9g", x); f.out << ':' << len; };
@@ -2084,7 +2218,8 @@ void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc,
         stack.push_back(Frame{children[s], 0, (double)length[s]});
         continue;
       }
-      if (fr.node < n) write_newick_name(f.out, mc.names[(size_t)fr.node]); else f.out << ')';
+      if (fr.node < n) write_newick_name(f.out, mc.names[(size_t)fr.node]);
+      else { f.out << ')'; if (support) f.out << support_percent((*support)[(size_t)(fr.node - n)]); }
       put_length(fr.length);
       stack.pop_back();
       if (!stack.empty() && stack.back().phase == 0) f.out << ',';   // a sibling follows (a parent, phase 1, closes its bracket)
@@ -2094,7 +2229,6 @@ void write_tree_nj(const std::string &path, ani_ctx *ctx, const MatrixCells &mc,
   f.out << ";\n";
   f.out.close();
   if (f.out.fail()) { std::cerr << "ERROR, could not write " << path << std::endl; exit(1); }
-  trace("tree written");
 }
 
 // ---- --sketchANI / --treeFill sketch: the whole-genome sketch estimate between the .matrix genomes (ani_signature_pairs on the first
@@ -2400,7 +2534,7 @@ int main(int argc, char **argv)
   ani_params_t ap;
   if (ani_params_default(&ap, o.kmerSize, o.fragLen)) die("parameters");
   if (o.signatures()) g_sigs.init(o.sketchSize, o.refs.size());
-  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o); g_paint.init(o); g_synteny.init(o);
+  g_profile.init(o); g_fragdist.init(o); g_hits.init(o); g_ci.init(o); g_boot.init(o); g_paint.init(o); g_synteny.init(o);
   const Mode m = check_options(o, ap);
   GenomeLengths lengths(ap.fragLen);
   lengths.keepContigs = o.hits || o.paint || o.synteny;
@@ -2431,7 +2565,8 @@ int main(int argc, char **argv)
   if (o.cluster > 0.0f) write_clusters(o.out + ".clusters", su.dev[0].ctx, o.cluster, mc);
   std::vector<Cell> fill;
   const char *streamEnv = getenv("ANI_TEST_CLI_SINGLE_STREAM");
-  const bool streamed = o.streamable() && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
+  // (--treeSupport needs the fill cells on the host, so it takes the pair step's way; beyond its 65 536 genomes it was refused before mapping)
+  const bool streamed = o.streamable() && !o.treeSupport && (mc.names.size() > 65536 || (streamEnv && atoi(streamEnv) == 1));
   if ((o.sketchANI || o.treeFill) && !streamed) fill = sketch_pairs(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchNeighbors) write_neighbors(o, su.dev[0].ctx, ap.kmerSize, mc);
   if (o.sketchCluster > 0.0f) write_sketch_clusters(o, su.dev[0].ctx, ap.kmerSize, mc);

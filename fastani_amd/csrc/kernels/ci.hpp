@@ -64,6 +64,50 @@ __device__ __forceinline__ unsigned long long ci_replicate(const uint32_t *f, ui
   return s;
 }
 
+// The non-empty cells of genome g's bins for query qi, in bin order -> F[0 .. count) in sF, or in gF for a pair above the cap (`big`,
+// block-uniform), with the minimum and the maximum of the cells' bits and the sum of the F, the same in every thread on return: a slab
+// of 256 bins per turn, the next slab's load in flight over the barrier.  For a workgroup of kTPB threads, all of them (barriers inside);
+// the cells are visible to every thread on return.  Shared with kernels/boot.hpp.
+__device__ __forceinline__ void ci_gather(const CiArgs &a, int qi, int g, uint32_t count, bool big, uint32_t *gF, uint32_t *sF,
+                                          uint32_t (*sCnt)[kTPB / kWave], uint32_t *sMin, uint32_t *sMax, unsigned long long *sSum,
+                                          uint32_t &mn, uint32_t &mx, unsigned long long &sum)
+{
+  const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wv = t >> 6;
+  const uint32_t *b = a.bins + (size_t)qi * a.binsPerQuery;
+  const uint32_t xg = a.genomeBinStart[g], x1 = a.genomeBinStart[g + 1];
+  uint32_t at = 0, turn = 0;
+  mn = 0xffffffffu; mx = 0; sum = 0;
+  uint32_t next = (xg + t < x1) ? b[xg + t] : 0u;
+  for (uint32_t x0 = xg; x0 < x1; x0 += kTPB, turn ^= 1u) {       // block-uniform bounds
+    const uint32_t bits = next;
+    next = (x1 - x0 > (uint32_t)kTPB + t) ? b[x0 + kTPB + t] : 0u;
+    const unsigned long long m = __ballot(bits != 0);
+    if (lane == 0) sCnt[turn][wv] = (uint32_t)__popcll(m);
+    __syncthreads();                                    // (sCnt[turn] is written again two turns on, behind the next turn's barrier)
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)(kTPB / kWave); w++) { const uint32_t c = sCnt[turn][w]; before += w < wv ? c : 0u; all += c; }
+    const uint32_t slot = at + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (bits && slot < count) {                         // (slot < count always: countSeq is the number of these cells)
+      const uint32_t f = (uint32_t)llrint((double)__uint_as_float(bits) * 1048576.0);
+      if (big) gF[slot] = f; else sF[slot] = f;
+      mn = bits < mn ? bits : mn; mx = bits > mx ? bits : mx; sum += f;
+    }
+    at += all;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t omn = __shfl_xor(mn, d), omx = __shfl_xor(mx, d);
+    const unsigned long long os = __shfl_xor(sum, d);
+    mn = omn < mn ? omn : mn; mx = omx > mx ? omx : mx; sum += os;
+  }
+  if (lane == 0) { sMin[wv] = mn; sMax[wv] = mx; sSum[wv] = sum; }
+  __syncthreads();                                      // the workgroup's own writes to the pool are visible to it behind the barrier
+  sum = 0;
+#pragma unroll
+  for (int w = 0; w < kTPB / kWave; w++) { mn = sMin[w] < mn ? sMin[w] : mn; mx = sMax[w] > mx ? sMax[w] : mx; sum += sSum[w]; }
+}
+
 // pair index p = query * nRefGenomes + genome of the chunk
 static __global__ __launch_bounds__(kTPB) void k_ci_flags(CiArgs a, int32_t *__restrict__ flags)
 {
@@ -95,47 +139,16 @@ static __global__ __launch_bounds__(kTPB) void k_ci_records(CiArgs a, const uint
   __shared__ uint32_t sCnt[2][kTPB / kWave], sMin[kTPB / kWave], sMax[kTPB / kWave];
   const uint32_t r = blockIdx.x;
   if (r >= n) return;                                   // block-uniform
-  const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wv = t >> 6;
+  const uint32_t t = threadIdx.x;
   const uint32_t p = list[first + r];
   const int qi = (int)(p / (uint32_t)a.nRefGenomes), g = (int)(p % (uint32_t)a.nRefGenomes);
   const uint32_t count = a.pairCount[(size_t)qi * (size_t)a.outStride + (size_t)a.outCol0 + (size_t)g];   // = the non-empty cells of g
   const bool big = count > a.ldsCells;                  // block-uniform
   uint32_t *gF = pool + (big ? poolOff[first + r] - poolBase : 0u);
 
-  // the cells in bin order -> F[0 .. count): a slab of 256 bins per turn, the next slab's load in flight over the barrier
-  const uint32_t *b = a.bins + (size_t)qi * a.binsPerQuery;
-  const uint32_t xg = a.genomeBinStart[g], x1 = a.genomeBinStart[g + 1];
-  uint32_t at = 0, mn = 0xffffffffu, mx = 0, turn = 0;
-  unsigned long long sum = 0;
-  uint32_t next = (xg + t < x1) ? b[xg + t] : 0u;
-  for (uint32_t x0 = xg; x0 < x1; x0 += kTPB, turn ^= 1u) {       // block-uniform bounds
-    const uint32_t bits = next;
-    next = (x1 - x0 > (uint32_t)kTPB + t) ? b[x0 + kTPB + t] : 0u;
-    const unsigned long long m = __ballot(bits != 0);
-    if (lane == 0) sCnt[turn][wv] = (uint32_t)__popcll(m);
-    __syncthreads();                                    // (sCnt[turn] is written again two turns on, behind the next turn's barrier)
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)(kTPB / kWave); w++) { const uint32_t c = sCnt[turn][w]; before += w < wv ? c : 0u; all += c; }
-    const uint32_t slot = at + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (bits && slot < count) {                         // (slot < count always: countSeq is the number of these cells)
-      const uint32_t f = (uint32_t)llrint((double)__uint_as_float(bits) * 1048576.0);
-      if (big) gF[slot] = f; else sF[slot] = f;
-      mn = bits < mn ? bits : mn; mx = bits > mx ? bits : mx; sum += f;
-    }
-    at += all;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t omn = __shfl_xor(mn, d), omx = __shfl_xor(mx, d);
-    const unsigned long long os = __shfl_xor(sum, d);
-    mn = omn < mn ? omn : mn; mx = omx > mx ? omx : mx; sum += os;
-  }
-  if (lane == 0) { sMin[wv] = mn; sMax[wv] = mx; sSum[wv] = sum; }
-  __syncthreads();                                      // the workgroup's own writes to the pool are visible to it behind the barrier
-  sum = 0;
-#pragma unroll
-  for (int w = 0; w < kTPB / kWave; w++) { mn = sMin[w] < mn ? sMin[w] : mn; mx = sMax[w] > mx ? sMax[w] : mx; sum += sSum[w]; }
+  uint32_t mn, mx;
+  unsigned long long sum;
+  ci_gather(a, qi, g, count, big, gF, sF, sCnt, sMin, sMax, sSum, mn, mx, sum);
 
   const uint32_t B = a.replicates;
   unsigned long long lowSum = sum, highSum = sum;

@@ -461,6 +461,32 @@ int ani_sketch_ci_begin(ani_sketch *sk, float minIdentity, int32_t minFragments,
 int ani_sketch_ci_take(ani_sketch *sk, ani_ci_t **rec, size_t *n);
 int ani_sketch_ci_end(ani_sketch *sk);
 
+/* ---- the bootstrap replicate sums of the ANI values as records (what the intervals draw and reduce to two order statistics, kept: the
+ * input of the trees' support values, ani_tree_support_bootstrap).  Between begin and end every call that reduces
+ * against the sketch (the calls of the profile's rule 5; ani_map_query adds nothing) appends one record and `replicates` sums per
+ * contributing pair to two lists on the host, which take hands over.  Everything is integer and the intervals' stated hash.
+ *  1. Values, gate, draws: the intervals' rule 1 word for word, their rule 2 (with this mode's own minIdentity and minFragments) and their
+ *     rule 3.  sums[i * B + r] is exactly the S[r] of that rule for pair i, r in 0 .. B - 1, in replicate order, not sorted; sum is the
+ *     sum of the F.  A pair whose cells are all bit-equal has S[r] = sum for every r; count = 1 is that case.
+ *  2. Consistency with the intervals.  With the same seed and B, the sorted S at lowRank and highRank of the intervals' rule 4 equal
+ *     ani_ci_t.lowSum and highSum of the same pair, and sum equals ani_ci_t.sum.
+ *  3. Replicate identity, computed by the caller and stated once: id_r = (float)((double) S[r] / ((double) count * 1048576.0)), the
+ *     formula of the intervals' rule 4.
+ *  4. Ids and order: the rows', as the intervals' rule 5.
+ *  5. Independence.  Rows are untouched.  Every other mode can be on beside it, the intervals included; each has its own gate, B and seed.
+ *  6. Determinism.  Nothing depends on schedule, sub-batch size, index chunking, residency or piece size.
+ * begin starts (a second begin drops what is pending and takes the new gate, B and seed).  take hands over everything appended since
+ * begin or the last take and empties the lists: rec[n] and sums[n * replicates], each released with ani_free; an empty list comes back
+ * NULL with 0 (sums may be null: the sums are then dropped).  24 + 8 B bytes per record of host memory until taken; the device holds one
+ * piece, at most 2^28 bytes of sums.  end releases (ani_sketch_destroy does too).  ANI_ERR_ARG: a null sketch (or rec or n), a gate
+ * outside its ranges (NaN included), replicates outside 1 .. 1024, take or end without a begin; a refused begin leaves a running mode as
+ * it was.  ANI_ERR_NOMEM: the records do not fit the host, or the device cannot hold a piece.  After a call that failed while reducing,
+ * the pending lists are unspecified until the next begin. */
+typedef struct { int32_t refGenomeId, qryGenomeId; uint32_t count, replicates; uint64_t sum; } ani_boot_t;   /* 24 bytes */
+int ani_sketch_boot_begin(ani_sketch *sk, float minIdentity, int32_t minFragments, int32_t replicates /* 1..1024 */, uint32_t seed);
+int ani_sketch_boot_take(ani_sketch *sk, ani_boot_t **rec, uint64_t **sums /* [n][replicates] */, size_t *n);
+int ani_sketch_boot_end(ani_sketch *sk);
+
 /* ---- the best reference of every query fragment over the whole reference set ("genome painting"; no counterpart in the reference, whose
  * outputs are all per pair of genomes).  Between begin and end every call that reduces against the sketch (the
  * calls of the profile's rule 5; ani_map_query adds nothing) appends one record per mapped query fragment to a list on the host, which
@@ -616,6 +642,42 @@ int ani_tree_nj(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes,
 int ani_tree_single(ani_ctx *ctx, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
                     int32_t *children, float *height, int32_t *edges);
 int ani_tree_single_rounds(const ani_ctx *ctx);
+
+/* ---- clade support of a tree over replicate trees (no counterpart in the reference).  A pure host function:
+ * no context.
+ *  1. Inputs.  Every tree is in the record form ani_tree_average, ani_tree_single and ani_tree_nj return: record s names two node ids, a
+ *     leaf's id is its index, record s creates node nGenomes + s.  L(leaf) = {leaf}; L(nGenomes + s) is the union of the leaf sets of the
+ *     record's two nodes, for every record, NJ's last one included.  children: 2 (nGenomes - 1) ids, the main tree; repChildren:
+ *     nReplicates such lists one after the other.
+ *  2. Rooted (unrooted = 0; average, single).  support[s] = the number of replicates that have a node u with L(u) = L(nGenomes + s).  The
+ *     last record's set is all leaves: its support is nReplicates.
+ *  3. Unrooted (unrooted != 0; NJ).  A node stands for the split {L, all \ L}: support[s] = the number of replicates with a node u,
+ *     leaves included, where L(u) = L(v) or L(u) = all \ L(v), v = nGenomes + s.  Splits with |L| >= nGenomes - 1 are trivial and get
+ *     nReplicates.  The same unrooted tree written with another last join therefore gets full support.
+ *  4. Exact: integers, no hashing of leaf sets.  Leaves are numbered in the main tree's traversal order, so a main clade is an interval
+ *     of numbers; a replicate node matches iff max - min + 1 = size and that interval is a main clade's (Day 1985), looked up in the sorted
+ *     list of the main clades' intervals: O(nGenomes log nGenomes) per replicate, the records walked in their order: no recursion,
+ *     whatever the depth.
+ *  5. nGenomes <= 1: ANI_OK, nothing is read or written.  nReplicates = 0: every support is 0.  ANI_ERR_ARG: a null pointer, a negative
+ *     count, or a record list that is not a tree (an id outside [0, nGenomes + s) in record s, or an id used twice).  ANI_ERR_NOMEM: host. */
+int ani_tree_support(const int32_t *children, int32_t nGenomes, const int32_t *repChildren /* [nReplicates][2 (nGenomes - 1)] */,
+                     int32_t nReplicates, int32_t unrooted, uint32_t *support /* [nGenomes - 1] */);
+
+/* ---- bootstrap support of an ANI tree: the composition, bit for bit, of nReplicates tree calls and ani_tree_support.  For r in
+ * 0 .. nReplicates - 1 the method's entry point (ANI_TREE_AVERAGE: ani_tree_average, ANI_TREE_NJ: ani_tree_nj, ANI_TREE_SINGLE:
+ * ani_tree_single) runs on the rows with identity := repIdentity[i * nReplicates + r] for row i; then ani_tree_support runs on `children`
+ * — the caller's main tree, normally the same entry point's over the rows as they are — and the nReplicates results, unrooted for NJ.
+ * repIdentity comes from ani_sketch_boot_take by the boot records' rule 3, joined to the rows by the caller.  A row that no replicate
+ * record covers (a fill row, a row below the boot gate) gets its own identity in every column: it does not vary.  The argument checks
+ * and limits are the tree calls' own; a repIdentity outside (0, 100] (NaN included), nReplicates < 0 or an unknown method is ANI_ERR_ARG;
+ * all checks run before any tree is made or any device memory taken (the check of `children` takes 2 nGenomes bytes of the host).  nGenomes <= 1: ANI_OK, nothing is read or written.  Host: a copy of the rows and
+ * nReplicates record lists. */
+#define ANI_TREE_AVERAGE 0
+#define ANI_TREE_NJ 1
+#define ANI_TREE_SINGLE 2
+int ani_tree_support_bootstrap(ani_ctx *ctx, int32_t method, const ani_cgi_t *rows, size_t n, int32_t nGenomes, float missingIdentity,
+                               const float *repIdentity /* [n][nReplicates] */, int32_t nReplicates,
+                               const int32_t *children, uint32_t *support /* [nGenomes - 1] */);
 
 /* ---- whole-genome sketch ANI: a Mash-style estimate between the reference genomes from the minimizers the sketch already holds (no
  * counterpart in the reference, which emits no row below about 80 % identity).  The smallest k-mer hashes of a

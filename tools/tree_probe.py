@@ -17,6 +17,10 @@ includes the upload, the matrix, every merge launch and the read-back.
                                                strip kept; beside it ani_signature_pairs + the fill rule + ani_tree_single on the same
                                                input, up to --compose-max genomes (default 10 000: the composition brings every pair
                                                that shares a value to the host, 1.5 * 10^9 rows at 65 536), and the two results compared
+    python tools/tree_probe.py --support 100   ani_tree_support_bootstrap (section 2.29) per method on species 1000 and species 10000 at
+                                               that many replicates, beside B times the plain call, one upload of the rows' bytes and
+                                               ani_tree_support alone; --support-budget S leaves out what B plain calls would take
+                                               longer than (default 60 s)
     python tools/tree_probe.py --reps 1        timed calls per row set (default 3)
     python tools/tree_probe.py --cli 1000      in addition: fastANI --ql L --rl L --tree on that many 5 Mbp genomes, the
                                                ANI_CLI_TRACE marks of the run ("rows ordered" -> "tree written" is the tree's share)
@@ -189,6 +193,61 @@ def time_single_sketch(e, rows, n, sig, length, reps=3, compose=True):
     return line
 
 
+def support_run(e, rng, replicates, only, reps, budget_s):
+    """--support B: ani_tree_support_bootstrap per method at 1000 and 10 000 genomes beside B times the plain tree call and the support
+    count alone, with the time one plain host-to-device copy of the rows' bytes takes — an estimate of the share B uploads of the same
+    ids have in the composed call; the engine's own upload goes through page-locked staging and feeds a sort, and is not timed apart.  The
+    replicate identities are the rows' own moved by up to 0.5.  A size whose B plain calls would pass --support-budget seconds is left out
+    and said so."""
+    import torch
+    from cluster_probe import species_rows
+    from fastani_amd.api import tree_support
+    for n, n_rows in ((1000, 10 ** 5), (10000, 10 ** 6)):
+        if not ("species %d" % n).startswith(only):
+            continue
+        rows = species_rows(rng, n, n_rows)
+        rep = np.clip(rows["identity"][:, None] + rng.uniform(-0.5, 0.5, (len(rows), replicates)).astype(np.float32), 1.0, 100.0).astype(np.float32)
+        raw = torch.from_numpy(rows.view(np.uint8).copy())
+        up = []
+        for _ in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            raw.to("cuda:0")
+            torch.cuda.synchronize()
+            up.append((time.perf_counter() - t0) * 1e3)
+        up_ms = float(np.median(up[1:]))
+        for method in ("average", "nj", "single"):
+            call = {"average": e.tree_average, "nj": e.tree_nj, "single": e.tree_single}[method]
+            main = call(rows, n)
+            children = (main[0] if method == "nj" else main[:, 0:2]).astype(np.int32)
+            plain = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                call(rows, n)
+                plain.append((time.perf_counter() - t0) * 1e3)
+            pm = float(np.median(plain))
+            head = "species %-6d rows %9d genomes %6d %-7s B %d   plain call %.2f ms, B of them %.1f ms; one plain host-to-device copy of the rows' bytes (%.1f MB; an estimate of the engine's upload, which also stages and sorts) %.3f ms, B of them %.1f ms" % (
+                n, len(rows), n, method, replicates, pm, pm * replicates, rows.nbytes / 1e6, up_ms, up_ms * replicates)
+            if pm * replicates / 1e3 > budget_s:
+                print(head + "   composed call NOT RUN: past the budget of %g s" % budget_s, flush=True)
+                continue
+            ms = []
+            for _ in range(max(1, min(reps, int(budget_s * 1e3 / (pm * replicates))))):
+                t0 = time.perf_counter()
+                support = e.tree_support_bootstrap(method, rows, n, rep, children)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            med = float(np.median(ms))
+            same = [children] * replicates
+            t0 = time.perf_counter()
+            tree_support(children, same, method == "nj", lib=e.lib)
+            count_ms = (time.perf_counter() - t0) * 1e3
+            print(head + "   ani_tree_support_bootstrap %s ms (median %.1f = %.2f x B plain calls; the copies, by that estimate, %.1f %% of it)   ani_tree_support alone over B trees %.2f ms"
+                  "   support min %d median %d max %d" % (" ".join("%.1f" % x for x in ms), med, med / (pm * replicates), 100.0 * up_ms * replicates / med, count_ms,
+                                                           int(support.min()), int(np.median(support)), int(support.max())), flush=True)
+        del rows, rep
+    return 0
+
+
 def cli_run(n):
     import bench
     import orc
@@ -228,6 +287,9 @@ def main():
     method = sys.argv[sys.argv.index("--method") + 1] if "--method" in sys.argv else "average"
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
     assert method in ("average", "nj", "single", "single-sketch"), method
+    if "--support" in sys.argv:
+        budget = float(sys.argv[sys.argv.index("--support-budget") + 1]) if "--support-budget" in sys.argv else 60.0
+        return support_run(e, rng, int(sys.argv[sys.argv.index("--support") + 1]), only, reps, budget)
     if method == "single-sketch":
         compose_max = int(sys.argv[sys.argv.index("--compose-max") + 1]) if "--compose-max" in sys.argv else 10000
         for n in (1000, 10000, 65536, 90000):
